@@ -11,11 +11,16 @@ N > 1: `python bench.py --gpus N` with no rank environment starts the N ranks it
 N = 1 line); under torch.distributed.run it joins the ranks it is given. After the timed loop every rank hashes its replica state: `config.replicas_bit_identical`,
 `config.exchange` (peer write-through | peer fences | rccl), `config.exchange_soak`; a peer-window run that expired a wait or left the replicas apart is re-timed on RCCL.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HIP-event timed on the launch stream; whole-update `hbm_frac` / `fp32_frac` at its top level) and,
-at N=1, `cpu_baseline` = the reference's OWN code timed live on this host's cores (oracle/_ref: its three hot-path modules byte-compiled from /root/reference by
+A plain run (`python bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times exactly N steps (`--repeats R`: R passes of N steps, their median) and prints ONE
+JSON line (rank 0): `metric`, `value` (updates/s), `unit`, `higher_is_better`, `dtype`, `ms_per_step` (milliseconds of one timed step) and the configuration.
+`--dump-outputs DIR` writes, after the timed steps, what the timed update computed in its last step as DIR/<name>.npy (see dump_outputs()).
+
+`--full` adds everything else to that line: `roofline` (dominant kernel, from device stamps or HIP events on the launch stream; whole-update `hbm_frac` / `fp32_frac` at its
+top level) and, at N=1, `cpu_baseline` = the reference's OWN code timed live on this host's cores (oracle/_ref: its three hot-path modules byte-compiled from the reference by
 __graft_entry__.build(), run by oracle/ref_cpu_baseline.py in a subprocess at 1 / 8 / all threads, with and without memory.sample; only when oracle/_ref is absent the
 committed build-container measurement profiles/cpu_reference.json stands in, and `where` says so) next to `cpu_port` = the numpy oracle port timed live;
-`population` = the aggregate rate of 128 independent learners (two sub-populations of 64) advanced by the same launches; `secondary` = the other single-GPU configurations of BASELINE.json.
+`population` = the aggregate rate of 128 independent learners (two sub-populations of 64) advanced by the same launches; `secondary` = the other single-GPU configurations of BASELINE.json;
+at N > 1 the A/B of the two gradient exchanges and the N = 1 schedule timed in the same job.
 """
 import argparse
 import ctypes as C
@@ -240,6 +245,23 @@ def secondary(device, plan, nets):
 def _lib_mod():
   from imitation_learning_amd import _lib
   return _lib
+
+
+def dump_outputs(out_dir, plan, nets):
+  """What the timed update handed its caller in the last timed step, one DIR/<name>.npy each (float32; the index draws as float64, exact): the two index draws, the
+  relabelled rewards, the policy's log-probabilities and the twin-critic values of the batch, and the learner state the update advanced (actor, critic, target critic,
+  log alpha, discriminator and its spectral-norm vectors). About 1.5 MB in all. Call after a synchronize."""
+  os.makedirs(out_dir, exist_ok=True)
+  actor, critic, target, log_alpha, disc = nets
+  arrays = dict(agent_indices=(plan.idx, np.float64), expert_indices=(plan.eidx, np.float64), rewards=(plan.rewards, np.float32), log_prob=(plan.logp, np.float32),
+                q=(plan.q, np.float32), actor=(actor.flat, np.float32), critic=(critic.flat, np.float32), target_critic=(target.flat, np.float32),
+                log_alpha=(log_alpha, np.float32), discriminator=(disc.flat, np.float32), discriminator_spectral_norm=(disc.sn, np.float32))
+  total = 0
+  for name, (t, dtype) in arrays.items():
+    a = t.detach().cpu().numpy().astype(dtype)
+    total += a.nbytes
+    np.save(os.path.join(out_dir, name + '.npy'), a)
+  assert total <= 64 << 20, f'--dump-outputs wrote {total} bytes'
 
 
 def cpu_baseline(tr, et, budget_s=12.0):
@@ -536,9 +558,12 @@ def main():
   ap.add_argument('--gpus', type=int, default=1)
   ap.add_argument('--steps', type=int, default=2000)
   ap.add_argument('--warmup', type=int, default=200)
-  ap.add_argument('--repeats', type=int, default=5, help='timed repeats; `value` is their median (SURVEY.md 8d)')
-  ap.add_argument('--min-seconds', type=float, default=0.2, help='a timed repeat runs max(--steps, enough replays for this many seconds)')
-  ap.add_argument('--stamp-bursts', type=int, default=20, help='extra untimed bursts of 50 replays after the timed repeats, each read for its launch stamps')
+  ap.add_argument('--full', action='store_true', help='also measure everything beyond the headline: roofline, population, secondary configurations, CPU baselines; '
+                                                      'at N > 1 the exchange A/B and the N = 1 schedule in the same job')
+  ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed steps, write what the last timed update computed as DIR/<name>.npy')
+  ap.add_argument('--repeats', type=int, default=1, help='timed repeats of --steps steps each; `value` is their median (SURVEY.md 8d)')
+  ap.add_argument('--min-seconds', type=float, default=0.0, help='if > 0, a timed repeat runs max(--steps, enough replays for this many seconds)')
+  ap.add_argument('--stamp-bursts', type=int, default=20, help='--full: extra untimed bursts of 50 replays after the timed repeats, each read for its launch stamps')
   ap.add_argument('--no-pmc', action='store_true', help='do not attach roofline.traffic from profiles/pmc_latest.json (what the counter-collecting passes themselves run with)')
   ap.add_argument('--no-graph', action='store_true', help='eager launches instead of hipGraph replay')
   ap.add_argument('--launch', choices=('graph', 'direct'), default=os.environ.get('IL_BENCH_LAUNCH', 'direct'), help='how the timed single-GPU updates are issued: UpdatePlan.launch_direct (the two branches as direct launches: two library calls per update, no hipGraph; the default since round 5: 17.5k against 16.6k updates/s on one box, profiles/r05_launch_ab.txt) or two hipGraph replays per update')
@@ -603,6 +628,19 @@ def main():
       dist.barrier()
       torch.cuda.synchronize()
 
+  def timed(step, n):
+    """n steps between two barrier + synchronize brackets; seconds, max over ranks."""
+    t0 = time.perf_counter()
+    for _ in range(n):
+      step()
+    barrier()
+    t = torch.tensor([time.perf_counter() - t0], device=device if backend == 'nccl' else 'cpu', dtype=torch.float64)
+    if world > 1:
+      dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    return float(t.item())
+
+  stamped = args.full and args.learners == 1   # launch-stamp readings for the roofline (--full)
+
   def measure():
     """warm-up (eager, then captured), the timed repeats, max over ranks. Returns (median seconds of a repeat, launch mode, timing record)."""
     beat('eager warm-up')
@@ -642,32 +680,26 @@ def main():
       step()
     barrier()
 
-    def timed(n):
-      """n steps between two barrier + synchronize brackets; seconds, max over ranks."""
-      t0 = time.perf_counter()
-      for _ in range(n):
-        step()
-      barrier()
-      t = torch.tensor([time.perf_counter() - t0], device=device if backend == 'nccl' else 'cpu', dtype=torch.float64)
-      if world > 1:
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-      return float(t.item())
-
     beat('timed region')
-    # `--steps` replays alone can be a ~1 ms window (the driver's --steps 20): every repeat times max(--steps, enough replays for --min-seconds), sized from one pass
-    # of --steps (max over ranks, so every rank computes the same count); `value` = the median of --repeats such repeats.
-    probe = timed(args.steps)
-    n = max(args.steps, int(np.ceil(args.min_seconds / max(probe / args.steps, 1e-9))))
+    # every repeat times exactly --steps steps; --min-seconds > 0 stretches a repeat to max(--steps, enough replays for that many seconds), sized from one untimed pass
+    # of --steps (max over ranks, so every rank computes the same count); `value` = the median of --repeats repeats.
+    n, probe = args.steps, None
+    if args.min_seconds > 0:
+      probe = timed(step, args.steps)
+      n = max(args.steps, int(np.ceil(args.min_seconds / max(probe / args.steps, 1e-9))))
     reps, stamps = [], []
-    stamped = args.learners == 1
     if stamped: _lib.check(_lib.lib().il_kernel_stamps_clear())
     for _ in range(max(1, args.repeats)):
-      reps.append(timed(n))
+      reps.append(timed(step, n))
       if stamped and rank == 0: stamps.append(stamp_sample(_lib))   # the last replay's launches, read outside the timed bracket
+    if args.dump_outputs and rank == 0:   # what the last timed step computed (a later measurement of the same job overwrites it), before any untimed replay below
+      dump_outputs(args.dump_outputs, plan, nets)
     for _ in range(args.stamp_bursts if stamped else 0):   # more readings of the same schedule: short bursts of back-to-back replays (untimed), the last replay of each is read
-      timed(min(n, 50))
+      timed(step, min(n, 50))
       if rank == 0: stamps.append(stamp_sample(_lib))
-    return float(np.median(reps)), launch, dict(timed_replays=n, repeats=len(reps), repeat_seconds=[round(r, 6) for r in reps], probe_seconds=round(probe, 6), stamps=stamps)
+    timing = dict(timed_replays=n, repeats=len(reps), repeat_seconds=[round(r, 6) for r in reps], stamps=stamps)
+    if probe is not None: timing['probe_seconds'] = round(probe, 6)
+    return float(np.median(reps)), launch, timing
 
   def health():
     """Collective verdict on the run just timed: (ok on every rank, replicas bit-identical, digests, note)."""
@@ -687,7 +719,7 @@ def main():
   # inside the optimiser launches where the schedule allows - then, from rank 0's replica state, torch.distributed all-reduces (RCCL). `value` is the better of the runs
   # that passed the post-run check (no expired wait, replicas bit-identical); config.exchange names it, config.exchange_ab carries both.
   exchange_ab = None
-  if world > 1 and getattr(runner, 'peer', None) is not None and ok and same and os.environ.get('IL_BENCH_EXCHANGE_AB', '1') != '0':
+  if args.full and world > 1 and getattr(runner, 'peer', None) is not None and ok and same and os.environ.get('IL_BENCH_EXCHANGE_AB', '1') != '0':
     first = dict(exchange=runner.exchange_name(), updates_per_s=round(world * steps_timed / elapsed, 1), ms_per_step=round(elapsed / steps_timed * 1e3, 5), launch=launch,
                  replicas_bit_identical=same, replica_digests=[d[:16] for d in digests], exchange_soak=getattr(runner.peer, 'soak_report', None), valid=True)
     peer_form = getattr(runner.peer, 'form', 0)
@@ -726,7 +758,7 @@ def main():
   beat('reporting')
 
   single = None
-  if world > 1 and os.environ.get('IL_BENCH_SINGLE', '1') != '0':
+  if args.full and world > 1 and os.environ.get('IL_BENCH_SINGLE', '1') != '0':
     # The N = 1 schedule (one GPU's own update plan: no split path, no exchange) timed on every rank at the same time, each on its own GPU and its own fresh learner, in this
     # same job: data-parallel efficiency = (value / n_gpus) / config.single_gpu_same_job.updates_per_s is computable from this one line.
     beat('N = 1 schedule, same job')
@@ -750,9 +782,10 @@ def main():
     # ---- per-kernel durations: device stamps taken inside the timed graph replays (il_kernel_stamps). Schedules whose kernels carry no stamps (IL_PAIR=0, shapes outside
     # pair mode, --no-graph --no-overlap runs under a counter-collecting profiler) fall back to HIP events around eager launches of the same kernels.
     samples = [sm for sm in timing['stamps'] if 'k_sac_chain_pair' in sm and 'k_policy_critic_pair' in sm and 'k_dw_adam_actor' in sm]
-    if samples and world == 1:
+    roof = None
+    if args.full and samples and world == 1:
       roof = roofline_from_stamps(samples, ms_per_step, use_pmc=not args.no_pmc)
-    else:
+    elif args.full:
       # (traced with the index draw stream-ordered ahead of the forward / critic-loss launch: with the resident draw that launch is dispatched while the draw is still
       #  waiting for the previous update, so its HIP-event window would include that wait instead of its own work; both schedules are bit-identical)
       fused_desc, plan.peer_desc = getattr(plan, 'peer_desc', None), None   # (data-parallel runs: the per-kernel windows are taken on this rank's plain single-GPU launches - the fused exchange lives on the resident-sampler schedule only, and rank 0 alone runs this section)
@@ -762,7 +795,8 @@ def main():
       plan.peer_desc = fused_desc
       if samples:   # N > 1: rank 0's stamps of the data-parallel launches, beside the eager windows of its single-GPU launches
         roof['stamped_kernels_data_parallel'] = roofline_from_stamps(samples, ms_per_step, use_pmc=False)['kernels']
-    roof['timing'] = {k: v for k, v in timing.items() if k != 'stamps'}
+    if roof is not None:
+      roof['timing'] = {k: v for k, v in timing.items() if k != 'stamps'}
 
     out = dict(metric='SAC+GAIL grad-updates/sec (batch 256, HalfCheetah dims)', value=round(ups, 1), unit='updates/s', n_gpus=world, steps=args.steps, warmup=args.warmup, timed_replays=steps_timed, repeats=timing['repeats'],
                ms_per_step=round(ms_per_step, 5), higher_is_better=True, scaling='weak', vs_baseline=None, dtype='f32', data='synthetic',
@@ -779,11 +813,12 @@ def main():
                            replicas_bit_identical=(same if runner is not plan else None), replica_digests=([d[:16] for d in digests] if runner is not plan else None),
                            branch_sync=('device counters (two graphs, no cross-stream edge)' if getattr(plan, 'device_sync', False) and runner is plan else 'stream dependencies'),
                            rows=('read from the rings through the drawn indices (il_batch.gather); reward relabel as a role of k_sac_chain_pair (16-wave schedule: inline in the critic-loss workgroups)' if getattr(plan, 'inline_relabel', False) and runner is plan
-                                 else ('read from the rings through the drawn indices (il_batch.gather)' if getattr(plan, 'ring_mode', False) and runner is plan else 'gathered by k_gather2'))),
-               roofline=roof)
+                                 else ('read from the rings through the drawn indices (il_batch.gather)' if getattr(plan, 'ring_mode', False) and runner is plan else 'gathered by k_gather2'))))
+    if roof is not None:
+      out['roofline'] = roof
     out['config']['handoffs'] = ('in-launch hand-offs between the two streams: producers write through (sc0 sc1) and drain, consumers read below the caches or acquire with every wave; soaked beside a '
                                  'busy neighbour process: 0 mismatching 50k-update runs in 108 (profiles/r06_soak_under_load.md; the round-5 forms: 27 %, at 2 % more updates/s)')
-    if world == 1 and args.learners == 1 and not args.no_population:
+    if args.full and world == 1 and args.learners == 1 and not args.no_population:
       # population axis (the reference's own usage: 10-seed sweeps / Ax trials): independent batch-256 learners advanced by the
       # SAME launches (learner id = grid dimension). Reported next to, never instead of, the single-learner `value`.
       from imitation_learning_amd import BatchedPopulationPlan
@@ -830,9 +865,9 @@ def main():
                                          fp32_frac=round(Lw * update_flops / dtw / 1e12 / FP32_PEAK_TFLOPS, 5))
         del popw
         torch.cuda.empty_cache()
-    if world == 1 and args.learners == 1 and not args.no_secondary:
+    if args.full and world == 1 and args.learners == 1 and not args.no_secondary:
       out['secondary'] = secondary(device, plan, nets)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
       port, ref = cpu_baseline(tr, et), cpu_reference()
       out['cpu_baseline'], out['cpu_port'] = (ref, port) if ref is not None else (port, None)
       if out['cpu_port'] is None: out.pop('cpu_port')

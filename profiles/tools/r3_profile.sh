@@ -10,11 +10,11 @@ for what in "$@"; do
     pwil) cmd="python profiles/tools/secondary_workloads.py pwil" ;;
     gmmil) cmd="python profiles/tools/secondary_workloads.py gmmil" ;;
     pop32) cmd="python profiles/tools/secondary_workloads.py population 32" ;;
-    headline) cmd="python bench.py --steps 400 --warmup 50 --no-cpu-baseline --no-population --no-secondary --trace-steps 2" ;;
+    headline) cmd="python bench.py --full --steps 400 --warmup 50 --no-cpu-baseline --no-population --no-secondary --trace-steps 2" ;;
     pmc)
       for c in FETCH_SIZE WRITE_SIZE; do
         rm -rf /tmp/pmc_$c
-        (cd $ROOT && rocprofv3 --pmc $c -d /tmp/pmc_$c -o p -- python bench.py --steps 100 --warmup 10 --no-graph --no-overlap --no-cpu-baseline --no-population --no-secondary --trace-steps 2 > $OUT/pmc_$c.log 2>&1)
+        (cd $ROOT && rocprofv3 --pmc $c -d /tmp/pmc_$c -o p -- python bench.py --full --steps 100 --warmup 10 --no-graph --no-overlap --no-cpu-baseline --no-population --no-secondary --trace-steps 2 > $OUT/pmc_$c.log 2>&1)
       done
       f=$(find /tmp/pmc_FETCH_SIZE -name "*.db" | head -1); w=$(find /tmp/pmc_WRITE_SIZE -name "*.db" | head -1)
       python profiles/tools/make_pmc_json.py $f $w > $OUT/pmc_latest.json 2> $OUT/pmc_json.err
@@ -28,7 +28,7 @@ for what in "$@"; do
       f=$(find /tmp/ppmc_FETCH_SIZE -name "*.db" | head -1); w=$(find /tmp/ppmc_WRITE_SIZE -name "*.db" | head -1)
       python profiles/tools/make_pmc_json.py $f $w > $OUT/pop32_pmc.json 2> $OUT/pop32_pmc.err
       continue ;;
-    dp) cmd="env IL_FORCE_DP=1 IL_PEER_EXCHANGE=force python bench.py --steps 400 --warmup 50 --no-cpu-baseline --no-population --no-secondary --trace-steps 2" ;;
+    dp) cmd="env IL_FORCE_DP=1 IL_PEER_EXCHANGE=force python bench.py --full --steps 400 --warmup 50 --no-cpu-baseline --no-population --no-secondary --trace-steps 2" ;;
   esac
   rm -rf /tmp/prof_$what
   (cd $ROOT && rocprofv3 --kernel-trace -d /tmp/prof_$what -o $what -- $cmd > $OUT/$what.log 2>&1)

@@ -9,7 +9,7 @@ timeout 900 python -m pytest tests/test_timed_path_oracle.py tests/test_update_p
 timeout 1200 python -m pytest tests/test_gpu_parity.py -m gpu -q -k "sac or schedule_switches or handoff or plan or relabel or pair_mode" > $OUT/pytest_parity.log 2>&1; echo "pytest parity rc=$?" | tee -a $OUT/summary.txt
 for f in $OUT/pytest_timed.log $OUT/pytest_parity.log; do tail -n 3 $f | tee -a $OUT/summary.txt; done
 fi
-run() { env "$@" timeout 300 python bench.py --steps 3000 --warmup 300 --no-cpu-baseline --no-population --no-secondary --trace-steps 50 2>/dev/null | python -c "
+run() { env "$@" timeout 300 python bench.py --full --steps 3000 --warmup 300 --no-cpu-baseline --no-population --no-secondary --trace-steps 50 2>/dev/null | python -c "
 import sys, json
 j = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$*', j['value'], j['ms_per_step'], {k: v['avg_us'] for k, v in j['roofline']['kernels'].items()})" | tee -a $OUT/ab.txt; }
@@ -21,7 +21,7 @@ IL_HIP_LIBRARY=$PWD/variants/tl/libil_hip.so IL_PAIR=1 timeout 300 python profil
 IL_HIP_LIBRARY=$PWD/variants/tl/libil_hip.so IL_PAIR=0 timeout 300 python profiles/tools/update_timeline.py 50 > $OUT/timeline_nopair.txt 2>&1
 for v in 1 0; do
   rm -rf /tmp/prof_$v
-  IL_PAIR=$v rocprofv3 --kernel-trace -d /tmp/prof_$v -o t -- python bench.py --steps 400 --warmup 50 --no-cpu-baseline --no-population --no-secondary --trace-steps 2 > $OUT/trace_$v.log 2>&1
+  IL_PAIR=$v rocprofv3 --kernel-trace -d /tmp/prof_$v -o t -- python bench.py --full --steps 400 --warmup 50 --no-cpu-baseline --no-population --no-secondary --trace-steps 2 > $OUT/trace_$v.log 2>&1
   db=$(find /tmp/prof_$v -name "*.db" | head -1)
   [ -n "$db" ] && python profiles/summarize_rocpd.py $db > $OUT/kernel_stats_pair$v.md && cp $db $OUT/trace_pair$v.db
 done

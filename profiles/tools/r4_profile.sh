@@ -9,7 +9,7 @@ TAG=$1; shift
 ROOT=$PWD
 OUT=$ROOT/gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
-HEAD="python bench.py --steps 100 --warmup 10 --no-graph --no-overlap --no-cpu-baseline --no-population --no-secondary --trace-steps 2"
+HEAD="python bench.py --full --steps 100 --warmup 10 --no-graph --no-overlap --no-cpu-baseline --no-population --no-secondary --trace-steps 2"
 POP="python profiles/tools/secondary_workloads.py population 32"
 counters() {   # counters <name> <cmd> <counter>...
   local name=$1 cmd=$2; shift 2
@@ -26,7 +26,7 @@ for what in "$@"; do
     pwil) cmd="python profiles/tools/secondary_workloads.py pwil" ;;
     gmmil) cmd="python profiles/tools/secondary_workloads.py gmmil" ;;
     pop32) cmd="$POP" ;;
-    headline) cmd="python bench.py --steps 400 --warmup 50 --no-cpu-baseline --no-population --no-secondary --trace-steps 2" ;;
+    headline) cmd="python bench.py --full --steps 400 --warmup 50 --no-cpu-baseline --no-population --no-secondary --trace-steps 2" ;;
     pmc)
       for c in FETCH_SIZE WRITE_SIZE; do
         rm -rf /tmp/pmc_$c

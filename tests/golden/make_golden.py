@@ -827,6 +827,24 @@ def gen_timed_sizes():
   np.savez_compressed(os.path.join(HERE, 'timed_sizes.npz'), **out)
 
 
+def gen_bc_config1():
+  """BASELINE.json configs[0] as the reference runs it (oracle/ref_bc_config1.py on the byte-compiled modules of oracle/build_ref.py): the initial parameters, the
+  parameters after 60 iterations and the loss of every one of 1,000 iterations. The expert rows and the batches are rebuilt from their seeds by the tests
+  (tests/test_reference_backend.py), so they are not stored."""
+  import subprocess
+  root = os.path.dirname(os.path.dirname(HERE))
+  sys.path.insert(0, os.path.join(root, 'oracle'))
+  import build_ref
+  assert build_ref.build(REF)
+  runs = {}
+  with tempfile.TemporaryDirectory() as d:
+    for k in (60, 1000):
+      subprocess.run([sys.executable, os.path.join(root, 'oracle', 'ref_bc_config1.py'), '--iterations', str(k), '--out', os.path.join(d, f'{k}.npz')], check=True)
+      runs[k] = dict(np.load(os.path.join(d, f'{k}.npz')))
+  assert np.array_equal(runs[60]['init'], runs[1000]['init']) and np.array_equal(runs[60]['losses'], runs[1000]['losses'][:60])
+  np.savez_compressed(os.path.join(HERE, 'bc_config1.npz'), init=runs[1000]['init'], final_60=runs[60]['final'], losses=runs[1000]['losses'])
+
+
 def gen_f64():
   """Float64 evaluations of the reference at the comparison sites whose float32 tolerance the GPU tests widen beyond rtol 1e-5 (rewards = a difference of
   logs near D = 1/2, log pi of actions at the clamp, second-order gradients of deep discriminators, exp(-1000 cost), a variance of 5 exponentials): the tests
@@ -853,6 +871,7 @@ if __name__ == '__main__':
   if want('sac_general'):
     for name, kw in gi.GENERAL_SAC_CASES.items(): gen_sac_general(name, kw)
   if want('bc'): gen_bc('bc_hopper', 'hopper', 256, 256, 3)
+  if want('bc_config1'): gen_bc_config1()
   if want('gail'):
     gen_gail('gail_default', gi.gail_case(31), lr=3e-5, weight_decay=10, grad_penalty=1.0, entropy_bonus=0.0)
     gen_gail('gail_h128_ent', gi.gail_case(32, hidden=128), lr=7.3e-5, weight_decay=6.35, grad_penalty=0.32, entropy_bonus=0.0155)

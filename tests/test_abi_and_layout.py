@@ -52,26 +52,35 @@ def test_product_package_never_imports_the_oracle():
       assert not pat.search(open(p).read())
 
 
-def test_reference_build_product_is_the_reference():
-  """oracle/_ref (what bench.py's cpu_baseline leg times live): byte-compiled from the reference's own three hot-path modules - the MANIFEST's source hashes equal the files
-  under /root/reference when that is present (this container), the modules import sourcelessly and expose the reference's entry points, and nothing of it is tracked by git."""
-  import hashlib, json, subprocess, sys
-  ref_dir = os.path.join(ROOT, 'oracle', '_ref')
-  have_reference = os.path.isfile('/root/reference/training.py')
-  if have_reference:
-    subprocess.run([sys.executable, os.path.join(ROOT, 'oracle', 'build_ref.py')], check=True, capture_output=True)
-  if not os.path.isdir(ref_dir):
-    pytest.skip('oracle/_ref is absent and there is no /root/reference to build it from')
-  man = json.load(open(os.path.join(ref_dir, 'MANIFEST.json')))
-  assert set(man['modules']) == {'memory', 'models', 'training'}
-  if have_reference:
+def test_reference_build_product_is_the_reference(tmp_path, monkeypatch):
+  """oracle/build_ref.py (what makes oracle/_ref, the tree bench.py's cpu_baseline leg times live) run on a stand-in for the reference's three hot-path modules, and
+  oracle/_ref itself where build() made it from the reference: the MANIFEST's source hashes equal the files it was built from (where those are readable), the modules
+  import sourcelessly and expose the reference's entry points, no source text lies next to them, and nothing of oracle/_ref is tracked by git."""
+  import hashlib, importlib, json, subprocess, sys
+  monkeypatch.syspath_prepend(os.path.join(ROOT, 'oracle'))
+  build_ref = importlib.import_module('build_ref')
+  stand_in = tmp_path / 'reference'
+  stand_in.mkdir()
+  (stand_in / 'memory.py').write_text('class ReplayMemory:\n  pass\n')
+  (stand_in / 'models.py').write_text('from omegaconf import DictConfig\n\n\nclass GAILDiscriminator:\n  pass\n')
+  (stand_in / 'training.py').write_text('def sac_update(*args):\n  pass\n\n\ndef adversarial_imitation_update(*args):\n  pass\n')
+  monkeypatch.setattr(build_ref, 'OUT', str(tmp_path / '_ref'))
+  assert build_ref.build(str(stand_in))
+  built = [str(tmp_path / '_ref')]
+  if os.path.isdir(os.path.join(ROOT, 'oracle', '_ref')):
+    built.append(os.path.join(ROOT, 'oracle', '_ref'))
+  for ref_dir in built:
+    man = json.load(open(os.path.join(ref_dir, 'MANIFEST.json')))
+    assert set(man['modules']) == {'memory', 'models', 'training'}
     for m, v in man['modules'].items():
-      assert v['source_sha256'] == hashlib.sha256(open(f'/root/reference/{m}.py', 'rb').read()).hexdigest()
-  assert not any(f.endswith('.py') for f in os.listdir(ref_dir)), 'no reference source text in the repo: byte code only (plus our omegaconf stand-in in its own directory)'
-  code = ('import sys; sys.path.insert(0, %r); import memory, models, training; '
-          'assert training.sac_update and training.adversarial_imitation_update and models.GAILDiscriminator and memory.ReplayMemory; print(memory.__file__)' % ref_dir)
-  r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True)
-  assert r.returncode == 0 and r.stdout.strip().endswith('memory.pyc'), r.stderr[-500:]
+      src = os.path.join(man['reference'], m + '.py')
+      if os.access(src, os.R_OK):
+        assert v['source_sha256'] == hashlib.sha256(open(src, 'rb').read()).hexdigest(), src
+    assert not any(f.endswith('.py') for f in os.listdir(ref_dir)), 'no reference source text in the repo: byte code only (plus our omegaconf stand-in in its own directory)'
+    code = ('import sys; sys.path.insert(0, %r); import memory, models, training; '
+            'assert training.sac_update and training.adversarial_imitation_update and models.GAILDiscriminator and memory.ReplayMemory; print(memory.__file__)' % ref_dir)
+    r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, cwd=str(tmp_path))
+    assert r.returncode == 0 and r.stdout.strip().endswith('memory.pyc'), r.stderr[-500:]
   tracked = subprocess.run(['git', '-C', ROOT, 'ls-files', 'oracle/_ref'], capture_output=True, text=True).stdout.strip()
   assert tracked == '', 'oracle/_ref must stay out of git history'
 

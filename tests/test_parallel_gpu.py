@@ -334,7 +334,7 @@ def test_bench_runs_the_multi_gpu_default_schedule_with_one_rank(fused):
   rank 0 runs after the timed region (round 4: it switched the plan to the stream-ordered draw while the fused exchange was still attached - the first real multi-GPU run
   would have died there after its measurement). IL_DP_FUSED=0: one exchange launch per sync point."""
   import json
-  r = _bench(['--steps', '40', '--warmup', '10', '--trace-steps', '3', '--no-cpu-baseline', '--no-population', '--no-secondary'], IL_FORCE_DP='1', IL_PEER_EXCHANGE='force', IL_DP_FUSED=fused,
+  r = _bench(['--full', '--steps', '40', '--warmup', '10', '--trace-steps', '3', '--no-cpu-baseline', '--no-population', '--no-secondary'], IL_FORCE_DP='1', IL_PEER_EXCHANGE='force', IL_DP_FUSED=fused,
              IL_PEER_SOAK_ROUNDS='100')
   assert r.returncode == 0, r.stderr[-3000:]
   j = json.loads(r.stdout.strip().splitlines()[-1])
@@ -349,7 +349,7 @@ def test_bench_starts_its_own_ranks_and_reports_the_replica_digest(peer):
   """`python bench.py --gpus 2` with no rank environment: bench.py launches the two ranks itself (here they share the box's GPU and meet over gloo: IL_BENCH_SHARE_GPU=1),
   prints n_gpus 2, the exchange actually used, the soak report and replicas_bit_identical."""
   import json
-  r = _bench(['--gpus', '2', '--steps', '30', '--warmup', '5', '--trace-steps', '2'], IL_BENCH_SHARE_GPU='1', IL_PEER_EXCHANGE=peer, IL_PEER_SOAK_ROUNDS='200', IL_DEVICE_SYNC='0')
+  r = _bench(['--gpus', '2', '--full', '--steps', '30', '--warmup', '5', '--trace-steps', '2'], IL_BENCH_SHARE_GPU='1', IL_PEER_EXCHANGE=peer, IL_PEER_SOAK_ROUNDS='200', IL_DEVICE_SYNC='0')
   assert r.returncode == 0, r.stderr[-3000:]
   j = json.loads(r.stdout.strip().splitlines()[-1])
   c = j['config']
@@ -369,3 +369,25 @@ def test_bench_starts_its_own_ranks_and_reports_the_replica_digest(peer):
   # the N = 1 schedule timed in the same job: data-parallel efficiency from this one line
   assert c['single_gpu_same_job']['updates_per_s'] > 0 and abs(c['dp_efficiency'] - j['value'] / 2 / c['single_gpu_same_job']['updates_per_s']) < 1e-3
   assert c['exchange_fallback'] is None and j['value'] > 0
+
+
+def test_plain_bench_times_the_given_steps_and_dumps_the_last_update(tmp_path):
+  """A plain `bench.py --gpus 1 --steps N --warmup W` times exactly N steps and reports the headline alone (roofline, population, secondary and CPU baselines are --full's);
+  --dump-outputs writes what the last timed update computed, float32 / float64, and two runs with the same arguments compute the same bits."""
+  import json
+  runs = []
+  for k in range(2):
+    d = tmp_path / f'out{k}'
+    r = _bench(['--gpus', '1', '--steps', '7', '--warmup', '3', '--dump-outputs', str(d)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    j = json.loads(r.stdout.strip().splitlines()[-1])
+    assert j['steps'] == j['timed_replays'] == 7 and j['repeats'] == 1 and j['unit'] == 'updates/s' and j['higher_is_better'] is True and j['dtype'] == 'f32'
+    assert j['ms_per_step'] > 0 and abs(j['value'] - 1e3 / j['ms_per_step']) < 1e-2 * j['value'] and j['config']['finite'] is True
+    assert not {'roofline', 'population', 'secondary', 'cpu_baseline', 'cpu_port'} & set(j)
+    runs.append({f.name[:-len('.npy')]: np.load(f) for f in d.iterdir()})
+  a, b = runs
+  assert set(a) == {'agent_indices', 'expert_indices', 'rewards', 'log_prob', 'q', 'actor', 'critic', 'target_critic', 'log_alpha', 'discriminator', 'discriminator_spectral_norm'}
+  assert all(x.dtype in (np.float32, np.float64) and np.isfinite(x).all() for x in a.values()) and sum(x.nbytes for x in a.values()) <= 64 << 20
+  assert a['agent_indices'].shape == a['rewards'].shape == (256,) and (a['agent_indices'] < 100_000).all() and (a['expert_indices'] < 25_000).all()
+  for name in a:
+    np.testing.assert_array_equal(a[name], b[name], err_msg=name)
