@@ -567,10 +567,10 @@ __device__ __forceinline__ void pair_store(float* slab, int64_t off, const f32x4
   if (same_xcd) *reinterpret_cast<f32x4*>(slab + off) = v;
   else wstore4<true>(slab, off, v);
 }
-__device__ __forceinline__ void pair_publish(unsigned* line) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+__device__ __forceinline__ void pair_publish(unsigned* line, int t_flag = 0) {   // t_flag: the thread that stores the flag (quad: the thread that polls next, so that its wait
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                // never depends on another wave's progress after the barrier)
   __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_store(line, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if ((int)threadIdx.x == t_flag) __hip_atomic_store(line, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 // copies the partner's 16 x 128 half out of `slab` into columns [c_base, c_base + 128) of the [16][ld] LDS tile; every thread calls (barriers inside)
 template <class Timeout>
@@ -594,6 +594,71 @@ __device__ __forceinline__ void pair_receive(unsigned* line, const float* slab, 
     __hip_atomic_store(line + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   __syncthreads();
+}
+// The hop between the four quarters of a quad (k_policy_critic_quad): quarter p publishes ONE slab, [64 columns][16 rows] (4 KB), with one flag line, and reads the other
+// three. Producer: pair_store / pair_publish unchanged. Flag line of slab p: word 0 = the flag, words 1 .. 3 = the XCD + 1 of its three consumers (consumer c announces in
+// word 1 + ((c - p - 1) & 3)), word 4 = how many consumers are done: the third clears the line (quad_release, at the END of the consumer's work: the next launch that
+// uses the line follows this one in stream order, and three dependent atomics cost ~1.3 us on the update's critical path where they were first placed, in quad_receive).
+// `lines` / `slabs` point at quarter 0's line / slab of the (tile, net).
+__device__ __forceinline__ void quad_announce(unsigned* lines, int q) {   // consumer q, first thing: on the lines of the three other quarters
+  if (threadIdx.x == 0) {
+    const unsigned x = il_xcc_id() + 1u;
+    for (int o = 1; o < 4; ++o) { const int p = (q + o) & 3; __hip_atomic_store(lines + p * IL_CTR_STRIDE + 1 + ((q - p - 1) & 3), x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  }
+}
+__device__ __forceinline__ bool quad_same_xcd(unsigned* line) {   // producer: every consumer announced this XCD (wave-uniform)
+#if IL_PAIR_L2_HOP
+  const unsigned x = il_xcc_id() + 1u;
+  const unsigned a = __hip_atomic_load(line + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), b = __hip_atomic_load(line + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
+                 c = __hip_atomic_load(line + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return a == x && b == x && c == x;
+#else
+  return false;
+#endif
+}
+// copies the other three quarters' 16 x 64 blocks into columns [64 p, 64 p + 64) of the [16][ld] LDS tile; every thread calls (barriers inside). Only threads >= t_first
+// take part - thread t_first, which stored this quarter's own flag (pair_publish(.., t_first)), polls the three flags together per round (bounded like every device-side
+// wait), then they copy with sc0 sc1 loads as in pair_receive - so the
+// waves below t_first may have a panel in flight meanwhile: their loads do not queue in front of the hop's (3 * 64 * 4 lanes <= 4 per thread of the copying waves).
+template <class Timeout>
+__device__ __forceinline__ void quad_receive(unsigned* lines, const float* slabs, int q, float* Ts, int ld, int t_first, Timeout timed_out) {
+  if ((int)threadIdx.x == t_first) {
+    unsigned* l0 = lines + ((q + 1) & 3) * IL_CTR_STRIDE; unsigned* l1 = lines + ((q + 2) & 3) * IL_CTR_STRIDE; unsigned* l2 = lines + ((q + 3) & 3) * IL_CTR_STRIDE;
+    int spins = 0;
+    for (;;) {
+      const unsigned a = __hip_atomic_load(l0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), b = __hip_atomic_load(l1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
+                     c = __hip_atomic_load(l2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (a != 0u && b != 0u && c != 0u) break;
+      __builtin_amdgcn_s_sleep(1);
+      if (++spins > IL_SYNC_SPIN_LIMIT) { timed_out(); break; }
+    }
+  }
+  __syncthreads();
+  const int n = (int)blockDim.x - t_first, i0 = (int)threadIdx.x - t_first;
+  if (i0 >= 0) {
+    f32x4 v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {   // every lane requested before the first is written (clamped index: no branch around a load)
+      const int i = min(i0 + u * n, 3 * 64 * 4 - 1), p = (q + 1 + (i >> 8)) & 3;
+      if (u * n < 3 * 64 * 4) v[u] = pair_load4(slabs, (int64_t)p * (IL_TILE_R * 64) + ((i >> 2) & 63) * 16 + (i & 3) * 4);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int i = i0 + u * n, p = (q + 1 + (i >> 8)) & 3, c = (i >> 2) & 63, r4 = (i & 3) * 4;
+      if (i < 3 * 64 * 4)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) Ts[(r4 + e) * ld + 64 * p + c] = v[u][e];
+    }
+  }
+  __syncthreads();
+}
+__device__ __forceinline__ void quad_release(unsigned* lines, int q) {   // consumer q, after its last use of the hop (one thread); the third consumer of a slab clears its line
+  unsigned* l0 = lines + ((q + 1) & 3) * IL_CTR_STRIDE; unsigned* l1 = lines + ((q + 2) & 3) * IL_CTR_STRIDE; unsigned* l2 = lines + ((q + 3) & 3) * IL_CTR_STRIDE;
+  const unsigned a = __hip_atomic_fetch_add(l0 + 4, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), b = __hip_atomic_fetch_add(l1 + 4, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
+                 c = __hip_atomic_fetch_add(l2 + 4, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (a == 2u) for (int w = 0; w < 5; ++w) __hip_atomic_store(l0 + w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (b == 2u) for (int w = 0; w < 5; ++w) __hip_atomic_store(l1 + w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (c == 2u) for (int w = 0; w < 5; ++w) __hip_atomic_store(l2 + w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -35,7 +35,7 @@ struct SacWs {  // float offsets into il_sac.workspace
   int64_t c_x0, c_h1, c_h2, c_q, t_q, c_dz3, c_dz2, c_dz1;
   int64_t p_q, p_g, a_dz3, a_dz2, a_dz1, alpha_part, pair_ctr, chain_ctr;
   int64_t pk_af, pk_ab, pk_cf, pk_cb, pk_tf, pk_tb;  // lane-ordered copies of the H x H layers (mlp_tile.hpp "Packed hidden-layer weights")
-  int64_t x_slab, x_flag, c_rew, p_part;   // p_part: pair-mode k_policy_critic: dQ/da partial tiles [2][nt][16 n-blocks][16 rows][A]   // pair mode (mlp_tile.hpp): 6 * nt hop slabs of 16 x H/2 floats, their flags (one 128-byte line each), the relabel role's rewards [B]
+  int64_t x_slab, x_flag, c_rew, p_part;   // p_part: pair-mode k_policy_critic: dQ/da partial tiles [2][nt][16 n-blocks][16 rows][A]   // pair mode (mlp_tile.hpp): 6 * nt hop slabs of 16 x H/2 floats (quad mode: 8 * nt of 16 x H/4), 8 * nt flag lines (one 128-byte line each), the relabel role's rewards [B]
   int64_t total;
 };
 __host__ __device__ inline SacWs sac_ws(int S, int A, int H, int B) {
@@ -50,7 +50,7 @@ __host__ __device__ inline SacWs sac_ws(int S, int A, int H, int B) {
   const int64_t HH = (int64_t)H * H;
   w.pk_af = take(HH); w.pk_ab = take(HH); w.pk_cf = take(2 * HH); w.pk_cb = take(2 * HH); w.pk_tf = take(2 * HH); w.pk_tb = take(2 * HH);
   o = (o + 31) & ~(int64_t)31;   // slabs and flag lines start on 128-byte lines of their own
-  w.x_slab = take((int64_t)6 * (B / IL_TILE_R) * IL_TILE_R * (H / 2)); o = (o + 31) & ~(int64_t)31; w.x_flag = take((int64_t)6 * (B / IL_TILE_R) * IL_CTR_STRIDE + 32); w.c_rew = take(B); w.p_part = take((int64_t)2 * (B / IL_TILE_R) * 16 * IL_TILE_R * A);
+  w.x_slab = take((int64_t)6 * (B / IL_TILE_R) * IL_TILE_R * (H / 2)); o = (o + 31) & ~(int64_t)31; w.x_flag = take((int64_t)8 * (B / IL_TILE_R) * IL_CTR_STRIDE + 32); w.c_rew = take(B); w.p_part = take((int64_t)2 * (B / IL_TILE_R) * 16 * IL_TILE_R * A);
   w.total = o;
   return w;
 }
@@ -96,7 +96,8 @@ __global__ __launch_bounds__(256) void k_repack(il_sac d, unsigned mask, const i
   {
     for (int i = threadIdx.x; i < d.batch / IL_TILE_R; i += blockDim.x) { reinterpret_cast<unsigned*>(d.workspace + ws.pair_ctr)[i * IL_CTR_STRIDE] = 0u; reinterpret_cast<unsigned*>(d.workspace + ws.chain_ctr)[i * IL_CTR_STRIDE] = 0u; }
     if (threadIdx.x == 0) reinterpret_cast<unsigned*>(d.workspace + ws.chain_ctr)[(d.batch / IL_TILE_R) * IL_CTR_STRIDE + 1] = 0u;   // il_sac_handoff_timeouts counts from here
-    for (int i = threadIdx.x; i < 6 * (d.batch / IL_TILE_R); i += blockDim.x) { reinterpret_cast<unsigned*>(d.workspace + ws.x_flag)[i * IL_CTR_STRIDE] = 0u; reinterpret_cast<unsigned*>(d.workspace + ws.x_flag)[i * IL_CTR_STRIDE + 1] = 0u; }   // pair-mode hop flags (their consumers clear them; this covers a reused arena)
+    for (int i = threadIdx.x; i < 8 * (d.batch / IL_TILE_R); i += blockDim.x)   // pair- / quad-mode hop flag lines, words 0 .. 4 (their consumers clear them; this covers a reused arena)
+      for (int w = 0; w < 5; ++w) reinterpret_cast<unsigned*>(d.workspace + ws.x_flag)[i * IL_CTR_STRIDE + w] = 0u;
   }
   if (!((mask >> net) & 1u)) return;
   const int64_t HH = (int64_t)H * H, ns = net_stride(IN, H, 1);
@@ -1434,6 +1435,186 @@ __device__ __forceinline__ void policy_critic_pair(const il_sac& d, const il_bat
   IL_TL(11, 7);
 }
 
+// Quad mode of k_policy_critic (k_policy_critic_quad): (critic k, tile) is FOUR 512-thread workgroups. In pair mode each SIMD issues two waves x 64 MFMAs of the hidden
+// layer's forward and again of its backward (1.7 us each) and each CU pulls a 128 KB panel; here wave w < 4 of quarter q owns output tile 4 q + w - the MFMAs, k order and
+// operands of wave 4 q + w of k_policy_critic - so one wave per SIMD issues 64 MFMAs and a CU pulls 64 KB. Waves 4 .. 7 share the first layer (computed in full by every
+// quarter, as in the pair), the hop copies and the Q pass, and wait at the barriers while the MFMA waves run. The hop is four-way (quad_receive: every quarter reads the
+// other three 4 KB slabs); dQ/da: wave w of quarter q forms the partial tile of n-block 4 q + w and writes it through, as in the pair; the tile's helpers wait for eight
+// arrivals. A quad waits for each other: every workgroup must be resident - (8 + helpers) * nt within the budget of policy_critic_quad_ok. Bit-identical to k_policy_critic.
+__device__ __forceinline__ void policy_critic_quad(const il_sac& d, const il_batch& b, int k, int tile, int q, float* smem) {
+  const int S = d.state_dim, A = d.action_dim, H = d.hidden, B = d.batch, IN = S + A;
+  const int nt = B / IL_TILE_R, row0 = tile * IL_TILE_R;
+  const int INp = round_up16(IN), ldx = INp + 4, ldh = H + 4;
+  float* Xs = smem; float* H1s = Xs + IL_TILE_R * ldx; float* H2s = H1s + IL_TILE_R * ldh; float* W1s = pair_w1s(smem, INp, H);
+  const int ldw1 = INp + 4, w1_lanes = H * IN / 4;
+  const SacWs ws = sac_ws(S, A, H, B);
+  float* W = d.workspace;
+  const MlpView p = mlp_view(d.critic + k * net_stride(IN, H, 1), IN, H, 1);
+  const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const bool mw = wave < 4;                 // the MFMA waves of the hidden layer (one per SIMD)
+  const int t2 = 4 * q + (wave & 3);        // their output tile
+  // hop slots: 4 (k nt + tile) + q in [0, 8 nt), slabs of 16 x H/4 floats
+  const int sq = (k * nt + tile) * 4;
+  float* slabs = W + ws.x_slab + (size_t)sq * IL_TILE_R * (H / 4); unsigned* lines = reinterpret_cast<unsigned*>(W + ws.x_flag) + (size_t)sq * IL_CTR_STRIDE;
+  const TileTimeouts tmo = tile_timeouts(d);
+  auto timed_out = [&] { __hip_atomic_fetch_add(tmo.slot, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (tmo.sync) sync_timed_out(tmo.sync); };
+  IL_TL(11, 0);
+  quad_announce(lines, q);   // consumer of the other quarters' h2 blocks ...
+  RowsPre rp; rows_idx(rp, INp, row0, nullptr);
+  const bool w1_regs = l1_rows_aligned(p.W1, IN);
+  W1Pre w1; L1Pre w1r;
+  if (w1_regs) l1_prefetch(w1r, p.W1, IN, INp, H); else w1_issue(w1, p.W1, w1_lanes);
+  rows_issue(rp, INp, b.states, b.ld_states, S, W + ws.a_anew, A, A, row0, false, 0, true);
+  const float pb1a = gload(p.b1 + wave * 16 + j), pb1b = gload(p.b1 + min((wave + nw) * 16 + j, H - 1)), pb3 = gload(p.b3);
+  float w3v[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) w3v[u] = gload(p.W3 + min(lane + 64 * u, H - 1));
+  // the MFMA waves' own operands: bias of tile t2 and n-block t2 of the first action k-block of W1 (tile_bwd_dx_cols_prefetch's lanes, for this wave's dQ/da partial tile)
+  const int kb0 = (S >> 4) << 4;
+  float pb2 = 0.f, w1c[4] = {0.f, 0.f, 0.f, 0.f};
+  if (mw) {
+    pb2 = gload(p.b2 + t2 * 16 + j);
+    const float* wp = p.W1 + min(kb0 + j, IN - 1);
+#pragma unroll
+    for (int s_ = 0; s_ < 4; ++s_) w1c[s_] = gload(wp + (size_t)(t2 * 16 + 4 * g + s_) * IN);
+  }
+  issue_fence();
+  Panel16 pf; if (mw) panel_prefetch_lo(pf, W + ws.pk_cf + (size_t)k * H * H, t2);
+  if (!w1_regs) w1_commit(w1, W1s, ldw1, IN, INp, H, w1_lanes);
+  rows_commit(rp, Xs, ldx, INp, IN);
+  __syncthreads();
+  IL_TL(11, 1);
+  {
+    auto epi1 = [&](int c0, f32x4 acc) {
+      const int col = c0 + j; const float bb = (c0 == wave * 16) ? pb1a : pb1b;
+      f32x4 hv;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { hv[r] = fmaxf(acc[r] + bb, 0.f); H1s[(4 * g + r) * ldh + col] = hv[r]; }
+      if (q == 0) debug_mask4(d, 6 + 2 * k, row0 + 4 * g, col, hv);
+    };
+    if (w1_regs) l1_compute_regs(w1r, Xs, ldx, INp, H, epi1); else l1_compute_lds(W1s, ldw1, Xs, ldx, INp, H, epi1);
+  }
+  __syncthreads();
+  IL_TL(11, 2);
+  if (mw) {
+    const bool near = quad_same_xcd(lines + q * IL_CTR_STRIDE);
+    panel_prefetch_hi(pf, W + ws.pk_cf + (size_t)k * H * H, t2);
+    tile_packed_regs(H1s, ldh, pf, t2, [&](int c0, f32x4 acc) {
+      const int col = c0 + j;
+      f32x4 hv;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { hv[r] = fmaxf(acc[r] + pb2, 0.f); H2s[(4 * g + r) * ldh + col] = hv[r]; }
+      debug_mask4(d, 7 + 2 * k, row0 + 4 * g, col, hv);
+      pair_store(slabs + (size_t)q * IL_TILE_R * 64, (int64_t)(col - 64 * q) * 16 + 4 * g, hv, near);
+    });
+  }
+  pair_publish(lines + q * IL_CTR_STRIDE, 256);
+  IL_TL(11, 3);
+  Panel16 pk; if (mw) panel_prefetch(pk, W + ws.pk_cb + (size_t)k * H * H, t2);   // the whole backward panel (64 KB per CU) streams in under the hop: waves 4 .. 7 receive
+  quad_receive(lines, slabs, q, H2s, ldh, 256, timed_out);
+  IL_TL(11, 4);
+  // Q = h2 . w3 + b3 and dz2 = w3 [h2 > 0] in place: whole rows, computed by every quarter (quarter 0 stores Q)
+  for (int r = wave; r < IL_TILE_R; r += nw) {
+    float sq_ = 0.f;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int n = lane + 64 * u;
+      if (n < H) { const float h = H2s[r * ldh + n]; sq_ += h * w3v[u]; H2s[r * ldh + n] = h > 0.f ? w3v[u] : 0.f; }
+    }
+    sq_ = wave_sum(sq_);
+    if (lane == 0 && q == 0) wstore1(W, ws.p_q + (int64_t)k * B + row0 + r, sq_ + pb3);   // (written through: the helpers read it without an acquire)
+  }
+  __syncthreads();
+  IL_TL(11, 5);
+  if (mw) {
+    tile_packed_regs(H2s, ldh, pk, t2, [&](int kb, f32x4 acc) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { float* h = H1s + (4 * g + r) * ldh + kb + j; *h = *h > 0.f ? acc[r] : 0.f; }   // dz1 in place, this wave's columns
+    });
+  }
+  __syncthreads();
+  IL_TL(11, 6);
+  if (mw) {   // dQ/da: the partial tile of n-block t2 (the four MFMAs of tile_bwd_dx_cols), written through, as in policy_critic_pair
+    const int n0 = t2 * 16;
+    float* pp = W + ws.p_part + ((int64_t)(k * nt + tile) * 16 + t2) * IL_TILE_R * A;
+    const f32x4 a = *reinterpret_cast<const f32x4*>(H1s + j * ldh + n0 + 4 * g);
+    for (int kb = kb0; kb < S + A; kb += 16) {
+      float bq[4];
+      if (kb == kb0) {
+#pragma unroll
+        for (int s_ = 0; s_ < 4; ++s_) bq[s_] = w1c[s_];
+      } else {
+        const float* wp = p.W1 + min(kb + j, IN - 1);
+#pragma unroll
+        for (int s_ = 0; s_ < 4; ++s_) bq[s_] = gload(wp + (size_t)(n0 + 4 * g + s_) * IN);
+      }
+      f32x4 acc0 = zero4(), acc1 = zero4();
+      acc0 = mfma16(a[0], bq[0], acc0);
+      acc1 = mfma16(a[1], bq[1], acc1);
+      acc0 = mfma16(a[2], bq[2], acc0);
+      acc1 = mfma16(a[3], bq[3], acc1);
+      const f32x4 acc = acc0 + acc1;
+      const int c = kb + j - S;
+      if (c >= 0 && c < A) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) wstore1(pp, (int64_t)(4 * g + r) * A + c, acc[r]);
+      }
+    }
+  }
+  sync_drain_stores();
+  __syncthreads();
+  unsigned* ctr = reinterpret_cast<unsigned*>(W + ws.pair_ctr) + tile * IL_CTR_STRIDE;
+  if (threadIdx.x == 0) __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  IL_TL(11, 7);
+  if (threadIdx.x == 0) quad_release(lines, q);
+}
+
+// A helper of the pair / quad launches (block h - the launch's critic workgroups - of the helper range): waits for the `arrivals` of its tile's critic workgroups (both
+// critics, every part), then the policy backward of the tile with the last GEMM split over the helpers.
+__device__ __forceinline__ void policy_critic_helper(const il_sac& d, const il_batch& b, float* __restrict__ out_logp, float* __restrict__ out_q, int helpers, int h, unsigned arrivals,
+                                                     float* smem) {
+  const int nt = d.batch / IL_TILE_R, tile = h % nt, part = h / nt;
+  const SacWs ws = sac_ws(d.state_dim, d.action_dim, d.hidden, d.batch);
+  unsigned* ctr = reinterpret_cast<unsigned*>(d.workspace + ws.pair_ctr) + tile * IL_CTR_STRIDE;
+  if (h == 0 && threadIdx.x == 0) { adam_tick(d.actor_opt); adam_tick(d.alpha_opt); }
+  IL_TL(3, 0);
+  const auto wait = [&] {   // every part of both critics has written Q and its dQ/da partial tiles THROUGH (sc0 sc1) before arriving: one relaxed poll, no acquire
+    IL_TL(3, 1);
+    if (threadIdx.x == 0) {
+      const TileTimeouts tmo = tile_timeouts(d);
+      int spins = 0;
+      while (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < arrivals) {
+        __builtin_amdgcn_s_sleep(2);
+        if (++spins > IL_SYNC_SPIN_LIMIT) { __hip_atomic_fetch_add(tmo.slot, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (tmo.sync) sync_timed_out(tmo.sync); break; }
+      }
+    }
+    __syncthreads();
+    IL_TL(3, 2);
+    if (threadIdx.x == 0 && __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == arrivals - 1u + (unsigned)helpers)
+      __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  };
+  if ((d.hidden >> 4) <= helpers * (int)(blockDim.x >> 6)) actor_bwd_tile<16, true, true>(d, b, tile, out_logp, out_q, smem, part, helpers, wait);   // one output tile of the last GEMM per wave at most
+  else actor_bwd_tile<16, false, true>(d, b, tile, out_logp, out_q, smem, part, helpers, wait);
+  IL_TL_END(3);
+}
+
+#ifdef IL_EXP_CHECK
+__device__ __forceinline__ void policy_critic_exp_check(const il_sac& d) {   // (block 0 of the launch) what the chain launch handed over, against its recorded copies
+  const SacWs cws = sac_ws(d.state_dim, d.action_dim, d.hidden, d.batch);
+  const float* CW = d.workspace; const int CB = min(d.batch, 4096), CA = d.action_dim;
+  for (int row = threadIdx.x; row < CB; row += blockDim.x) {
+    const unsigned fr = __float_as_uint(sload1(CW, cws.c_rew + row)), t1 = __float_as_uint(sload1(CW, cws.t_q + row)), t2 = __float_as_uint(sload1(CW, cws.t_q + d.batch + row)), lp = __float_as_uint(sload1(CW, cws.n_logp2 + row));
+    for (int k = 0; k < 2; ++k) {
+      if (__float_as_uint(il_chk_rew[k][row]) != fr) atomicAdd(&il_chk[5], 1u);
+      if (__float_as_uint(il_chk_tq[k][0][row]) != t1 || __float_as_uint(il_chk_tq[k][1][row]) != t2) atomicAdd(&il_chk[6], 1u);
+      if (__float_as_uint(il_chk_tq[k][2][row]) != lp) atomicAdd(&il_chk[7], 1u);
+    }
+    if (CA <= 8) for (int c = 0; c < CA; ++c) { const unsigned a2 = __float_as_uint(sload1(CW, cws.n_a2 + (int64_t)row * CA + c)); for (int q = 0; q < 4; ++q) if (__float_as_uint(il_chk_a2[q][row * 8 + c]) != a2) atomicAdd(&il_chk[8], 1u); }
+  }
+  if (threadIdx.x == 0) atomicAdd(&il_chk[0], 1u);   // checks made
+}
+#endif
+
 __global__ __launch_bounds__(512) void k_policy_critic_pair(il_sac d, il_batch b, float* __restrict__ out_logp, float* __restrict__ out_q, int helpers, int overlap) {   // overlap: 0 = off, else the grid size of the critic optimiser launch this launch waits for
   extern __shared__ __attribute__((aligned(16))) float smem[];
   globalize(d); globalize(b);
@@ -1441,46 +1622,11 @@ __global__ __launch_bounds__(512) void k_policy_critic_pair(il_sac d, il_batch b
   const int nt = d.batch / IL_TILE_R, bx = blockIdx.x;
   long long* osy = reinterpret_cast<long long*>(d.sync);
 #ifdef IL_EXP_CHECK
-  if (bx == 0) {
-    const SacWs cws = sac_ws(d.state_dim, d.action_dim, d.hidden, d.batch);
-    const float* CW = d.workspace; const int CB = min(d.batch, 4096), CA = d.action_dim;
-    for (int row = threadIdx.x; row < CB; row += blockDim.x) {
-      const unsigned fr = __float_as_uint(sload1(CW, cws.c_rew + row)), t1 = __float_as_uint(sload1(CW, cws.t_q + row)), t2 = __float_as_uint(sload1(CW, cws.t_q + d.batch + row)), lp = __float_as_uint(sload1(CW, cws.n_logp2 + row));
-      for (int k = 0; k < 2; ++k) {
-        if (__float_as_uint(il_chk_rew[k][row]) != fr) atomicAdd(&il_chk[5], 1u);
-        if (__float_as_uint(il_chk_tq[k][0][row]) != t1 || __float_as_uint(il_chk_tq[k][1][row]) != t2) atomicAdd(&il_chk[6], 1u);
-        if (__float_as_uint(il_chk_tq[k][2][row]) != lp) atomicAdd(&il_chk[7], 1u);
-      }
-      if (CA <= 8) for (int c = 0; c < CA; ++c) { const unsigned a2 = __float_as_uint(sload1(CW, cws.n_a2 + (int64_t)row * CA + c)); for (int q = 0; q < 4; ++q) if (__float_as_uint(il_chk_a2[q][row * 8 + c]) != a2) atomicAdd(&il_chk[8], 1u); }
-    }
-    if (threadIdx.x == 0) atomicAdd(&il_chk[0], 1u);   // checks made
-  }
+  if (bx == 0) policy_critic_exp_check(d);
 #endif
   const long long ov = overlap ? ov_own(osy, IL_OV_PC) : -1;   // (helpers need nothing of the critic optimiser launch: they wait for this launch's critic workgroups)
   if (bx >= 4 * nt) {   // helper: behind both critics' pairs of its tile in block order
-    const int h = bx - 4 * nt, tile = h % nt, part = h / nt;
-    const SacWs ws = sac_ws(d.state_dim, d.action_dim, d.hidden, d.batch);
-    unsigned* ctr = reinterpret_cast<unsigned*>(d.workspace + ws.pair_ctr) + tile * IL_CTR_STRIDE;
-    if (h == 0 && threadIdx.x == 0) { adam_tick(d.actor_opt); adam_tick(d.alpha_opt); }
-    IL_TL(3, 0);
-    const auto wait = [&] {   // both halves of both critics have written Q and their dQ/da partial tiles THROUGH (sc0 sc1) before arriving: one relaxed poll, no acquire
-      IL_TL(3, 1);
-      if (threadIdx.x == 0) {
-        const TileTimeouts tmo = tile_timeouts(d);
-        int spins = 0;
-        while (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < 4u) {
-          __builtin_amdgcn_s_sleep(2);
-          if (++spins > IL_SYNC_SPIN_LIMIT) { __hip_atomic_fetch_add(tmo.slot, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (tmo.sync) sync_timed_out(tmo.sync); break; }
-        }
-      }
-      __syncthreads();
-      IL_TL(3, 2);
-      if (threadIdx.x == 0 && __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 3u + (unsigned)helpers)
-        __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
-    if ((d.hidden >> 4) <= helpers * (int)(blockDim.x >> 6)) actor_bwd_tile<16, true, true>(d, b, tile, out_logp, out_q, smem, part, helpers, wait);   // one output tile of the last GEMM per wave at most
-    else actor_bwd_tile<16, false, true>(d, b, tile, out_logp, out_q, smem, part, helpers, wait);
-    IL_TL_END(3);
+    policy_critic_helper(d, b, out_logp, out_q, helpers, bx - 4 * nt, 4u, smem);
     IL_ST_END(IL_ST_POLICY_CRITIC);
     if (overlap) ov_done(osy, IL_OV_PC);
     return;
@@ -1491,6 +1637,32 @@ __global__ __launch_bounds__(512) void k_policy_critic_pair(il_sac d, il_batch b
   policy_critic_pair(d, b, k, tile, half, smem, ov, overlap);
   IL_ST_END(IL_ST_POLICY_CRITIC);
   if (overlap) ov_done(osy, IL_OV_PC);
+}
+
+// Block order: the 8 nt critic quarters, then the helpers. Quarter q of (tile, net) segment s in [0, 2 nt): block (s / 8) 32 + 8 q + s % 8 when 2 nt % 8 == 0 - the four
+// quarters share block id mod 8 (same XCD under round-robin dispatch: the hop stays in one L2; placement is speed only, quad_same_xcd checks it) - else q 2 nt + s.
+__device__ __forceinline__ void quad_decode(int bx, int n_seg, int& q, int& s) {
+  if ((n_seg & 7) == 0) { q = (bx >> 3) & 3; s = ((bx >> 5) << 3) | (bx & 7); }
+  else { q = bx / n_seg; s = bx - q * n_seg; }
+}
+__global__ __launch_bounds__(512) void k_policy_critic_quad(il_sac d, il_batch b, float* __restrict__ out_logp, float* __restrict__ out_q, int helpers) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  globalize(d); globalize(b);
+  IL_ST_BEGIN(IL_ST_POLICY_CRITIC);
+  const int nt = d.batch / IL_TILE_R, bx = blockIdx.x;
+#ifdef IL_EXP_CHECK
+  if (bx == 0) policy_critic_exp_check(d);
+#endif
+  if (bx >= 8 * nt) {   // helper: behind every quarter of both critics of its tile in block order
+    policy_critic_helper(d, b, out_logp, out_q, helpers, bx - 8 * nt, 8u, smem);
+    IL_ST_END(IL_ST_POLICY_CRITIC);
+    return;
+  }
+  int q, s, k, tile;
+  quad_decode(bx, 2 * nt, q, s);
+  seg_decode(s, nt, 2, k, tile);
+  policy_critic_quad(d, b, k, tile, q, smem);
+  IL_ST_END(IL_ST_POLICY_CRITIC);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2168,6 +2340,7 @@ static int pair_lds_ready() {
   static const int rc = [] {
     if (hipFuncSetAttribute((const void*)k_sac_chain_pair, hipFuncAttributeMaxDynamicSharedMemorySize, (int)IL_PAIR_LDS_BYTES) != hipSuccess) return 1;
     if (hipFuncSetAttribute((const void*)k_policy_critic_pair, hipFuncAttributeMaxDynamicSharedMemorySize, (int)IL_PAIR_LDS_BYTES) != hipSuccess) return 1;
+    if (hipFuncSetAttribute((const void*)k_policy_critic_quad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)IL_PAIR_LDS_BYTES) != hipSuccess) return 1;
     return 0;
   }();
   if (rc) (void)hipGetLastError();
@@ -2178,10 +2351,22 @@ static bool policy_critic_pair_ok(const il_sac* d) {
   const int nt = d->batch / IL_TILE_R, hp = pc_helpers(nt);
   return pair_env() && pair_shape_ok(d) && hp > 0 && (4 + hp) * nt <= device_cu_count() && pair_lds_ready();
 }
-static void launch_policy_critic(const il_sac* d, const il_batch* b, float* out_logp, float* out_q, size_t lds, hipStream_t st, int overlap = 0) {
+// Quad mode (k_policy_critic_quad): four CUs per (tile, critic) instead of two. Its workgroups wait for each other, so all of them must be resident beside what the other
+// stream keeps resident meanwhile: the discriminator branch of the headline schedule (k_gail_grad's 3 nt + 3 and k_gail_reduce's 7 at batch 256: 58 CUs) - the budget
+// leaves IL_QUAD_CU_RESERVE CUs to it. Beyond the budget, or under IL_QUAD=0 (developer A/B switch: the same bits either way), the pair launch runs.
+#define IL_QUAD_CU_RESERVE 60
+static bool quad_env() { static const int on = [] { const char* e = getenv("IL_QUAD"); return e && e[0] == '0' ? 0 : 1; }(); return on != 0; }
+static bool quad_budget_ok(int workgroups) { return quad_env() && workgroups + IL_QUAD_CU_RESERVE <= device_cu_count(); }
+static bool policy_critic_quad_ok(const il_sac* d) {
+  const int nt = d->batch / IL_TILE_R, hp = pc_helpers(nt);
+  return policy_critic_pair_ok(d) && quad_budget_ok((8 + hp) * nt);
+}
+// quad = false: the data-parallel phases (pair mode as before); overlap != 0 (IL_MAIN_OVERLAP): always the pair launch
+static void launch_policy_critic(const il_sac* d, const il_batch* b, float* out_logp, float* out_q, size_t lds, hipStream_t st, int overlap = 0, bool quad = true) {
   const int H = d->hidden, nt = d->batch / IL_TILE_R;
   IL_TRACE("k_policy_critic", st);
   const int hp = pc_helpers(nt);
+  if (quad && !overlap && policy_critic_quad_ok(d)) { k_policy_critic_quad<<<(8 + hp) * nt, 512, IL_PAIR_LDS_BYTES, st>>>(*d, *b, out_logp, out_q, hp); return; }
   if (policy_critic_pair_ok(d)) { k_policy_critic_pair<<<(4 + hp) * nt, 512, IL_PAIR_LDS_BYTES, st>>>(*d, *b, out_logp, out_q, hp, overlap); return; }
   const bool px = hp > 0 && hp <= 6 && chain_xcd_nets(nt);
   k_policy_critic<<<px ? 8 * nt : (2 + hp) * nt, tile_threads(H), lds, st>>>(*d, *b, out_logp, out_q, nullptr, nullptr, px ? (hp | IL_PC_XCD_NETS) : hp);
@@ -2386,7 +2571,7 @@ static int sac_update_gather_impl(const il_sac* d, const il_batch* rows, const i
     IL_CHECK_LAUNCH("il_sac_update_gather");
     return IL_OK;
   }
-  launch_policy_critic(d, rows, out_logp, out_q, lds, st);
+  launch_policy_critic(d, rows, out_logp, out_q, lds, st, 0, !peer_critic && !peer_actor);   // (data-parallel ranks keep the pair launch)
   DwArgs aa = actor_dw_args(d, rows, flags);
   if (peer_actor) {
     DwPeer ap = {*peer_actor, mlp_numel(d->state_dim, d->hidden, 2 * d->action_dim)};
@@ -2797,7 +2982,7 @@ extern "C" int il_sac_dp_phase(const il_sac* d, const il_batch* b, int32_t phase
   } else if (phase == 2) {
     const int64_t n = 2 * net_stride(S + A, H, 1);
     { IL_TRACE("k_apply_critic", st); k_apply_critic<<<(int)((n + 255) / 256), 256, 0, st>>>(*d); }
-    launch_policy_critic(d, b, out_logp, out_q, lds, st);
+    launch_policy_critic(d, b, out_logp, out_q, lds, st, 0, false);
     DwArgs aa = actor_dw_args(d, b, IL_FLAG_GRADS_ONLY);
     { IL_TRACE("k_dw_adam_actor", st); launch_dw_adam(aa, aa.n_dw_blocks + 1, st); }
   } else {
@@ -2821,7 +3006,7 @@ extern "C" int il_sac_dp_phase_peer(const il_sac* d, const il_batch* b, int32_t 
   if (phase == 2) {
     IL_CHECK_ARG(x->n == 2 * net_stride(S + A, H, 1), "il_sac_dp_phase_peer: phase 2 takes the critic bucket (%lld floats, got %lld)", (long long)(2 * net_stride(S + A, H, 1)), (long long)x->n);
     { IL_TRACE("k_peer_apply_critic", st); k_peer_apply_critic<<<(unsigned)peer_chunks(x->n), 256, 0, st>>>(*d, *x); }
-    launch_policy_critic(d, b, out_logp, out_q, lds, st);
+    launch_policy_critic(d, b, out_logp, out_q, lds, st, 0, false);
     DwArgs aa = actor_dw_args(d, b, IL_FLAG_GRADS_ONLY);
     { IL_TRACE("k_dw_adam_actor", st); launch_dw_adam(aa, aa.n_dw_blocks + 1, st); }
   } else {
