@@ -6,25 +6,10 @@
 #include "mlp_tile.hpp"
 #include "peer_device.hpp"
 
-// How the optimiser epilogues store p / m / v and the lane-ordered copies (IL_DW_STORE_MODE): 0 = plain stores (the lines sit dirty in this XCD's L2 until the
-// end-of-kernel write-back, which is on the critical path of the following launch boundary), 1 = `nt` (streaming) stores, 2 = `sc0 sc1` write-through stores (the data
-// leaves for memory while the kernel still runs; nothing of it is left to flush). m and v are not read again before the next update, p only by other XCDs.
-#ifndef IL_POLYAK_WT
-#define IL_POLYAK_WT 1
-#endif
-#ifndef IL_DW_STORE_MODE
-#define IL_DW_STORE_MODE 2
-#endif
-typedef unsigned dw_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void dw_store4(float* base, int64_t off, const f32x4& v) {
-#if IL_DW_STORE_MODE == 1
-  __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(base + off));
-#elif IL_DW_STORE_MODE == 2
-  wstore4(base, off, v);
-#else
-  *reinterpret_cast<f32x4*>(base + off) = v;
-#endif
-}
+// The optimiser epilogues store p / m / v and the lane-ordered copies with `sc0 sc1` write-through stores: the data leaves for memory while the kernel still runs and
+// nothing of it is left to flush (plain stores leave the lines dirty in this XCD's L2 until the end-of-kernel write-back, which is on the critical path of the following
+// launch boundary; `nt` stores: no change, il_common.hpp wstore4). m and v are not read again before the next update, p only by other XCDs.
+__device__ __forceinline__ void dw_store4(float* base, int64_t off, const f32x4& v) { wstore4(base, off, v); }
 struct DwArgs {
   float* params; float* grads; il_adam opt; int grads_only;
   int n_nets; int64_t net_stride;

@@ -40,20 +40,13 @@ __device__ __forceinline__ f32x4 gload4(const float* p) { return *(const __attri
 // Write-through stores for data that the NEXT launch reads on other XCDs (activations / dZ in the workspace, the optimiser's p / m / v and lane-ordered copies). A plain
 // store leaves a dirty line in this XCD's L2; the end-of-kernel release writes all of them back, and that write-back sits between this launch and the next one on the
 // update's critical path (round 3: `sc0 sc1` stores in the dW epilogue alone: 14.76k -> 14.97k updates/s; `nt` stores: no change). `base` must be wave-uniform (it
-// becomes the buffer resource), `off` is in floats (< 2^29). IL_WT_STORES=0: plain stores (A/B builds).
-#ifndef IL_WT_STORES
-#define IL_WT_STORES 1
-#endif
+// becomes the buffer resource), `off` is in floats (< 2^29).
 typedef unsigned il_u32x4 __attribute__((ext_vector_type(4)));
 template <bool WT = true>
 __device__ __forceinline__ void wstore4(float* base, int64_t off, const f32x4& v) {
-#if IL_WT_STORES
   if (!WT) { *reinterpret_cast<f32x4*>(base + off) = v; return; }   // (the 80-VGPR population builds keep plain stores: their chip is oversubscribed, the flush is not exposed)
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7ffffff0, 0x00020000);   // raw buffer, byte offsets
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(il_u32x4, v), rs, (int)(off * 4), 0, 17);       // sc0 | sc1
-#else
-  *reinterpret_cast<f32x4*>(base + off) = v;
-#endif
 }
 
 // One float written through / read below this CU's L1 (the fence-free hand-offs of the pair-mode kernels: a few scalars per lane next to a relaxed arrival counter)
@@ -278,11 +271,7 @@ __device__ __forceinline__ void sync_drain_stores() { asm volatile("s_waitcnt vm
 __device__ __forceinline__ void sync_signal(long long* ctr) {   // all threads of the workgroup, after their stores
   sync_drain_stores();
   __syncthreads();
-#ifdef IL_SYNC_UNSAFE
-  if (threadIdx.x == 0) __hip_atomic_fetch_add(ctr, 1LL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
   if (threadIdx.x == 0) __hip_atomic_fetch_add(ctr, 1LL, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-#endif
 }
 __device__ __forceinline__ void sync_timed_out(long long* sync) {   // one thread: count the expired wait, and raise the host's flag if it gave us one ([IL_SYNC_HOST_FLAG])
   const long long n = __hip_atomic_fetch_add(sync + IL_SYNC_TIMEOUTS, 1LL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
@@ -300,27 +289,12 @@ __device__ __forceinline__ bool sync_poisoned(const long long* sync) {
 // (buffer_inv sc1) that is ordered only against the later loads of the wave that issued it and is not counted by vmcnt, so the polling wave cannot wait for its completion
 // before it releases the barrier; two XCDs' L2s are not coherent inside a launch (profiles/tools/l2_stale_probe.hip: a plain re-load of a line another XCD rewrote was stale
 // 20 000 times of 20 000), e.g. the discriminator's parameters, which the concurrently running k_gail_grad of the same update reads (pre-step) into the L2 the critic-loss
-// launch uses. Hardening found while chasing profiles/r06_soak_under_load.md (whose main cause was on the release side: sync_drain_stores). IL_SYNC_LEADER_ACQUIRE: the
-// round-5 form, for A/B builds.
-__device__ __forceinline__ void sync_acquire_all() {
-#ifndef IL_SYNC_UNSAFE
-#ifdef IL_SYNC_LEADER_ACQUIRE
-  if (threadIdx.x == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  __syncthreads();
-#else
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
-#endif
-}
+// launch uses. Hardening found while chasing profiles/r06_soak_under_load.md (whose main cause was on the release side: sync_drain_stores).
+__device__ __forceinline__ void sync_acquire_all() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); }
 // a counter read as a wait TARGET (the epoch of this launch): an agent-scope load like the polls, never a cached one - a poll of another resident kernel that was in flight
-// when this launch's start invalidated the L2 can install the line's previous value behind the invalidation, and a plain load would then hit it (IL_SYNC_PLAIN_EPOCH: the
-// round-5 plain loads, for the soak A/B under profiles/)
+// when this launch's start invalidated the L2 can install the line's previous value behind the invalidation, and a plain load would then hit it
 __device__ __forceinline__ long long sync_read(const long long* sync, int which) {
-#ifdef IL_SYNC_PLAIN_EPOCH
-  return sync[which];
-#else
   return __hip_atomic_load(sync + which, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
 }
 // LEADER_ACQUIRE (sync_wait_leader): one invalidate, by the polling thread, in front of the barrier - ONLY where no cache of this XCD can hold a line of the guarded data that
 // was fetched after this launch started and before its producer wrote it (each use says why); everywhere else every wave acquires (sync_acquire_all).
@@ -334,9 +308,7 @@ __device__ __forceinline__ void sync_wait(long long* sync, int which, long long 
       if (limit == 0) { const long long own = sync[IL_SYNC_SPIN]; limit = own > 0 ? (int)(own > 0x7fffffffLL ? 0x7fffffffLL : own) : IL_SYNC_SPIN_LIMIT; }
       if (++spins > limit) { sync_timed_out(sync); break; }
     }
-#ifndef IL_SYNC_UNSAFE
     if (LEADER_ACQUIRE && !NO_ACQUIRE) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
   }
   __syncthreads();
   if (!LEADER_ACQUIRE && !NO_ACQUIRE) sync_acquire_all();

@@ -12,9 +12,6 @@
 #pragma once
 #include "il_common.hpp"
 
-#ifndef IL_L1_PAIR
-#define IL_L1_PAIR 1   // tile_fwd: k-blocks of a narrow first layer fetched pairwise (0 = the round-2 one-at-a-time loop, for A/B builds); same MFMA order, same bits
-#endif
 __device__ __forceinline__ f32x4 zero4() { f32x4 z = {0.f, 0.f, 0.f, 0.f}; return z; }
 
 // Operand loads are never wrapped in a branch or a select (hipcc turns `cond ? load : 0` into an exec-masked branch that
@@ -45,7 +42,6 @@ template <int MODE, int PANEL, class Epi>
 __device__ __forceinline__ void tile_fwd_impl(const float* Xs, int ldx, int Kpad, const float* __restrict__ W, int ldw, int Kw, int N, Epi epi) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
   const int j = lane & 15, g = lane >> 4;
-#if IL_L1_PAIR
   if (Kpad == 32 && N == 32 * nw) {   // (round 4) a narrow first layer with TWO column tiles per wave (the 8-wave population kernels): the weight lanes of both tiles are
     f32x4 b[2][2];                    // requested before the first MFMA - the tile loop below made the second tile's round trip wait for the first tile's epilogue
 #pragma unroll
@@ -70,7 +66,6 @@ __device__ __forceinline__ void tile_fwd_impl(const float* Xs, int ldx, int Kpad
     }
     return;
   }
-#endif
   for (int c0 = wave * 16; c0 < N; c0 += nw * 16) {
     f32x4 acc0 = zero4(), acc1 = zero4();  // two accumulators: the 16x16x4 f32 MFMA has a 40-cycle dependent latency vs 32-cycle issue
     const float* wr = W + (size_t)(c0 + j) * ldw + 4 * g;
@@ -118,7 +113,6 @@ __device__ __forceinline__ void tile_fwd_impl(const float* Xs, int ldx, int Kpad
         acc1 = mfma16(a[3], b[u][3], acc1);
       }
     }
-#if IL_L1_PAIR
     for (; k0 + 32 <= Kpad; k0 += 32) {   // the first layers (K = 17 .. 32 -> Kpad = 32): both k-blocks' weight lanes requested before the first MFMA instead of two dependent L2 round trips
       f32x4 b[2];
 #pragma unroll
@@ -133,7 +127,6 @@ __device__ __forceinline__ void tile_fwd_impl(const float* Xs, int ldx, int Kpad
         acc1 = mfma16(a[3], b[u][3], acc1);
       }
     }
-#endif
     for (; k0 < Kpad; k0 += 16) {
       const f32x4 a = *reinterpret_cast<const f32x4*>(xr + k0);
       const f32x4 b = load4<MODE>(wr - 4 * g, k0 + 4 * g, Kw);
@@ -212,9 +205,6 @@ __device__ __forceinline__ void tile_bwd_dx(const float* dYs, int ldy, int Npad,
 // The weight operands of tile_bwd_dx_cols / tile_fwd_small depend on nothing the kernel computes: `*_prefetch` requests this wave's lanes (first column tile; up to two
 // n- / k-blocks per wave, i.e. every block of a 16- or 8-wave workgroup at H = 256) at the top of the kernel, so that the small GEMM at the END of a dependent chain of
 // layers starts from registers instead of from an L2 / fabric round trip behind a barrier. Same values, same MFMA order: same bits.
-#ifndef IL_SMALL_PREFETCH
-#define IL_SMALL_PREFETCH 1
-#endif
 struct ColsPre { float b[2][4]; };
 __device__ __forceinline__ ColsPre tile_bwd_dx_cols_prefetch(const float* __restrict__ W, int ldw, int K, int N, int c_lo) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
@@ -541,13 +531,10 @@ __device__ __forceinline__ void rows_commit(const RowsPre& p, float* Xs, int ldx
 // Flag line (128 bytes per slab): word 0 = the flag (producer: 1; consumer: back to 0), word 1 = the CONSUMER's XCD + 1 (announced at its start, cleared with the flag).
 // Producer: pair_store lanes, then pair_publish (every wave drains its stores; barrier; ONE relaxed agent-scope flag store). Consumer: pair_announce at its start;
 // pair_receive (one polling lane, bounded like every device-side wait; barrier; sc0 sc1 loads: never served by this CU's L1; thread 0 clears the line).
-// Two store flavours, chosen per wave (IL_PAIR_L2_HOP): if the consumer has announced the producer's own XCD (HW_REG_XCC_ID - checked, not assumed from the block id), the
+// Two store flavours, chosen per wave: if the consumer has announced the producer's own XCD (HW_REG_XCC_ID - checked, not assumed from the block id), the
 // halves share an L2: plain stores are complete for every CU of the XCD once vmcnt says so (the vector L1 writes through), and the consumer's L1-bypassing loads hit that
 // L2 - no trip to HBM on either side (measured on the update's timeline: publish 1.3 -> 0.6-0.9 us, receive 1.0-1.2 -> 0.7-1.0 us). Otherwise (other XCD, or not announced yet): write-through (sc0 sc1) stores,
 // the form that is valid under any placement (MI355X guide, "Valid forms").
-#ifndef IL_PAIR_L2_HOP
-#define IL_PAIR_L2_HOP 1
-#endif
 __device__ __forceinline__ unsigned il_xcc_id() { unsigned v; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v)); return v & 0xfu; }
 __device__ __forceinline__ f32x4 pair_load4(const float* base, int64_t off) {
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, 0x7ffffff0, 0x00020000);
@@ -557,11 +544,7 @@ __device__ __forceinline__ void pair_announce(unsigned* line) {   // consumer, f
   if (threadIdx.x == 0) __hip_atomic_store(line + 1, il_xcc_id() + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ bool pair_same_xcd(unsigned* line) {   // producer, a little before its stores (the load's latency hides under the MFMAs); wave-uniform
-#if IL_PAIR_L2_HOP
   return __hip_atomic_load(line + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == il_xcc_id() + 1u;
-#else
-  return false;
-#endif
 }
 __device__ __forceinline__ void pair_store(float* slab, int64_t off, const f32x4& v, bool same_xcd) {
   if (same_xcd) *reinterpret_cast<f32x4*>(slab + off) = v;
@@ -607,14 +590,10 @@ __device__ __forceinline__ void quad_announce(unsigned* lines, int q) {   // con
   }
 }
 __device__ __forceinline__ bool quad_same_xcd(unsigned* line) {   // producer: every consumer announced this XCD (wave-uniform)
-#if IL_PAIR_L2_HOP
   const unsigned x = il_xcc_id() + 1u;
   const unsigned a = __hip_atomic_load(line + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), b = __hip_atomic_load(line + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
                  c = __hip_atomic_load(line + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   return a == x && b == x && c == x;
-#else
-  return false;
-#endif
 }
 // copies the other three quarters' 16 x 64 blocks into columns [64 p, 64 p + 64) of the [16][ld] LDS tile; every thread calls (barriers inside). Only threads >= t_first
 // take part - thread t_first, which stored this quarter's own flag (pair_publish(.., t_first)), polls the three flags together per round (bounded like every device-side
@@ -740,14 +719,9 @@ __device__ __forceinline__ void xcd_tile_net(int b, int nt, int n_nets, int& til
 // the linear id puts learner l on XCD l % 8 - groups of 8 learners are interleaved - so an L2 holds the panels of the two learners it is working on and the 16 tiles of a
 // network re-use them. A learner's workgroups keep their relative order (a role that waits for lower-numbered workgroups of its learner still does). Learners beyond the
 // last full group of 8 keep the natural decode. Pure re-labelling: results are bit-identical.
-#ifndef IL_POP_XCD
-#define IL_POP_XCD 1
-#endif
 __device__ __forceinline__ void pop_ids(int& bx, int& by) {
-#if IL_POP_XCD
   const int nx = gridDim.x, g = by * nx + bx, full = ((int)gridDim.y >> 3) * 8 * nx;
   if (g < full) { const int grp = g / (8 * nx), r = g - grp * 8 * nx; by = grp * 8 + (r & 7); bx = r >> 3; }
-#endif
 }
 
 struct MlpView {  // flat torch-order parameter vector of a depth-2 MLP

@@ -25,10 +25,7 @@ extern "C" int il_debug_check(unsigned* out_host) { return hipMemcpyFromSymbol(o
 
 // Measured (round 3, same box, three interleaved rounds): write-through stores in the dW / AdamW epilogue ONLY: 14.71k -> 14.90k updates/s; ALSO for the activations and dZ
 // the tile kernels leave in the workspace: 14.59k - the next launch reads those, and a written-through line is not left behind in the L2 for the readers of its own XCD.
-#ifndef IL_WT_TILE_STORES
-#define IL_WT_TILE_STORES 0
-#endif
-
+// Hence the tile kernels store those with wstore4<false> (plain stores).
 
 struct SacWs {  // float offsets into il_sac.workspace
   int64_t a_h1, a_h2, a_xpre, a_eps, a_lsraw, a_anew, a_logp, n_a2, n_logp2, a_x0;
@@ -142,9 +139,7 @@ __device__ __forceinline__ void actor_fwd_tile(const il_sac& d, const il_batch& 
   // threads their noise sample (Philox + Box-Muller is ~1 us of dependent ALU work that needs nothing from the MLP) and absorbing flag.
   const int pc = min(wave * 16 + j, H - 1);
   const float pb1 = gload(net.b1 + pc), pb2 = gload(net.b2 + pc);
-#if IL_SMALL_PREFETCH
   const SmallPre w3pre = tile_fwd_small_prefetch(net.W3, H, 2 * A, H);   // the head's weight lanes: consumed after both hidden layers
-#endif
   const uint32_t ctr = d.noise_counter ? *d.noise_counter : 0u;
   float e_pre = 0.f, absorb_pre = 0.f;
   if (tid < IL_TILE_R * A) {
@@ -166,7 +161,7 @@ __device__ __forceinline__ void actor_fwd_tile(const il_sac& d, const il_batch& 
     f32x4 hv;
 #pragma unroll
     for (int r = 0; r < 4; ++r) { hv[r] = fmaxf(acc[r] + bb, 0.f); H1s[(4 * g + r) * ldh + col] = hv[r]; }
-    if (is_cur) { wstore4<(IL_WT_TILE_STORES && PANEL >= 16)>(W, ws.a_h1 + (int64_t)col * B + row0 + 4 * g, hv); debug_mask4(d, 0, row0 + 4 * g, col, hv); }
+    if (is_cur) { wstore4<false>(W, ws.a_h1 + (int64_t)col * B + row0 + 4 * g, hv); debug_mask4(d, 0, row0 + 4 * g, col, hv); }
   });
   __syncthreads();
   IL_TL(is_cur ? 6 : 5, 2);
@@ -175,15 +170,11 @@ __device__ __forceinline__ void actor_fwd_tile(const il_sac& d, const il_batch& 
     f32x4 hv;
 #pragma unroll
     for (int r = 0; r < 4; ++r) { hv[r] = fmaxf(acc[r] + bb, 0.f); H2s[(4 * g + r) * ldh + col] = hv[r]; }
-    if (is_cur) { wstore4<(IL_WT_TILE_STORES && PANEL >= 16)>(W, ws.a_h2 + (int64_t)col * B + row0 + 4 * g, hv); debug_mask4(d, 1, row0 + 4 * g, col, hv); }
+    if (is_cur) { wstore4<false>(W, ws.a_h2 + (int64_t)col * B + row0 + 4 * g, hv); debug_mask4(d, 1, row0 + 4 * g, col, hv); }
   });
   __syncthreads();
   IL_TL(is_cur ? 6 : 5, 3);
-#if IL_SMALL_PREFETCH
   tile_fwd_small(H2s, ldh, H, net.W3, H, 2 * A, net.b3, Os, part, &w3pre);
-#else
-  tile_fwd_small(H2s, ldh, H, net.W3, H, 2 * A, net.b3, Os, part);
-#endif
   IL_TL(is_cur ? 6 : 5, 4);
   // head: one thread per (row, action component); per-row sums through LDS (sequential over A like torch's sum(-1))
   float* nl = part; float* la = part + 256;
@@ -333,7 +324,7 @@ __device__ __forceinline__ void critic_fwd_tile(const il_sac& d, const il_batch&
     f32x4 hv;
 #pragma unroll
     for (int r = 0; r < 4; ++r) { hv[r] = fmaxf(acc[r] + bb, 0.f); H1s[(4 * g + r) * ldh + col] = hv[r]; }
-    if (!is_target) { wstore4<(IL_WT_TILE_STORES && PANEL >= 16)>(W, ws.c_h1 + (int64_t)k * B * H + (int64_t)col * B + row0 + 4 * g, hv); debug_mask4(d, 2 + 2 * k, row0 + 4 * g, col, hv); }
+    if (!is_target) { wstore4<false>(W, ws.c_h1 + (int64_t)k * B * H + (int64_t)col * B + row0 + 4 * g, hv); debug_mask4(d, 2 + 2 * k, row0 + 4 * g, col, hv); }
   });
   __syncthreads();
   IL_TL(8, 2);
@@ -342,7 +333,7 @@ __device__ __forceinline__ void critic_fwd_tile(const il_sac& d, const il_batch&
     f32x4 hv;
 #pragma unroll
     for (int r = 0; r < 4; ++r) { hv[r] = fmaxf(acc[r] + bb, 0.f); H2s[(4 * g + r) * ldh + col] = hv[r]; }
-    if (!is_target) { wstore4<(IL_WT_TILE_STORES && PANEL >= 16)>(W, ws.c_h2 + (int64_t)k * B * H + (int64_t)col * B + row0 + 4 * g, hv); debug_mask4(d, 3 + 2 * k, row0 + 4 * g, col, hv); }
+    if (!is_target) { wstore4<false>(W, ws.c_h2 + (int64_t)k * B * H + (int64_t)col * B + row0 + 4 * g, hv); debug_mask4(d, 3 + 2 * k, row0 + 4 * g, col, hv); }
   });
   __syncthreads();
   IL_TL(8, 3);
@@ -418,7 +409,7 @@ __device__ __forceinline__ void k_critic_bwd_body(il_sac d, il_batch b, const il
     f32x4 o;
 #pragma unroll
     for (int q = 0; q < 4; ++q) { const float m = hv[q] > 0.f ? w3 : 0.f; DZ2s[(r4 + q) * ldh + n] = m; o[q] = dz3s[r4 + q] * m; }
-    wstore4<(IL_WT_TILE_STORES && PANEL >= 16)>(W, ws.c_dz2 + (int64_t)k * B * H + (int64_t)n * B + row0 + r4, o);
+    wstore4<false>(W, ws.c_dz2 + (int64_t)k * B * H + (int64_t)n * B + row0 + r4, o);
   }
   __syncthreads();
   // dz1 = dQ * ([h1 > 0] (m . W2)) with m = [h2 > 0] w3: the row factor dQ is applied AFTER the GEMM, so that k_sac_chain can run the GEMM
@@ -429,7 +420,7 @@ __device__ __forceinline__ void k_critic_bwd_body(il_sac d, il_batch b, const il
     f32x4 o;
 #pragma unroll
     for (int r = 0; r < 4; ++r) o[r] = dz3s[4 * g + r] * (hv[r] > 0.f ? acc[r] : 0.f);
-    wstore4<(IL_WT_TILE_STORES && PANEL >= 16)>(W, ws.c_dz1 + (int64_t)k * B * H + (int64_t)off, o);
+    wstore4<false>(W, ws.c_dz1 + (int64_t)k * B * H + (int64_t)off, o);
   });
   IL_TL_END(9);
 }
@@ -461,7 +452,7 @@ __device__ __forceinline__ void critic_bwd_resident_gemm(const il_sac& d, int k,
 }
 // relabel: the rewards of this tile are the discriminator `dd`'s prediction on (s, a) - the rows still sit in Xs - computed here once its AdamW step of
 // this update is complete ([IL_SYNC_PARAMS], n_reduce workgroups per step); otherwise dense `rewards` or the batch's own reward field.
-struct ChainRelabel { il_disc dd; int on, n_reduce; float* out; int fwd_only; int wait_indices; int local_rewards; int xcd_nets, gather_wgs; int early_draw; int overlap; long long ov_n; };   // overlap: 0 = off, else the grid size of the actor optimiser launch this launch waits for   // overlap (k_sac_chain_pair, il_sac_update_gather_overlap): the previous update's actor optimiser launch may still be running on the other stream - ov_n = this stage's own epoch (ov_own, set by the kernel) stands in for [IL_SYNC_MAIN_EPOCH] and the roles wait for [IL_SYNC_OV_EPOCH + IL_OV_DWA] >= ov_n where they first need what that launch writes   // early_draw: publish [IL_SYNC_CHAIN_WGS] (IL_EARLY_DRAW=0: the resident sampler waits for the previous update's end, as in round 4)   // xcd_nets: grid = 8 * nt, one network per XCD (chain_decode_xcd); gather_wgs: row-copy workgroups among the blocks of XCDs 6, 7   // wait_indices: IL_FLAG_SAC_WAIT_INDICES; local_rewards: il_sac_update_gather without `rewards` / `relabel` (the ring's reward field: nothing to wait for)   // fwd_only: the forward kernels only (IL_FLAG_SAC_FORWARD_ONLY / data-parallel phase 0): no critic backward
+struct ChainRelabel { il_disc dd; int on, n_reduce; float* out; int fwd_only; int wait_indices; int local_rewards; int reserved_[2]; int early_draw; int overlap; long long ov_n; };   // overlap: 0 = off, else the grid size of the actor optimiser launch this launch waits for   // overlap (k_sac_chain_pair, il_sac_update_gather_overlap): the previous update's actor optimiser launch may still be running on the other stream - ov_n = this stage's own epoch (ov_own, set by the kernel) stands in for [IL_SYNC_MAIN_EPOCH] and the roles wait for [IL_SYNC_OV_EPOCH + IL_OV_DWA] >= ov_n where they first need what that launch writes   // early_draw: publish [IL_SYNC_CHAIN_WGS] (IL_EARLY_DRAW=0: the resident sampler waits for the previous update's end, as in round 4)   // reserved_: unused padding, kept so that the size and the field offsets stay as they were: k_sac_chain_pair takes this struct by value and its register allocation depends on the argument offsets (8 bytes shorter, it compiled with 20 bytes of scratch instead of none)   // wait_indices: IL_FLAG_SAC_WAIT_INDICES; local_rewards: il_sac_update_gather without `rewards` / `relabel` (the ring's reward field: nothing to wait for)   // fwd_only: the forward kernels only (IL_FLAG_SAC_FORWARD_ONLY / data-parallel phase 0): no critic backward
 // Runs between the critic's own work and its wait for the targets: the discriminator's step usually lands while the targets are still being computed,
 // so the relabel stays off the critical path. Leaves the tile's rewards in LDS (rew16) for critic_bwd_resident_scale.
 __device__ __forceinline__ void critic_relabel_tile(const il_sac& d, const ChainRelabel& rl, int k, int tile, float* smem) {
@@ -529,8 +520,8 @@ __device__ __forceinline__ void critic_bwd_resident_scale(const il_sac& d, const
     f32x4 o2, o1;
 #pragma unroll
     for (int q = 0; q < 4; ++q) { o2[q] = dz3s[r4 + q] * H2s[(r4 + q) * ldh + n]; o1[q] = dz3s[r4 + q] * H1s[(r4 + q) * ldh + n]; }
-    wstore4<(IL_WT_TILE_STORES != 0)>(W, ws.c_dz2 + (int64_t)k * B * H + (int64_t)n * B + row0 + r4, o2);
-    wstore4<(IL_WT_TILE_STORES != 0)>(W, ws.c_dz1 + (int64_t)k * B * H + (int64_t)n * B + row0 + r4, o1);
+    wstore4<false>(W, ws.c_dz2 + (int64_t)k * B * H + (int64_t)n * B + row0 + r4, o2);
+    wstore4<false>(W, ws.c_dz1 + (int64_t)k * B * H + (int64_t)n * B + row0 + r4, o1);
   }
 }
 
@@ -560,18 +551,6 @@ __device__ __forceinline__ void chain_decode(int bid, int nt, int& role, int& ne
     net = l / nt; tile = l - net * nt;
   }
 }
-// One network per XCD (grid = 8 * nt; workgroup b runs on XCD b % 8): the nt tile workgroups of a role-network all sit on the same XCD, so its weights cross the fabric
-// once instead of once per XCD that hosts one of its tiles (chain_decode: 8x for the actor roles, 4x for the critic-shaped ones - 11 MB of reads per launch against
-// 1.7 MB of weights). XCD 0: actor(s'), 1-2: targets, 3-4: critics, 5: actor(s), 6-7: the row-copy workgroups (the rest of their blocks exit at once). A role still only
-// waits for lower-numbered workgroups (tile q: 8q < 8q + 1, 8q + 2 < 8q + 3, 8q + 4).
-__device__ __forceinline__ void chain_decode_xcd(int bid, int& role, int& net, int& tile) {
-  const int x = bid & 7;
-  tile = bid >> 3;
-  if (x == 0) { role = 0; net = 0; }
-  else if (x <= 2) { role = 1; net = x - 1; }
-  else if (x <= 4) { role = 2; net = x - 3; }
-  else { role = 3; net = 0; }
-}
 // b.gather != NULL (il_sac_update_gather): the batch has been drawn but not gathered. Every role reads its rows straight from the ring through the
 // indices, and the workgroups behind the 6 * nt chain roles copy the rows to `rows_out` for the later kernels of the update (one 16-byte
 // lane per thread, [IL_SYNC_ROWS] += 1 per workgroup) - they wait for nothing and nobody in this launch waits for them.
@@ -582,8 +561,7 @@ __device__ __forceinline__ void sac_chain_body(il_sac& d, il_batch& b, const flo
   // update's last kernel in its stream, so [IL_SYNC_MAIN_EPOCH] already counts that update; the draw usually finished while this launch was being dispatched.
   const int bid = blockIdx.x;
   int gw = -1, G = 0;   // row-copy workgroup index / count
-  if (rl.xcd_nets) { if ((bid & 7) >= 6) { gw = 2 * (bid >> 3) + (bid & 7) - 6; G = rl.gather_wgs; if (gw >= G) return; } }
-  else if (bid >= 6 * nt) { gw = bid - 6 * nt; G = (int)gridDim.x - 6 * nt; }
+  if (bid >= 6 * nt) { gw = bid - 6 * nt; G = (int)gridDim.x - 6 * nt; }
   IL_TL(0, 0);
   if (rl.wait_indices) { long long* sy = reinterpret_cast<long long*>(d.sync); sync_wait_leader(sy, IL_SYNC_INDICES, sync_read(sy, IL_SYNC_MAIN_EPOCH) + 1); }   // (leader: see k_sac_chain_pair)
   IL_TL(0, 1);
@@ -600,7 +578,7 @@ __device__ __forceinline__ void sac_chain_body(il_sac& d, il_batch& b, const flo
     return;
   }
   int role, net, tile;
-  if (rl.xcd_nets) chain_decode_xcd(bid, role, net, tile); else chain_decode(bid, nt, role, net, tile);
+  chain_decode(bid, nt, role, net, tile);
   const SacWs ws = sac_ws(d.state_dim, d.action_dim, d.hidden, d.batch);
   unsigned* ctr = reinterpret_cast<unsigned*>(d.workspace + ws.chain_ctr) + tile * IL_CTR_STRIDE;
   if (role == 0) { actor_fwd_tile(d, b, eps_next, eps_cur, false, tile, smem); IL_TL(0, 6); tile_arrive(ctr); IL_TL(0, 7); }
@@ -640,17 +618,6 @@ __global__ __launch_bounds__(1024) void k_sac_chain(il_sac d, il_batch b, const 
   sac_chain_body(d, b, eps_next, eps_cur, rewards, rows_out, rl, smem);
   __syncthreads();
   chain_done(d, rl.early_draw);
-}
-
-// Population launch of the chain: grid (6 * nt, learners). Workgroups are dispatched in linear order (x fastest), a role only waits for lower-numbered workgroups of ITS
-// learner (block order actor(s') < targets < critics < actor(s)), so the waits are deadlock-free without the whole grid being co-resident: a producer is always dispatched
-// before its consumers. Replaces k_actor_fwd + k_critic_fwd + k_critic_bwd of the population path (two launches and the h1 / h2 round trip of the critics less).
-__global__ __launch_bounds__(1024) void k_sac_chain_pop(const il_sac* __restrict__ dL, const il_batch* __restrict__ bL) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  il_sac d = dL[blockIdx.y]; il_batch b = bL[blockIdx.y];
-  globalize(d); globalize(b);
-  ChainRelabel rl = {};
-  sac_chain_body(d, b, nullptr, nullptr, nullptr, nullptr, rl, smem);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1102,7 +1069,7 @@ __device__ __forceinline__ void actor_bwd_tile(const il_sac& d, const il_batch& 
     f32x4 o;
 #pragma unroll
     for (int r = 0; r < 4; ++r) { o[r] = hv[r] > 0.f ? acc[r] : 0.f; DZ2s[(4 * g + r) * ldh + kb + j] = o[r]; }
-    if (part == 0) wstore4<(IL_WT_TILE_STORES && PANEL >= 16)>(W, ws.a_dz2 + (int64_t)off, o);
+    if (part == 0) wstore4<false>(W, ws.a_dz2 + (int64_t)off, o);
   });
   __syncthreads();
   IL_STAMP(stamp, 28);
@@ -1112,7 +1079,7 @@ __device__ __forceinline__ void actor_bwd_tile(const il_sac& d, const il_batch& 
     f32x4 o;
 #pragma unroll
     for (int r = 0; r < 4; ++r) o[r] = hv[r] > 0.f ? acc[r] : 0.f;
-    wstore4<(IL_WT_TILE_STORES && PANEL >= 16)>(W, ws.a_dz1 + (int64_t)off, o);
+    wstore4<false>(W, ws.a_dz1 + (int64_t)off, o);
   };
   if (PARK) { if (own_tile) tile_packed_regs(DZ2s, ldh, parked, pt0 + wave, epi_dz1); }
   else tile_bwd_packed<PANEL>(DZ2s, ldh, H, W + ws.pk_ab, epi_dz1, pt0, pt1);
@@ -1123,8 +1090,7 @@ __device__ __forceinline__ void actor_bwd_tile(const il_sac& d, const il_batch& 
 // arriver but by `helpers` extra workgroups per tile that wait for both critics (tile counter) with their own operands already requested,
 // and split the last GEMM between them by output columns. Same arithmetic per element, so the result is bit-identical to helpers = 0.
 #define IL_PC_HELPERS 4
-#define IL_PC_XCD_NETS 0x100   // flag bit in k_policy_critic's `helpers` argument
-#define IL_PC_NO_TAIL 0x200    // flag bit: critic workgroups only, the policy backward is a launch of its own (k_actor_bwd: population path, IL_POP_SPLIT_TAIL)
+#define IL_PC_NO_TAIL 0x200    // flag bit in k_policy_critic's `helpers` argument: critic workgroups only, the policy backward is a launch of its own (k_actor_bwd: population path, IL_POP_SPLIT_TAIL)
 template <int PANEL>
 __device__ __forceinline__ void k_policy_critic_body(il_sac d, il_batch b, float* __restrict__ out_logp, float* __restrict__ out_q, const il_sac* __restrict__ dL,
                                                         const il_batch* __restrict__ bL, int helpers, float* smem) {
@@ -1133,15 +1099,10 @@ __device__ __forceinline__ void k_policy_critic_body(il_sac d, il_batch b, float
   globalize(d); globalize(b);
   const int S = d.state_dim, A = d.action_dim, H = d.hidden, B = d.batch, IN = S + A;
   const int nt = B / IL_TILE_R;
-  // helpers & IL_PC_XCD_NETS (single learner, grid = 8 * nt): one critic per XCD (workgroup b runs on XCD b % 8) - XCD 0 / 1: the nt tiles of critic 0 / 1, XCD 2 ..
-  // 2 + helpers - 1: helper part p of every tile (its column slice of the actor's backward panel is read by that XCD alone), the other blocks exit. Tile q: blocks
-  // 8q, 8q + 1 (critics) < 8q + 2 + p (helpers): a helper still only waits for lower-numbered workgroups.
-  const bool xcd_nets = (helpers & IL_PC_XCD_NETS) != 0;
   const bool no_tail = (helpers & IL_PC_NO_TAIL) != 0;
-  helpers &= ~(IL_PC_XCD_NETS | IL_PC_NO_TAIL);
-  if (xcd_nets && (bx & 7) >= 2 + helpers) return;
-  if (xcd_nets ? (bx & 7) >= 2 : bx >= 2 * nt) {   // helper: block order keeps it behind both critics of its tile (it only waits for lower-numbered workgroups)
-    const int h = xcd_nets ? ((bx & 7) - 2) * nt + (bx >> 3) : bx - 2 * nt, tile = h % nt, part = h / nt;
+  helpers &= ~IL_PC_NO_TAIL;
+  if (bx >= 2 * nt) {   // helper: block order keeps it behind both critics of its tile (it only waits for lower-numbered workgroups)
+    const int h = bx - 2 * nt, tile = h % nt, part = h / nt;
     const SacWs ws = sac_ws(S, A, H, B);
     unsigned* ctr = reinterpret_cast<unsigned*>(d.workspace + ws.pair_ctr) + tile * IL_CTR_STRIDE;
     if (h == 0 && threadIdx.x == 0) { adam_tick(d.actor_opt); adam_tick(d.alpha_opt); }   // consumed by the next kernel
@@ -1157,7 +1118,7 @@ __device__ __forceinline__ void k_policy_critic_body(il_sac d, il_batch b, float
     return;
   }
   int k, tile;
-  if (xcd_nets) { k = bx & 7; tile = bx >> 3; } else xcd_tile_net(bx, nt, 2, tile, k);
+  xcd_tile_net(bx, nt, 2, tile, k);
   const int row0 = tile * IL_TILE_R;
   const int INp = round_up16(IN), ldx = INp + 4, ldh = H + 4;
   float* Xs = smem; float* H1s = Xs + IL_TILE_R * ldx; float* H2s = H1s + IL_TILE_R * ldh; float* q16 = H2s + IL_TILE_R * ldh;
@@ -1175,7 +1136,7 @@ __device__ __forceinline__ void k_policy_critic_body(il_sac d, il_batch b, float
   float w3v[4];
 #pragma unroll
   for (int u = 0; u < 4; ++u) w3v[u] = gload(p.W3 + min(lane + 64 * u, H - 1));
-  constexpr bool cols_pre = IL_SMALL_PREFETCH && PANEL >= 16;   // (the 80-VGPR population build has no registers to park them in)
+  constexpr bool cols_pre = PANEL >= 16;   // (the 80-VGPR population build has no registers to park them in)
   ColsPre w1pre = {};
   if (cols_pre) w1pre = tile_bwd_dx_cols_prefetch(p.W1, IN, IN, H, S);   // the action columns of W1 for dQ/da, the last GEMM of this workgroup
   load_rows_cat(Xs, ldx, INp, b.states, b.ld_states, S, W + ws.a_anew, A, A, row0, IL_TILE_R);
@@ -1407,7 +1368,7 @@ __device__ __forceinline__ void policy_critic_pair(const il_sac& d, const il_bat
     const int kb0 = (S >> 4) << 4;
     for (int kb = kb0; kb < S + A; kb += 16) {
       float bq[4];
-      if (IL_SMALL_PREFETCH && kb == kb0) {
+      if (kb == kb0) {
 #pragma unroll
         for (int s_ = 0; s_ < 4; ++s_) bq[s_] = half == 0 ? w1pre.b[0][s_] : w1pre.b[1][s_];
       } else {
@@ -1695,17 +1656,8 @@ __device__ __forceinline__ void adam_store(const DwArgs& a, const adam_consts& a
   a.params[o] = pp; a.opt.m[o] = mm; a.opt.v[o] = vv;
 }
 
-#ifndef IL_DW_PREFETCH
-#define IL_DW_PREFETCH 1
-#endif
-#ifndef IL_DW_SCHED_BARRIER
-#define IL_DW_SCHED_BARRIER 1   // dw_tile: all operand loads of a chunk ahead of its MFMAs (0 = the round-2 schedule, for A/B builds)
-#endif
 #ifndef IL_TAIL_BLOCKS
 #define IL_TAIL_BLOCKS 69       // single learner: tail blocks of the actor launch (block 0: Adam(log alpha) + counters; all: polyak over the target arena and its lane-ordered copies, one trip each at H = 256)
-#endif
-#ifndef IL_DW_XCD_BLOCKS
-#define IL_DW_XCD_BLOCKS 1      // dw_block_job: the H x H layer's 64 blocks dealt to the XCDs as 2 x 4 rectangles (fabric traffic; 0 = row-major job order)
 #endif
 #ifndef IL_DW_BLOCK32
 #define IL_DW_BLOCK32 1         // single learner: the H x H layers' dW as 32 x 32 blocks staged through LDS (dw_block32); 0 = a wave per 16 x 16 tile straight from global memory
@@ -1737,7 +1689,7 @@ __device__ __forceinline__ void dw_tile(const DwArgs& a, const adam_consts& ac, 
   // HBM latency (they were last touched one update ago) hides under it instead of following it.
   const int k = kb + j, kk = min(k, Kvalid - 1);
   float pp[4], mm[4], vv[4];
-  if (IL_DW_PREFETCH && !a.grads_only) {
+  if (!a.grads_only) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int64_t o = poff + (int64_t)min(n0 + 4 * g + r, Nvalid - 1) * Kvalid + kk;
@@ -1753,7 +1705,7 @@ __device__ __forceinline__ void dw_tile(const DwArgs& a, const adam_consts& ac, 
   for (; r0 + 16 * (UU) <= B; r0 += 16 * (UU)) {                                                                   \
     f32x4 av[UU], bv[UU];                                                                                          \
     _Pragma("unroll") for (int u = 0; u < (UU); ++u) { av[u] = gload4(dzp + r0 + 16 * u); bv[u] = ldx4(r0 + 16 * u); } \
-    if (IL_DW_SCHED_BARRIER) __builtin_amdgcn_sched_barrier(0);                                                    \
+    __builtin_amdgcn_sched_barrier(0);                                                                             \
     _Pragma("unroll") for (int u = 0; u < (UU); ++u) {                                                             \
       acc0 = mfma16(av[u][0], bv[u][0], acc0);                                                                     \
       acc1 = mfma16(av[u][1], bv[u][1], acc1);                                                                     \
@@ -1780,7 +1732,6 @@ __device__ __forceinline__ void dw_tile(const DwArgs& a, const adam_consts& ac, 
     const int n = n0 + 4 * g + r;
     if (n < Nvalid) {
       const int64_t o = poff + (int64_t)n * Kvalid + k;
-      if (!IL_DW_PREFETCH) { pp[r] = a.params[o]; mm[r] = a.opt.m[o]; vv[r] = a.opt.v[o]; }
       adam_update(pp[r], acc[r], mm[r], vv[r], ac);
       a.params[o] = pp[r]; a.opt.m[o] = mm[r]; a.opt.v[o] = vv[r];
     }
@@ -1800,7 +1751,6 @@ __device__ __forceinline__ void dw_bias(const DwArgs& a, const adam_consts& ac, 
   const float* p = dzT + (size_t)min(n0 + j, Nvalid - 1) * B + 4 * g;
   f32x4 s4 = zero4();
   int r0 = 0;
-#if IL_DW_SCHED_BARRIER
   // (round 3) as a plain loop this was load -> s_waitcnt vmcnt(0) -> add, once per 16 rows: sixteen DEPENDENT L2 round trips at B = 256 - the bias jobs, not the MFMA
   // tiles, were the long pole of the launch. All lanes of a chunk are requested first; the adds keep their order (ascending rows), so the sums keep their bits.
   for (; r0 + 256 <= B; r0 += 256) {
@@ -1819,7 +1769,6 @@ __device__ __forceinline__ void dw_bias(const DwArgs& a, const adam_consts& ac, 
 #pragma unroll
     for (int u = 0; u < 4; ++u) s4 += t[u];
   }
-#endif
   for (; r0 < B; r0 += 16) s4 += *reinterpret_cast<const f32x4*>(p + r0);
   float s = (s4[0] + s4[1]) + (s4[2] + s4[3]);
   s += __shfl_xor(s, 16, 64);
@@ -1832,7 +1781,6 @@ __device__ __forceinline__ void dw_tail_alpha(const DwArgs& a, const DwPeer* pp,
   if (a.log_alpha && threadIdx.x == 0) {
     float s = 0.f;
     int i0 = 0;
-#if IL_DW_SCHED_BARRIER
     for (; i0 + 16 <= a.n_alpha_part; i0 += 16) {   // one thread, B / 16 partials: requested together, added in index order (as a plain loop: one dependent round trip per partial)
       float t[16];
 #pragma unroll
@@ -1841,7 +1789,6 @@ __device__ __forceinline__ void dw_tail_alpha(const DwArgs& a, const DwPeer* pp,
 #pragma unroll
       for (int u = 0; u < 16; ++u) s += t[u];
     }
-#endif
     for (int i = i0; i < a.n_alpha_part; ++i) s += a.alpha_part[i];
     const float alpha = expf(a.log_alpha[0]);
     float gr = -(alpha) * (s / (float)a.batch);
@@ -1863,7 +1810,6 @@ __device__ __forceinline__ void dw_tail_alpha(const DwArgs& a, const DwPeer* pp,
 __device__ __forceinline__ void dw_tail_polyak(const DwArgs& a, const int tb, const int ntb) {   // every tail block: target <- tau target + (1 - tau) critic
   if (a.target && !a.grads_only) {
     const float omt = (float)(1.0 - a.tau), tau = (float)a.tau;
-#if IL_DW_SCHED_BARRIER
     // (round 3) target <- tau target + (1 - tau) critic over the parameter arena AND its lane-ordered copies as ONE index space of 16-byte lanes, four lanes per thread
     // and trip with all eight loads requested first: the grid-stride loops below were a dependent HBM round trip per trip (the target was last touched an update ago),
     // 8 trips per thread with 33 tail blocks. Elementwise: the bits do not depend on who computes which lane.
@@ -1884,18 +1830,13 @@ __device__ __forceinline__ void dw_tail_polyak(const DwArgs& a, const int tb, co
 #pragma unroll
           for (int q = 0; q < 4; ++q) t[u][q] = __fadd_rn(__fmul_rn(t[u][q], tau), __fmul_rn(omt, p[u][q]));
           if (i + u * stride < n1 + n2) {
-#if IL_DW_STORE_MODE == 2 && IL_POLYAK_WT
             const int64_t q2 = i + u * stride;   // written through like p / m / v: the target network is not read again before the next update's forward
             if (q2 >= n1) wstore4(a.pk_target, (q2 - n1) * 4, t[u]); else wstore4(a.target, q2 * 4, t[u]);
-#else
-            *dst[u] = t[u];
-#endif
           }
         }
       }
       return;
     }
-#endif
     for (int64_t i = ((int64_t)tb * blockDim.x + threadIdx.x) * 4; i < a.polyak_n; i += (int64_t)ntb * blockDim.x * 4) {
       if (a.polyak_fused) {   // the H x H layers were stepped by the critic launch's blocks: whole lanes inside them are skipped, lanes at their edges go element by element
         // (the twin critic's layout from what the tail knows: polyak_n = 2 strides, stride = H IN + H | H H | H | H | 1 rounded up to a multiple of 4 floats)
@@ -1989,14 +1930,8 @@ __device__ __forceinline__ void dw_adam_body(const DwArgs& a, const int bid, con
 // Every tile keeps dw_tile's two accumulators and its MFMA order (row groups ascending; k-steps 0, 2 -> acc0 and 1, 3 -> acc1), so the gradients, and with them
 // the learners, stay bit-identical to the single-learner kernel.
 // ---------------------------------------------------------------------------------------------
-#ifndef IL_POP_XCD_DW
-#define IL_POP_XCD_DW 1
-#endif
 #define IL_FLAG_POP_FUSE_POLYAK 0x8000u   // internal (set by il_sac_update_population unless IL_POP_FUSE_POLYAK=0): see DwArgs.fuse_polyak
 #define DWB 64            // block edge (features) and batch rows per chunk
-#ifndef IL_POP_DW_EARLY_PMV
-#define IL_POP_DW_EARLY_PMV 1   // 0: p / m / v requested at the start of the AdamW epilogue (round 4; A/B builds)
-#endif
 #define DWB_LD (DWB + 4)
 __device__ __forceinline__ void dw_block64(const DwArgs& a, const adam_consts& ac, const float* __restrict__ dzT, const float* __restrict__ xT, int H, int n0, int k0, int64_t poff,
                                            float* __restrict__ pkf, float* __restrict__ pkb, float* smem, const il_sac* dsrc = nullptr) {
@@ -2046,7 +1981,7 @@ __device__ __forceinline__ void dw_block64(const DwArgs& a, const adam_consts& a
   // workgroup's 16.1 us, profiles/r04_population_timeline.txt) runs under the products. Same loads, same arithmetic: same bits.
   stage();
   f32x4 pv[4], mv[4], vv[4];
-  if (!a.grads_only && IL_POP_DW_EARLY_PMV) {
+  if (!a.grads_only) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int64_t o = poff + (int64_t)(n0 + sf + 16 * u) * H + k0 + sr;
@@ -2079,13 +2014,6 @@ __device__ __forceinline__ void dw_block64(const DwArgs& a, const adam_consts& a
       *reinterpret_cast<f32x4*>(a.grads + poff + (int64_t)(n0 + rr) * H + k0 + sr) = *reinterpret_cast<const f32x4*>(Gs + rr * DWB_LD + sr);
     }
     return;
-  }
-  if (!IL_POP_DW_EARLY_PMV) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int64_t o = poff + (int64_t)(n0 + sf + 16 * u) * H + k0 + sr;
-      pv[u] = gload4(a.params + o); mv[u] = gload4(a.opt.m + o); vv[u] = gload4(a.opt.v + o);
-    }
   }
   // (round 5, IL_POP_FUSE_POLYAK) target <- tau target + (1 - tau) critic for this block, from the NEW parameters in registers: the tail of the actor launch read the
   // target, the critic and both lane-ordered copies again (36 B per H x H parameter); here 4 B are read and 8 written. Same two multiplies and one add per element.
@@ -2158,7 +2086,7 @@ __device__ __forceinline__ void dw_block_job(const DwArgs& a, int net, int job, 
   const float* dz1 = a.dz1 + net * a.h_net_stride; const float* dz2 = a.dz2 + net * a.h_net_stride;
   if (job < nbh * nbh) {
     int nb = job / nbh, kb = job % nbh;
-    if (IL_DW_XCD_BLOCKS && nbh == 8) {
+    if (nbh == 8) {
       // Workgroup b runs on XCD b % 8 (and a network's job list starts at a multiple of 8), and every XCD has a private L2: with (n, k) = (job / 8, job % 8) the eight
       // blocks that share a dZ panel sit on eight different XCDs and every XCD pulls EVERY dZ panel through the fabric. Here XCD x owns the 2 x 4 rectangle of blocks
       // n in {2 (x / 2), + 1}, k in {4 (x % 2) .. + 3}: 2 + 4 panels per XCD instead of 8 + 1. A re-labelling of the jobs: same tiles, same bits.
@@ -2318,8 +2246,6 @@ static int device_cu_count() {
   static const int n = [] { int dev = 0, cu = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cu = 0; return cu; }();
   return n;
 }
-// IL_CHAIN_XCD_NETS=1: single-learner k_sac_chain / k_policy_critic launches place each network's tile workgroups on ONE XCD (chain_decode_xcd; grid = 8 * nt)
-static bool chain_xcd_nets(int nt) { static const int on = [] { const char* e = getenv("IL_CHAIN_XCD_NETS"); return e && e[0] == '1' ? 1 : 0; }(); return on != 0 && 8 * nt <= device_cu_count(); }
 static int pc_helpers(int nt) {
   static const int on = [] { const char* e = getenv("IL_PC_SPLIT"); return e && e[0] == '0' ? 0 : 1; }();
   return (on && (2 + IL_PC_HELPERS) * nt <= device_cu_count()) ? IL_PC_HELPERS : 0;
@@ -2368,8 +2294,7 @@ static void launch_policy_critic(const il_sac* d, const il_batch* b, float* out_
   const int hp = pc_helpers(nt);
   if (quad && !overlap && policy_critic_quad_ok(d)) { k_policy_critic_quad<<<(8 + hp) * nt, 512, IL_PAIR_LDS_BYTES, st>>>(*d, *b, out_logp, out_q, hp); return; }
   if (policy_critic_pair_ok(d)) { k_policy_critic_pair<<<(4 + hp) * nt, 512, IL_PAIR_LDS_BYTES, st>>>(*d, *b, out_logp, out_q, hp, overlap); return; }
-  const bool px = hp > 0 && hp <= 6 && chain_xcd_nets(nt);
-  k_policy_critic<<<px ? 8 * nt : (2 + hp) * nt, tile_threads(H), lds, st>>>(*d, *b, out_logp, out_q, nullptr, nullptr, px ? (hp | IL_PC_XCD_NETS) : hp);
+  k_policy_critic<<<(2 + hp) * nt, tile_threads(H), lds, st>>>(*d, *b, out_logp, out_q, nullptr, nullptr, hp);
 }
 extern "C" int il_sac_critic_step(const il_sac* d, const il_batch* b, const float* eps_next, uint32_t flags, il_stream_t stream_) {
   if (int rc = check_sac(d, b)) return rc;
@@ -2436,17 +2361,16 @@ extern "C" int il_sac_update(const il_sac* d, const il_batch* b, const float* ep
   const bool whole = !(flags & (IL_FLAG_SAC_SKIP_FORWARD | IL_FLAG_SAC_FORWARD_ONLY));
   if (whole && chain_enabled() && 6 * nt <= device_cu_count()) {   // forward + critic loss chained per tile in one co-resident launch (k_sac_chain)
     if (!(flags & IL_FLAG_SAC_PREPARED)) { IL_TRACE("k_repack", st); k_repack<<<dim3(repack_blocks(H), 5), 256, 0, st>>>(*d, 0x1Fu, nullptr); }
-    ChainRelabel cr = {}; cr.xcd_nets = chain_xcd_nets(nt) ? 1 : 0;
+    ChainRelabel cr = {};
     if (chain_pair_ok(d, 0, 0)) { IL_TRACE("k_sac_chain", st); k_sac_chain_pair<<<chain_pair_workgroups(nt, 0, 0), 512, IL_PAIR_LDS_BYTES, st>>>(*d, *b, eps_next, eps_cur, nullptr, nullptr, cr); }
-    else { IL_TRACE("k_sac_chain", st); k_sac_chain<<<(cr.xcd_nets ? 8 : 6) * nt, tile_threads(H), lds, st>>>(*d, *b, eps_next, eps_cur, nullptr, nullptr, cr); }
+    else { IL_TRACE("k_sac_chain", st); k_sac_chain<<<6 * nt, tile_threads(H), lds, st>>>(*d, *b, eps_next, eps_cur, nullptr, nullptr, cr); }
     flags |= IL_FLAG_SAC_SKIP_FORWARD | 0x80000000u;
   }
   if ((flags & IL_FLAG_SAC_FORWARD_ONLY) && !(flags & IL_FLAG_SAC_SKIP_FORWARD) && chain_enabled() && 6 * nt <= device_cu_count()) {
     // the four forward passes as one launch chained per tile (the target critics wait for their tile's actor(s') inside it), no critic backward
     if (!(flags & IL_FLAG_SAC_PREPARED)) { IL_TRACE("k_repack", st); k_repack<<<dim3(repack_blocks(H), 5), 256, 0, st>>>(*d, 0x1Fu, nullptr); }
     ChainRelabel fo = {}; fo.fwd_only = 1;
-    fo.xcd_nets = chain_xcd_nets(nt) ? 1 : 0;
-    { IL_TRACE("k_sac_chain", st); k_sac_chain<<<(fo.xcd_nets ? 8 : 6) * nt, tile_threads(H), lds, st>>>(*d, *b, eps_next, eps_cur, nullptr, nullptr, fo); }
+    { IL_TRACE("k_sac_chain", st); k_sac_chain<<<6 * nt, tile_threads(H), lds, st>>>(*d, *b, eps_next, eps_cur, nullptr, nullptr, fo); }
     IL_CHECK_LAUNCH("il_sac_update");
     return IL_OK;
   }
@@ -2560,10 +2484,7 @@ static int sac_update_gather_impl(const il_sac* d, const il_batch* rows, const i
   }
   if (!(flags & IL_FLAG_SAC_PREPARED)) { IL_TRACE("k_repack", st); k_repack<<<dim3(repack_blocks(H), 5), 256, 0, st>>>(*d, 0x1Fu, nullptr); }
   if (chain_pair_ok(d, rl.on, G)) { IL_TRACE("k_sac_chain", st); k_sac_chain_pair<<<chain_pair_workgroups(nt, rl.on, G), 512, IL_PAIR_LDS_BYTES, st>>>(*d, *ring, eps_next, eps_cur, rewards, const_cast<float*>(rows->states), rl); }
-  else {
-    if (chain_xcd_nets(nt) && G <= 2 * nt) { rl.xcd_nets = 1; rl.gather_wgs = G; }
-    IL_TRACE("k_sac_chain", st); k_sac_chain<<<rl.xcd_nets ? 8 * nt : 6 * nt + G, tile_threads(H), lds, st>>>(*d, *ring, eps_next, eps_cur, rewards, const_cast<float*>(rows->states), rl);
-  }
+  else { IL_TRACE("k_sac_chain", st); k_sac_chain<<<6 * nt + G, tile_threads(H), lds, st>>>(*d, *ring, eps_next, eps_cur, rewards, const_cast<float*>(rows->states), rl); }
   DwArgs ca = critic_dw_args(d, flags);
   if (peer_critic) { DwPeer cp = {*peer_critic, 0}; IL_TRACE("k_dw_adam_critic", st); k_dw_adam_peer<<<ca.n_dw_blocks, 256, 0, st>>>(ca, cp); }
   else { IL_TRACE("k_dw_adam_critic", st); launch_dw_adam(ca, ca.n_dw_blocks, st); }
@@ -2613,37 +2534,11 @@ extern "C" int il_sac_update_gather_peer(const il_sac* d, const il_batch* rows, 
 // are device arrays of n_learners descriptors (each learner has its own arenas, optimiser state, workspace, noise counter and batch);
 // gridDim.y (z for k_repack) selects the learner. Kernels are latency-bound at B = 256 (16-64 workgroups): a population fills the chip.
 // ---------------------------------------------------------------------------------------------
-#ifndef IL_POP_SMALL_BLOCKS
-#define IL_POP_SMALL_BLOCKS 1
-#endif
-__host__ __device__ static inline bool pop_small_blocks(int H, int B) { return IL_POP_SMALL_BLOCKS && H % DWS == 0 && B % DWS_ROWS == 0; }
+__host__ __device__ static inline bool pop_small_blocks(int H, int B) { return H % DWS == 0 && B % DWS_ROWS == 0; }
 // workgroups per learner of a population dW launch behind its nb64 dw_block64 workgroups (without the tail)
 static inline int pop_dw_small_grid(int IN, int H, int OUT, int nets, int B, bool b64) {
   if (b64 && pop_small_blocks(H, B)) return (dw_block_jobs(IN, H, OUT) - (H / DWS) * (H / DWS)) * nets + (H / 16 * nets + 3) / 4;
   return dw_blocks(IN, H, OUT, nets, b64);
-}
-// (round 5, experiment) The dW launches' own decode of the linear workgroup id. pop_ids hands out, per group of 8 learners, the group's 64 x 64 blocks (16 us each), then its 32 x 32
-// block jobs (7 - 10 us), bias jobs and tail, and only then the next group's blocks: the launch is slot-bound (3 - 4 workgroups per CU, profiles/r05_pop_dw_timeline.txt),
-// so the LAST group's block workgroups start at 37 of a 52 us launch and its end is 15 us of a chip that drains. Here: the blocks of ALL full groups first, then
-// everything else - the launch ends on jobs half as long. Learner l stays on XCD l % 8 (both phases start at a multiple of 8); learners behind the last full group of 8
-// keep the natural decode. No job of these launches waits for another one: pure re-labelling, same bits. MEASURED NEUTRAL (three interleaved same-box A/Bs,
-// profiles/r05_pop_dw_ab.txt: +0.8 %, +0.1 %; with 4 waves per SIMD -1 %): with every slot holding a block workgroup the MFMA pipes saturate (products 12 -> 15 - 20 us)
-// and the small jobs' memory latency no longer hides under them. Kept as an A/B switch, OFF: IL_POP_DW_BIG_FIRST=1 selects it.
-#ifndef IL_POP_DW_BIG_FIRST
-#define IL_POP_DW_BIG_FIRST 0
-#endif
-__device__ __forceinline__ void pop_dw_ids(int& bx, int& by, int nb64) {
-#if IL_POP_DW_BIG_FIRST && IL_POP_XCD
-  const int nx = gridDim.x, lf = ((int)gridDim.y >> 3) * 8, g = by * nx + bx;
-  if (nb64 > 0 && nb64 < nx && g < lf * nx) {
-    const int nbig = lf * nb64;
-    if (g < nbig) { const int q = g >> 3; by = (q / nb64) * 8 + (g & 7); bx = q % nb64; }
-    else { const int r = g - nbig, q = r >> 3, nr = nx - nb64; by = (q / nr) * 8 + (r & 7); bx = nb64 + q % nr; }
-    return;
-  }
-  if (g >= lf * nx) return;
-#endif
-  pop_ids(bx, by);
 }
 // (round 5) Register budget of 4 waves per SIMD: the default allocation (121 VGPRs + 32 AGPRs for the accumulators) leaves 3 workgroups per CU; capped at 128 the kernel
 // keeps everything in VGPRs without a spill and a CU holds 4 (LDS: 4 x 34 KB). The launch is slot-bound outside its 64 x 64 blocks' products
@@ -2659,9 +2554,7 @@ __device__ __forceinline__ void pop_dw_ids(int& bx, int& by, int nb64) {
 __global__ __launch_bounds__(256) IL_POP_DW_ATTR void k_dw_adam_pop(const il_sac* __restrict__ dL, const il_batch* __restrict__ bL, int kind, uint32_t flags, int nb64) {
   __shared__ __attribute__((aligned(16))) float smem[2 * DWB * DWB_LD];
   int bx = blockIdx.x, by = blockIdx.y;
-#if IL_POP_XCD_DW
-  pop_dw_ids(bx, by, nb64);   // a learner's blocks on one XCD: the four blocks that share a [64 features][B] operand panel find it in that L2
-#endif
+  pop_ids(bx, by);   // a learner's blocks on one XCD: the four blocks that share a [64 features][B] operand panel find it in that L2
   il_sac d = dL[by]; il_batch b = bL[by];
   globalize(d); globalize(b);
   DwArgs a = kind ? actor_dw_args(&d, &b, flags) : critic_dw_args(&d, flags);
@@ -2731,19 +2624,12 @@ extern "C" int il_sac_update_population(const il_sac* descs_dev, const il_batch*
   static const int pop_threads_env = [] { const char* e = getenv("IL_POP_TILE_THREADS"); return e ? atoi(e) : 0; }();
   const int tt_default = tile_threads(H) >= 512 ? tile_threads(H) / 2 : tile_threads(H);
   const int tt = (pop_threads_env >= 256 && pop_threads_env <= tile_threads(H) && pop_threads_env % 64 == 0) ? pop_threads_env : tt_default;
-  // Measured at 32 learners (round 2): chained 61.6k aggregate updates/s vs 70.7k with the three separate launches (k_sac_chain_pop 215 us against 46 + 71 + 35 us): the
-  // workgroups that wait for their tile's producers hold CU slots the oversubscribed launch needs. Hence OFF by default; IL_POP_CHAIN=1 switches it on.
+  // The forward and the critic loss stay three separate launches here. Measured at 32 learners (round 2): chained per tile in one launch like k_sac_chain, 61.6k aggregate
+  // updates/s vs 70.7k (215 us against 46 + 71 + 35 us): the workgroups that wait for their tile's producers hold CU slots the oversubscribed launch needs.
   // (round 3) the `_pop` builds of the tile kernels (half weight panels, <= 80 VGPRs: three workgroups per CU instead of two) whenever the launch is at most 512 threads wide;
   // IL_POP_THREE=0 keeps the 128-VGPR builds (bit-identical either way)
   static const int pop_three = [] { const char* e = getenv("IL_POP_THREE"); return e && e[0] == '0' ? 0 : 1; }();
   const bool pop3 = pop_three && tt <= 512;
-  static const int pop_chain = [] { const char* e = getenv("IL_POP_CHAIN"); return e && e[0] == '1' ? 1 : 0; }();
-  const bool whole = !(flags & (IL_FLAG_SAC_SKIP_FORWARD | IL_FLAG_SAC_FORWARD_ONLY));
-  if (whole && pop_chain) {   // forward + critic loss chained per tile inside one launch (k_sac_chain_pop); IL_POP_CHAIN=0: the three separate launches
-    if (!(flags & IL_FLAG_SAC_PREPARED)) { IL_TRACE("k_repack", st); k_repack<<<dim3(repack_blocks(H), 5, L), 256, 0, st>>>(z, 0x1Fu, descs_dev); }
-    { IL_TRACE("k_sac_chain", st); k_sac_chain_pop<<<dim3(6 * nt, L), tt, lds, st>>>(descs_dev, batches_dev); }
-    flags |= IL_FLAG_SAC_SKIP_FORWARD | 0x80000000u;
-  }
   if (!(flags & IL_FLAG_SAC_SKIP_FORWARD)) {
     if (!(flags & IL_FLAG_SAC_PREPARED)) { IL_TRACE("k_repack", st); k_repack<<<dim3(repack_blocks(H), 5, L), 256, 0, st>>>(z, 0x1Fu, descs_dev); }
     if (pop3) {
@@ -2755,7 +2641,7 @@ extern "C" int il_sac_update_population(const il_sac* descs_dev, const il_batch*
     }
   }
   if (!(flags & IL_FLAG_SAC_FORWARD_ONLY)) {
-    if (!(flags & 0x80000000u)) {
+    {
       IL_TRACE("k_critic_bwd", st);
       if (pop3) k_critic_bwd_pop<<<dim3(2 * nt, L), tt, lds, st>>>(z, zb, descs_dev, batches_dev);
       else k_critic_bwd<<<dim3(2 * nt, L), tt, lds, st>>>(z, zb, descs_dev, batches_dev);
@@ -2969,8 +2855,7 @@ extern "C" int il_sac_dp_phase(const il_sac* d, const il_batch* b, int32_t phase
   if (phase == 0 && chain_enabled() && 6 * nt <= device_cu_count()) {
     if (!(flags & IL_FLAG_SAC_PREPARED)) { IL_TRACE("k_repack", st); k_repack<<<dim3(repack_blocks(H), 5), 256, 0, st>>>(*d, 0x1Fu, nullptr); }
     ChainRelabel fo = {}; fo.fwd_only = 1;
-    fo.xcd_nets = chain_xcd_nets(nt) ? 1 : 0;
-    { IL_TRACE("k_sac_chain", st); k_sac_chain<<<(fo.xcd_nets ? 8 : 6) * nt, tile_threads(H), lds, st>>>(*d, *b, nullptr, nullptr, nullptr, nullptr, fo); }
+    { IL_TRACE("k_sac_chain", st); k_sac_chain<<<6 * nt, tile_threads(H), lds, st>>>(*d, *b, nullptr, nullptr, nullptr, nullptr, fo); }
   } else if (phase == 0) {
     if (!(flags & IL_FLAG_SAC_PREPARED)) { IL_TRACE("k_repack", st); k_repack<<<dim3(repack_blocks(H), 5), 256, 0, st>>>(*d, 0x1Fu, nullptr); }
     { IL_TRACE("k_actor_fwd", st); k_actor_fwd<<<2 * nt, tile_threads(H), lds, st>>>(*d, *b, nullptr, nullptr, 0, nullptr, nullptr); }

@@ -1,6 +1,6 @@
-"""Python models of two workgroup re-labellings of the HIP kernels (no GPU): what must hold for ANY launch shape is a bijection plus an ordering property the
-device-side waits rely on. The formulas are restated from the kernels (imitation-learning_amd/csrc/mlp_tile.hpp pop_ids, csrc/sac.hip chain_decode_xcd and the
-IL_PC_XCD_NETS decode of k_policy_critic); the -m gpu tests check the kernels themselves bit for bit."""
+"""Python models of workgroup re-labellings of the HIP kernels (no GPU): what must hold for ANY launch shape is a bijection plus an ordering property the
+device-side waits rely on. The formulas are restated from the kernels (imitation-learning_amd/csrc/mlp_tile.hpp pop_ids, csrc/sac.hip dw_block_job); the -m gpu
+tests check the kernels themselves bit for bit."""
 import pytest
 
 
@@ -28,65 +28,6 @@ def test_pop_ids_is_a_bijection_that_pins_a_learner_to_one_xcd_and_keeps_its_blo
   assert len(seen) == nx * L
 
 
-def chain_decode_xcd(bid):
-  x, tile = bid & 7, bid >> 3
-  if x == 0: return 0, 0, tile      # actor(s')
-  if x <= 2: return 1, x - 1, tile  # targets
-  if x <= 4: return 2, x - 3, tile  # critics
-  if x == 5: return 3, 0, tile      # actor(s)
-  return None                        # XCDs 6, 7: row-copy workgroups / idle
-
-
-def pop_dw_ids(bx, by, nx, L, nb64):
-  """csrc/sac.hip pop_dw_ids (IL_POP_DW_BIG_FIRST=1 builds; an A/B switch, off by default): the 64 x 64 block workgroups of ALL full groups of 8 learners first, then every
-  other job; learners behind the last full group keep the natural decode."""
-  lf, g = (L >> 3) * 8, by * nx + bx
-  if 0 < nb64 < nx and g < lf * nx:
-    nbig = lf * nb64
-    if g < nbig:
-      q = g >> 3
-      return q % nb64, (q // nb64) * 8 + (g & 7)
-    r = g - nbig
-    q, nr = r >> 3, nx - nb64
-    return nb64 + q % nr, (q // nr) * 8 + (r & 7)
-  if g >= lf * nx:
-    return bx, by
-  return pop_ids(bx, by, nx, L)
-
-
-@pytest.mark.parametrize('nx,L,nb64', [(72, 32, 32), (69, 18, 16), (69, 9, 16), (72, 3, 32), (69, 64, 16), (40, 16, 0)])
-def test_pop_dw_ids_is_a_bijection_that_keeps_a_learner_on_its_xcd_and_puts_the_blocks_first(nx, L, nb64):
-  seen, lf, first_small = set(), (L >> 3) * 8, None
-  for g in range(nx * L):
-    by, bx = divmod(g, nx)
-    nbx, nby = pop_dw_ids(bx, by, nx, L, nb64)
-    assert 0 <= nbx < nx and 0 <= nby < L and (nbx, nby) not in seen
-    seen.add((nbx, nby))
-    if nby < lf:
-      assert g % 8 == nby % 8
-      if nb64 and nbx >= nb64 and first_small is None: first_small = g
-      if nb64 and nbx < nb64: assert first_small is None, 'every block workgroup of the full groups is dispatched before the first small job'
-  assert len(seen) == nx * L
-
-
-@pytest.mark.parametrize('nt', [1, 5, 16, 32])
-def test_chain_decode_xcd_one_network_per_xcd_and_waits_only_on_lower_blocks(nt):
-  where = {}
-  for bid in range(8 * nt):
-    d = chain_decode_xcd(bid)
-    if d is None: continue
-    role, net, tile = d
-    assert (role, net, tile) not in where and tile < nt
-    where[(role, net, tile)] = bid
-    assert bid % 8 == {(0, 0): 0, (1, 0): 1, (1, 1): 2, (2, 0): 3, (2, 1): 4, (3, 0): 5}[(role, net)], 'every tile of a role-network sits on the same XCD'
-  assert len(where) == 6 * nt
-  for tile in range(nt):
-    for net in (0, 1):
-      assert where[(0, 0, tile)] < where[(1, net, tile)], 'a target waits for actor(s′) of its tile'
-      for tnet in (0, 1):
-        assert where[(1, tnet, tile)] < where[(2, net, tile)], 'a critic waits for both targets of its tile'
-
-
 @pytest.mark.parametrize('nt,helpers', [(16, 4), (5, 4), (16, 6)])
 def test_policy_critic_xcd_decode(nt, helpers):
   crit, help_ = {}, {}
@@ -105,7 +46,7 @@ def test_policy_critic_xcd_decode(nt, helpers):
 
 
 def test_dw_block_xcd_rectangles():
-  """csrc/sac.hip dw_block_job (IL_DW_XCD_BLOCKS): the 64 blocks of an H = 256 layer's dW re-labelled so that XCD x (= workgroup index % 8; a network's job list starts at a
+  """csrc/sac.hip dw_block_job: the 64 blocks of an H = 256 layer's dW re-labelled so that XCD x (= workgroup index % 8; a network's job list starts at a
   multiple of 8) owns the 2 x 4 rectangle n in {2 (x / 2), + 1}, k in {4 (x % 2) .. + 3}: a bijection, 2 + 4 operand panels per XCD instead of 8 + 1."""
   seen, panels = set(), {x: (set(), set()) for x in range(8)}
   for job in range(64):

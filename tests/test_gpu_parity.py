@@ -886,7 +886,7 @@ def test_population_xcd_decode_and_groups_are_bit_identical():
 
 @pytest.mark.gpu
 def test_population_launch_switches_are_bit_identical():
-  """The population path's optional schedules - forward / critic loss chained per tile inside the population launch (IL_POP_CHAIN=1), full-width tile kernels
+  """The population path's optional schedules - full-width tile kernels
   (IL_POP_TILE_THREADS=1024), dW without the LDS-staged blocks (IL_POP_DW_LDS=0), no second stream (IL_POP_OVERLAP=0) - run the same arithmetic per element."""
   import subprocess, sys, json
   code = (
@@ -902,7 +902,7 @@ def test_population_launch_switches_are_bit_identical():
       "  for n in list(nets) + [plan.logp, plan.q, plan.rewards]: h.update(np.ascontiguousarray(N(n.flat if hasattr(n, 'flat') else n)).tobytes())\n"
       "print(json.dumps(dict(digest=h.hexdigest())))\n")
   digests = {}
-  for name, env in (('default', {}), ('chain', dict(IL_POP_CHAIN='1', IL_POP_OVERLAP='0')), ('full width', dict(IL_POP_TILE_THREADS='1024')), ('dw tiles', dict(IL_POP_DW_LDS='0')),
+  for name, env in (('default', {}), ('full width', dict(IL_POP_TILE_THREADS='1024')), ('dw tiles', dict(IL_POP_DW_LDS='0')),
                     ('one stream', dict(IL_POP_OVERLAP='0'))):
     r = subprocess.run([sys.executable, '-c', code], env=dict(os.environ, **env), cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (name, r.stderr[-2000:])
@@ -1328,9 +1328,9 @@ def test_update_plan_batch_sizes_of_the_tuned_configs(monkeypatch, B, ring):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize('switch,B', [('IL_RING_GATHER', 256), ('IL_INLINE_RELABEL', 256), ('IL_SAC_CHAIN', 256), ('IL_PC_SPLIT', 256), ('IL_RESIDENT_SAMPLER', 256), ('IL_RESIDENT_SAMPLER', 80),
-                                      ('IL_SAC_CHAIN', 80), ('IL_RING_GATHER', 80), ('IL_PC_SPLIT', 48), ('IL_CHAIN_XCD_NETS', 256), ('IL_CHAIN_XCD_NETS', 80),
+                                      ('IL_SAC_CHAIN', 80), ('IL_RING_GATHER', 80), ('IL_PC_SPLIT', 48),
                                       ('IL_PAIR', 256), ('IL_PAIR', 128), ('IL_PAIR', 80), ('IL_STAGE_ROWS', 256), ('IL_STAGE_ROWS', 80), ('IL_EARLY_DRAW', 256), ('IL_EARLY_DRAW', 48),
-                                      ('IL_MAIN_OVERLAP', 256), ('IL_MAIN_OVERLAP', 128)])   # IL_MAIN_OVERLAP (round 6): the SAC branch's four launches alternating over two streams (il_sac_update_gather_overlap) against in-order launches   # IL_PAIR: the column-split pairs of k_sac_chain_pair / k_policy_critic_pair against the 16-wave workgroups   # 80 / 48 rows: 5 / 3 tiles, the non-XCD-aware role decode; IL_CHAIN_XCD_NETS: one network per XCD (off by default)
+                                      ('IL_MAIN_OVERLAP', 256), ('IL_MAIN_OVERLAP', 128)])   # IL_MAIN_OVERLAP (round 6): the SAC branch's four launches alternating over two streams (il_sac_update_gather_overlap) against in-order launches   # IL_PAIR: the column-split pairs of k_sac_chain_pair / k_policy_critic_pair against the 16-wave workgroups   # 80 / 48 rows: 5 / 3 tiles, the non-XCD-aware role decode
 def test_schedule_switches_are_bit_identical(monkeypatch, switch, B):
   """Every schedule of the update (rows through il_batch.gather vs a gather kernel, inline relabel vs k_gail_reward, chained vs separate forward / critic-loss
   launches, helper-split vs second-arriver policy tail) runs the same arithmetic per element: switching one off must not change a bit.
