@@ -6,6 +6,10 @@ episode ends by true termination with absorbing=true, `memory.wrap_for_absorbing
 on the sequence-number echo the kernel stores (system-scope release) after the action — no stream synchronisation, no H2D/D2H copies,
 no per-field device ops.  The ring cursor is advanced on the device; the host mirrors it arithmetically for the index draws.
 
+General actor shapes (any depth 1-8, relu / tanh / sigmoid, wide action spaces: `SoftActor.general`) take `il_act_step_general`: the same mailbox, carry and cursor, ONE launch
+where the tile engine of csrc/general.hip applies (hidden a multiple of 16 up to 512, state <= 512, action <= 8), otherwise the per-function path's layer-at-a-time launches
+reading the mailbox plus one commit kernel (still no copies or synchronisation; exact and fused schedules only - a snapshot read across several launches could tear).
+
 Schedules:
   exact   : act(obs) -> env.step -> append(transition) -> [update]           (reference order; 2 launches, 1 wait per env step)
   fused   : step(transition, obs) = append + act in ONE launch on the update stream (the action of step t+1 is sampled before update t)
@@ -77,15 +81,26 @@ def _row(x) -> np.ndarray:
   return np.asarray(x, dtype=np.float32).reshape(-1)
 
 
+def general_one_launch(actor) -> bool:
+  """Whether il_act_step_general runs this general-shape actor's step as ONE launch (the tile engine of csrc/general.hip: hidden a multiple of 16 in 16..512, state <= 512,
+  2 * action <= 16, IL_GENERAL_TILES != 0 - the predicate of il_actor_act_general) or as the layer-at-a-time launches plus a commit kernel (exact / fused schedules only)."""
+  import os
+  H = actor.hidden
+  return (os.environ.get('IL_GENERAL_TILES', '1')[:1] != '0' and H % 16 == 0 and 16 <= H <= 512 and actor.state_size <= 512 and 2 * actor.action_size <= 16 and 1 <= actor.depth <= 8)
+
+
 class ActingWorker:
   """One environment worker feeding one `ReplayMemory` from one `SoftActor` (train.py:151-168)."""
 
   def __init__(self, actor, memory, mirror: bool = False):
     assert _lib.on_device(actor.flat) and _lib.on_device(memory.ring), 'ActingWorker needs the actor and the ring on the GPU (there is no CPU path)'
     assert actor.state_size == memory.state_size and actor.action_size == memory.action_size
-    if getattr(actor, 'general', False):
-      raise NotImplementedError('ActingWorker: the one-launch acting step is built for the fused actor shape (depth 2, ReLU, hidden <= 256, action_size <= 8); a general-shape actor acts through '
-                                'actor(state).sample() (csrc/general.hip)')
+    self.general = bool(getattr(actor, 'general', False))
+    self.one_launch = not self.general or general_one_launch(actor)
+    if mirror and not self.one_launch:
+      raise NotImplementedError(f'ActingWorker(mirror=True): the overlap schedule reads a parameter snapshot, which needs the one-launch acting step - hidden_size a multiple of 16 in 16..512, '
+                                f'state_size <= 512, action_size <= 8 (IL_GENERAL_TILES != 0); this actor (state {actor.state_size}, action {actor.action_size}, hidden {actor.hidden}) acts through '
+                                'several launches per step (csrc/general.hip): use the exact or the fused schedule')
     self.actor, self.memory = actor, memory
     self.S, self.A = memory.state_size, memory.action_size
     self._act_box, self._append_box = _Mailbox(self.S, self.A), _Mailbox(self.S, self.A)
@@ -95,6 +110,12 @@ class ActingWorker:
     self._seed = C.c_uint64(torch.initial_seed() & (2**64 - 1))
     self._fixed = {}
     self._pending_seq = None
+    self._workspace = None
+    if self.general:   # il_act_step_general: depth, activation id and the per-function path's workspace at n = 1, kept with the worker
+      from .models import ACTIVATION_IDS
+      self._depth, self._activation = actor.depth, ACTIVATION_IDS[actor.activation]
+      need = int(_lib.lib().il_actor_workspace_floats_general(self.S, self.A, actor.hidden, actor.depth, 1))
+      self._workspace = torch.zeros(need, dtype=torch.float32, device=dev)
     self.mirror = None
     if mirror:
       self._stride = (actor.flat.numel() + 63) // 64 * 64
@@ -115,9 +136,13 @@ class ActingWorker:
                                   _lib.ptr(self.memory.ring), _lib.ptr(self.memory._ring_state), _lib.ptr(self._version) if snapshot else None,
                                   self._stride if snapshot else 0)
     _, _, p_actor, p_box, p_carry, p_ring, p_state, p_version, stride = fixed
-    fn = _lib.lib().il_act_step   # (looked up per call: UpdatePlan.record_direct walks the hooks with a recording stand-in for the library)
+    L = _lib.lib()   # (looked up per call: UpdatePlan.record_direct walks the hooks with a recording stand-in for the library)
     st = (stream or torch.cuda.current_stream()).cuda_stream
-    rc = fn(p_actor, self.S, self.A, a.hidden, p_box, p_carry, p_ring, p_state, self._seed, a._act_calls & 0xFFFFFFFF, p_version, stride, st)
+    if self.general:
+      rc = L.il_act_step_general(p_actor, self.S, self.A, a.hidden, self._depth, self._activation, p_box, p_carry, p_ring, p_state, self._seed, a._act_calls & 0xFFFFFFFF, p_version, stride,
+                                 _lib.ptr(self._workspace), self._workspace.numel(), st)
+    else:
+      rc = L.il_act_step(p_actor, self.S, self.A, a.hidden, p_box, p_carry, p_ring, p_state, self._seed, a._act_calls & 0xFFFFFFFF, p_version, stride, st)
     if rc: _lib.check(rc)
 
   def _next_seq(self) -> int:

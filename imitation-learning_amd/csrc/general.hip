@@ -415,26 +415,22 @@ struct GtFwdPass {
 };
 struct GtFwd { GtFwdPass p[4]; int n, Bp, npass; };
 
-__global__ __launch_bounds__(512) void k_gt_fwd(GtFwd a) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  // 1-D grid of (tile, pass) pairs, decoded so that the tiles of ONE pass share 8 / passes XCDs (xcd_tile_net): an XCD's private L2 then pulls one or two networks through
-  // the fabric per layer instead of all of them (the first launch of an update, 4 passes x 16 tiles: 31 -> us with every XCD pulling all four networks)
-  int tile_, pass_;
-  xcd_tile_net((int)blockIdx.x, a.Bp / 16, a.npass, tile_, pass_);
-  const GtFwdPass& q = a.p[pass_];
-  const GtNet& nn = q.net;
-  const int H = nn.H, in = nn.in, depth = nn.depth, out = nn.out, act = nn.act, Bp = a.Bp;
-  const int row0 = tile_ * 16, nrows = min(16, a.n - row0);
+// The body of a forward pass on one 16-row tile: input rows cat(f1, f2) -> every hidden layer (g_act) -> the output layer; Os[r * 16 + c] = raw output c of row r.
+// Shared by k_gt_fwd and k_act_step_general, so an acting launch runs il_actor_act_general(n = 1)'s arithmetic by construction. LDS: gt_fwd_lds floats.
+// (The pass fields arrive by reference: k_gt_fwd then loads them from its argument block where they are used, as it did with this body inline - by value they sat in
+// SGPRs across the layers and cost two more SGPR spills.)
+struct GtTile { float* Os; float* part; };
+__device__ __forceinline__ GtTile gt_fwd_tile(float* smem, const GtNet& nn, const float* const& f1, const int& ld1, const int& K1, const float* const& f2, const int& ld2, const int& K2, float* const& X0T, float* const& HT, int Bp, int row0, int nrows,
+                                              bool stamp) {
+  const int H = nn.H, in = nn.in, depth = nn.depth, out = nn.out, act = nn.act;
   const int inp = round_up16(in), ldx = inp + 4, ldh = H + 4;
   float* Xs = smem; float* A0 = Xs + 16 * ldx; float* A1 = A0 + 16 * ldh; float* part = A1 + 16 * ldh; float* Os = part + (H >> 4) * 256;
   const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4, tid = threadIdx.x;
-  const bool stamp = tile_ == 0 && pass_ == 1;
-  IL_STAMP(stamp, 0);
-  load_rows_cat(Xs, ldx, inp, q.f1, q.ld1, q.K1, q.f2, q.ld2, q.K2, row0, nrows);
+  load_rows_cat(Xs, ldx, inp, f1, ld1, K1, f2, ld2, K2, row0, nrows);
   __syncthreads();
   IL_STAMP(stamp, 1);
-  if (q.X0T)
-    for (int i = tid; i < 16 * in; i += blockDim.x) { const int c = i >> 4, r = i & 15; q.X0T[(size_t)c * Bp + row0 + r] = Xs[r * ldx + c]; }
+  if (X0T)
+    for (int i = tid; i < 16 * in; i += blockDim.x) { const int c = i >> 4, r = i & 15; X0T[(size_t)c * Bp + row0 + r] = Xs[r * ldx + c]; }
   const float* P = nn.P;
   float* cur = A0; float* nxt = A1;
   const int wcol = min((int)(threadIdx.x >> 6) * 16 + j, H - 1);   // this lane's column of the wave's FIRST output tile: its bias is requested ahead of each layer's MFMAs
@@ -447,7 +443,7 @@ __global__ __launch_bounds__(512) void k_gt_fwd(GtFwd a) {
       f32x4 hv;
 #pragma unroll
       for (int r = 0; r < 4; ++r) { hv[r] = g_act(acc[r] + bb, act); cur[(4 * g + r) * ldh + col] = hv[r]; }
-      if (q.HT) *reinterpret_cast<f32x4*>(q.HT + (size_t)col * Bp + row0 + 4 * g) = hv;
+      if (HT) *reinterpret_cast<f32x4*>(HT + (size_t)col * Bp + row0 + 4 * g) = hv;
     });
   }
   __syncthreads();
@@ -455,7 +451,7 @@ __global__ __launch_bounds__(512) void k_gt_fwd(GtFwd a) {
   for (int l = 1; l < depth; ++l) {
     const GLayer L = g_layer(in, H, depth, out, l);
     const float* bias = P + L.ob;
-    float* ht = q.HT ? q.HT + (size_t)l * H * Bp : nullptr;
+    float* ht = HT ? HT + (size_t)l * H * Bp : nullptr;
     const float pb = gload(bias + wcol);
     auto epi = [&](int c0, f32x4 acc) {
       const int col = c0 + j; const float bb = col == wcol ? pb : gload(bias + col);
@@ -474,12 +470,29 @@ __global__ __launch_bounds__(512) void k_gt_fwd(GtFwd a) {
     const GLayer L = g_layer(in, H, depth, out, depth);
     tile_fwd_small(cur, ldh, H, P + L.oW, H, out, P + L.ob, Os, part);   // (barriers inside)
   }
+  return GtTile{Os, part};
+}
+
+__global__ __launch_bounds__(512) void k_gt_fwd(GtFwd a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  // 1-D grid of (tile, pass) pairs, decoded so that the tiles of ONE pass share 8 / passes XCDs (xcd_tile_net): an XCD's private L2 then pulls one or two networks through
+  // the fabric per layer instead of all of them (the first launch of an update, 4 passes x 16 tiles: 31 -> us with every XCD pulling all four networks)
+  int tile_, pass_;
+  xcd_tile_net((int)blockIdx.x, a.Bp / 16, a.npass, tile_, pass_);
+  const GtFwdPass& q = a.p[pass_];
+  const int out = q.net.out, Bp = a.Bp;
+  const int row0 = tile_ * 16, nrows = min(16, a.n - row0);
+  const int tid = threadIdx.x;
+  const bool stamp = tile_ == 0 && pass_ == 1;
+  IL_STAMP(stamp, 0);
+  const GtTile t = gt_fwd_tile(smem, q.net, q.f1, q.ld1, q.K1, q.f2, q.ld2, q.K2, q.X0T, q.HT, Bp, row0, nrows, stamp);
+  float* Os = t.Os; float* part = t.part;
   IL_STAMP(stamp, 10);
   if (q.OT)
     for (int i = tid; i < 16 * out; i += blockDim.x) { const int c = i >> 4, r = i & 15; q.OT[(size_t)c * Bp + row0 + r] = Os[r * 16 + c]; }
   if (q.head) {   // k_g_sample's arithmetic: one thread per (row, component) (a thread per row walked A Philox draws and heads one after the other: ~5 us of the launch), then
     const int A = out >> 1;                                                       // the per-row sums in component order, as k_g_sample adds them
-    float* nl = part; float* la = part + 256;
+    float* nl = part; float* la = Os + 256;   // (la used to be part + 256, which IS Os when H == 16: the OT copy above could then read what a faster wave had already overwritten)
     if (tid < 16 * A) {
       const int r = tid / A, c = tid - r * A, row = row0 + r;
       if (row < a.n) {
@@ -813,7 +826,8 @@ static bool gt_shape_ok(const GNet& s) {
   (void)al;
   return s.H % 16 == 0 && s.H >= 16 && s.H <= 512 && s.in <= 512 && s.out <= 16 && s.depth >= 1 && s.depth <= 8;
 }
-static size_t gt_fwd_lds(const GNet& s) { return sizeof(float) * ((size_t)16 * (round_up16(s.in) + 4) + 2 * (size_t)16 * (s.H + 4) + (size_t)(s.H >> 4) * 256 + 256); }
+// input tile, two activation tiles, the output layer's partial tiles, Os [16][16], and 256 floats of head scratch of their own (never aliasing Os, whatever H is)
+static size_t gt_fwd_lds(const GNet& s) { return sizeof(float) * ((size_t)16 * (round_up16(s.in) + 4) + 2 * (size_t)16 * (s.H + 4) + (size_t)(s.H >> 4) * 256 + 256 + 256); }
 static size_t gt_bwd_lds(const GNet& s) { return sizeof(float) * ((size_t)16 * 20 + 2 * (size_t)16 * (s.H + 4)); }
 // packed copies need 16-byte aligned H x H layers (their offset in the flat vector is a multiple of 4 floats) - otherwise the passes read W directly
 static bool gt_packable(const GNet& s, const float* P) {
@@ -1133,6 +1147,153 @@ extern "C" int il_bc_step_general(float* actor, float* actor_grad, const il_adam
   if (int rc = g_backward(st, an, actor, 0, 1, workspace + ws.x, 0, workspace + ws.h, workspace + ws.dout, workspace + ws.dz, nullptr, G, 0, Bp)) return rc;
   if (!grads_only) { if (int rc = il_adam_step(actor, G, opt, g_numel(S, H, depth, 2 * A), IL_FLAG_TICK, stream_)) return rc; }
   IL_CHECK_LAUNCH("il_bc_step_general");
+  return IL_OK;
+}
+// ---------------------------------------------------------------------------------------------------------------------------------------------------------------
+// One environment step of the acting worker (train.py:151-168) for general actor shapes (models.py:48-69, 90-94): il_act_step's contract - mailbox, IL_ACT_* flags, carry,
+// exactly-once append by commit word, ring_state, mirror selection (include/il_hip.h) - with the append, the carry copy and the mailbox reads STRIDED over the workgroup:
+// a ring row is 2S + A + 5 floats (up to ~1,040 at S = 512) against 256 - 512 threads, where k_act_step relies on row <= threads and 64 + S <= threads.
+// ---------------------------------------------------------------------------------------------------------------------------------------------------------------
+struct GActStep {
+  const float* actor; int S, A, H, depth, act;
+  float* mail; float* carry; float* ring; long long* ring_state; int row;
+  uint64_t seed; uint32_t offset; const int* version; long long mirror_stride;
+  const float* outT; int Bp;   // commit form only: the head outputs [2A][Bp] that g_forward left in the workspace
+};
+struct GActPost {
+  float commit; unsigned word, flags; bool pending, wrap; long long cursor, cap;
+  const float* m_next; const float* m_obs; float* m_act; float* m_echo;
+};
+// what this launch has to do: the commit word (the LAST thing the host writes), whether its transition is still to be appended (carry[S + A] holds the commit word of the
+// last appended one), and the cursor - every thread reads them here, before anything below is written
+__device__ __forceinline__ GActPost g_act_post(const GActStep& a) {
+  GActPost p;
+  const int Sp4 = (a.S + 3) & ~3, Ap4 = (a.A + 3) & ~3;
+  p.m_next = a.mail + IL_MAIL_HEADER; p.m_obs = p.m_next + Sp4; p.m_act = a.mail + IL_MAIL_HEADER + 2 * Sp4; p.m_echo = p.m_act + Ap4;
+  p.commit = a.mail[0];
+  p.word = (unsigned)p.commit; p.flags = p.word & 63u;
+  p.cursor = a.ring_state[0]; p.cap = a.ring_state[2];
+  p.pending = (p.flags & IL_ACT_PENDING) && __float_as_uint(a.carry[a.S + a.A]) != p.word;
+  p.wrap = p.pending && (p.flags & IL_ACT_WRAP_ABSORBING);
+  return p;
+}
+// memory.py:40-44 append (+ memory.py:65-68 absorbing wrap) of the pending transition: k_act_step's row, one column per thread per trip
+__device__ __forceinline__ void g_act_append(const GActStep& a, const GActPost& p) {
+  if (!p.pending) return;
+  const int S = a.S, A = a.A, row = a.row, o_next = S + A, o_rew = 2 * S + A;
+  const float* mail = a.mail;
+  for (int c = threadIdx.x; c < row; c += blockDim.x) {
+    float v = 0.f;
+    if (c < o_next) v = (p.flags & IL_ACT_CARRY_FROM_MAILBOX) ? (c < S ? p.m_obs[c] : p.m_act[c - S]) : a.carry[c];   // state | action of the transition
+    else if (c < o_rew) v = p.wrap ? (c == o_rew - 1 ? 1.f : 0.f) : p.m_next[c - o_next];    // next_state, or the absorbing state (memory.py:67)
+    else if (c == o_rew) v = mail[2];                                                        // reward
+    else if (c == o_rew + 1) v = p.wrap ? 0.f : mail[3];                                     // terminal (cleared by the wrap)
+    else if (c == o_rew + 2) v = mail[4];                                                    // timeout
+    else if (c == o_rew + 3) v = 1.f;                                                        // weight
+    else if (c == o_rew + 4) v = mail[5];                                                    // step
+    a.ring[p.cursor * row + c] = v;
+    if (p.wrap) {  // absorbing -> absorbing row (memory.py:68)
+      float w = 0.f;
+      if (c < S) w = (c == S - 1) ? 1.f : 0.f;
+      else if (c >= o_next && c < o_rew) w = (c == o_rew - 1) ? 1.f : 0.f;
+      else if (c == o_rew + 3) w = 1.f;
+      else if (c == o_rew + 4) w = mail[5];
+      a.ring[((p.cursor + 1) % p.cap) * row + c] = w;
+    }
+  }
+}
+// the cursor, the `full` flag and the consumed commit word move only here, by one thread behind the launch's LAST barrier: an append-only launch (IL_ACT_NO_ACTION) has no
+// other barrier between the waves' loads of ring_state[0] / carry[S + A] in g_act_post and these stores (the race the emulator found in k_act_step). Then the echo.
+__device__ __forceinline__ void g_act_commit(const GActStep& a, const GActPost& p) {
+  __threadfence_system();
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (p.pending) {
+      const long long adv = p.wrap ? 2 : 1, nc = p.cursor + adv;
+      a.ring_state[0] = nc % p.cap;
+      if (nc >= p.cap) a.ring_state[1] = 1;
+      a.carry[a.S + a.A] = __uint_as_float(p.word);
+    }
+    __hip_atomic_store(p.m_echo, p.commit, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+// Tile-engine shapes (gt_shape_ok): the whole step in ONE launch of one workgroup of gt_threads(H) threads. The actor runs as k_gt_fwd runs a tile with one valid row
+// (gt_fwd_tile, weights read directly), so the action is bit-identical to il_actor_act_general(n = 1) at the same Philox offset. The head keeps its values in registers:
+// nothing of it lives in LDS, so there is no scratch that could alias Os (k_gt_fwd's log-probability scratch did at H == 16).
+__global__ __launch_bounds__(512) void k_act_step_general(GActStep a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const float* actor = a.actor;
+  if (a.version) actor += (size_t)a.version[0] * a.mirror_stride;   // published snapshot (il_act_publish), selected ONCE: never the arena an update is rewriting
+  const int tid = threadIdx.x, S = a.S, A = a.A;
+  const GActPost p = g_act_post(a);
+  g_act_append(a, p);
+  if (!(p.flags & IL_ACT_NO_ACTION)) {  // block-uniform
+    const GtNet nn = {actor, S, a.H, a.depth, 2 * A, a.act, nullptr, nullptr};
+    const GtTile t = gt_fwd_tile(smem, nn, p.m_obs, (S + 3) & ~3, S, nullptr, 0, 0, nullptr, nullptr, 16, 0, 1, false);   // barriers inside: every carry[] read above precedes the writes below
+    if (tid < A) {   // row 0 of k_gt_fwd's head: Philox index row * A + c = c
+      const float mean = t.Os[tid], lsr = t.Os[A + tid];
+      float x, av, nlp, ladj;
+      if (p.flags & IL_ACT_GREEDY) av = tanhf(mean);
+      else g_head(mean, lsr, philox_normal(a.seed, a.offset, IL_STREAM_ACT, (uint32_t)tid), x, av, nlp, ladj);
+      p.m_act[tid] = av; a.carry[S + tid] = av;
+    }
+    for (int c = tid; c < S; c += blockDim.x) a.carry[c] = p.m_obs[c];
+  }
+  g_act_commit(a, p);
+}
+// Every other shape g_check_shape admits: the commit that follows the layer-at-a-time forward (k_g_pack from the mailbox's observation, k_g_linear per layer) of the same
+// step - the append, k_g_sample's head for row 0 from the workspace, the carry and the echo.
+__global__ __launch_bounds__(256) void k_act_commit_general(GActStep a) {
+  const int tid = threadIdx.x, S = a.S, A = a.A;
+  const GActPost p = g_act_post(a);
+  g_act_append(a, p);
+  if (!(p.flags & IL_ACT_NO_ACTION)) {  // block-uniform
+    __syncthreads();   // every carry[] read of the append precedes the writes below
+    for (int c = tid; c < A; c += blockDim.x) {
+      const float mean = a.outT[(size_t)c * a.Bp], lsr = a.outT[(size_t)(A + c) * a.Bp];
+      float x, av, nlp, ladj;
+      if (p.flags & IL_ACT_GREEDY) av = tanhf(mean);
+      else g_head(mean, lsr, philox_normal(a.seed, a.offset, IL_STREAM_ACT, (uint32_t)c), x, av, nlp, ladj);
+      p.m_act[c] = av; a.carry[S + c] = av;
+    }
+    for (int c = tid; c < S; c += blockDim.x) a.carry[c] = p.m_obs[c];
+  }
+  g_act_commit(a, p);
+}
+
+// train.py:151-168 per environment step - `actor(state).sample()` (models.py:48-69 any depth / activation, models.py:90-94 the tanh-Gaussian sample), memory.append and
+// wrap_for_absorbing_states - for general actor shapes; il_act_step's arguments + depth, activation and a workspace of il_actor_workspace_floats_general(S, A, H, depth, 1)
+extern "C" int il_act_step_general(const float* actor, int32_t S, int32_t A, int32_t H, int32_t depth, int32_t activation, float* mailbox, float* carry, float* ring, int64_t* ring_state,
+                                   uint64_t noise_seed, uint32_t noise_offset, const int32_t* mirror_version, int64_t mirror_stride, float* workspace, int64_t workspace_floats,
+                                   il_stream_t stream_) {
+  IL_CHECK_ARG(actor && mailbox && carry && ring && ring_state && workspace, "il_act_step_general: null argument");
+  const GNet an = {S, H, depth, 2 * A, activation};
+  if (int rc = g_check_shape(an, "il_act_step_general")) return rc;
+  IL_CHECK_ARG(workspace_floats >= il_actor_workspace_floats_general(S, A, H, depth, 1), "il_act_step_general: workspace too small");
+  hipStream_t st = (hipStream_t)stream_;
+  GActStep a = {};
+  a.actor = actor; a.S = S; a.A = A; a.H = H; a.depth = depth; a.act = activation; a.mail = mailbox; a.carry = carry; a.ring = ring; a.ring_state = (long long*)ring_state;
+  a.row = il_ring_row_floats(S, A); a.seed = noise_seed; a.offset = noise_offset; a.version = mirror_version; a.mirror_stride = mirror_stride;
+  if (gt_env() && gt_shape_ok(an)) {   // the predicate of il_actor_act_general: whatever the per-function path does for a shape, the worker does the same arithmetic
+    const size_t lds = gt_fwd_lds(an);
+    if (int rc = g_lds_ok((const void*)k_act_step_general, lds)) return rc;
+    { IL_TRACE("k_act_step_general", st); k_act_step_general<<<1, gt_threads(H), lds, st>>>(a); }
+    IL_CHECK_LAUNCH("il_act_step_general (tile engine)");
+    return IL_OK;
+  }
+  // Layer-at-a-time form: several launches read ONE post. That holds because the host waits for an act's echo before it posts to that mailbox again (exact and fused
+  // schedules: ActingWorker.act / step / append), so nothing can change the observation between k_g_pack and the commit. A parameter snapshot selected by a version word
+  // could change between two of the launches (a torn read across layers): refused.
+  IL_CHECK_ARG(!mirror_version, "il_act_step_general: a parameter mirror needs the one-launch form (hidden a multiple of 16 in 16..512, state_dim <= 512, action_dim <= 8; got in=%d hidden=%d "
+               "action_dim=%d%s): the layer-at-a-time form reads the parameters in several launches", S, H, A, gt_env() ? "" : ", IL_GENERAL_TILES=0");
+  const int Bp = 16;
+  const GActWs ws = g_act_ws(S, A, H, depth, Bp);
+  g_pack(st, mailbox + IL_MAIL_HEADER + ((S + 3) & ~3), (S + 3) & ~3, S, nullptr, 0, 0, 1, Bp, workspace + ws.x);   // (an append-only post runs the forward too: what a launch does is decided on the device, from the commit word)
+  if (int rc = g_forward(st, an, actor, 0, 1, workspace + ws.x, 0, workspace + ws.h, workspace + ws.o, Bp)) return rc;
+  a.outT = workspace + ws.o; a.Bp = Bp;
+  { IL_TRACE("k_act_commit_general", st); k_act_commit_general<<<1, 256, 0, st>>>(a); }
+  IL_CHECK_LAUNCH("il_act_step_general");
   return IL_OK;
 }
 IL_STAMP_READER(il_debug_stamps_general)

@@ -1259,6 +1259,8 @@ class UpdatePlan:
       for fn, args in self._direct_side + self._direct_main:
         if any(t is C.c_float or t is C.c_double for t in (fn.argtypes or ())):
           raise NotImplementedError(f'launch_async: {fn.__name__} takes floating-point arguments; the launcher re-issues integer / pointer arguments only (use launch_direct)')
+        if len(args) > 16:
+          raise NotImplementedError(f'launch_async: {fn.__name__} takes {len(args)} arguments; the launcher re-issues up to 16 (use launch_direct)')
         words = (C.c_uint64 * 16)(*[self._word(a) for a in args])
         _lib.check(L.il_launcher_add(self._launcher, C.cast(fn, C.c_void_p), words, len(args)))
       self._launcher_of = (self._direct_side, self._direct_main)

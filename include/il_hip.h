@@ -397,6 +397,17 @@ int il_act_step(const float* actor, int32_t state_dim, int32_t action_dim, int32
 /* Publish the actor arena (n floats) into snapshot slot (version+1)%3 of `mirror` and advance the version. version_and_counter: device
  * int32[2] = {version, internal completion counter}, zero-initialised. Enqueue after every update (capturable into the update's graph). */
 int il_act_publish(const float* actor, int64_t n, float* mirror, int64_t mirror_stride, int32_t* version_and_counter, il_stream_t stream);
+/* il_act_step for the general actor shapes of il_actor_act_general (train.py:151-168 with `actor(state).sample()` of models.py:48-69 any depth / relu, tanh, sigmoid and
+ * models.py:90-94 the tanh-Gaussian sample): the same mailbox layout, IL_ACT_* flags, carry (exactly-once append by commit word), ring_state and mirror selection.
+ * workspace >= il_actor_workspace_floats_general(S, A, H, depth, 1) floats (the per-function path's own workspace size at n = 1; there is no separate size function).
+ * Two forms, chosen by the predicate il_actor_act_general uses (so the action is that entry point's, bit for bit, at the same noise_offset):
+ *   (a) hidden a multiple of 16 in 16..512, state_dim <= 512, 2 * action_dim <= 16, IL_GENERAL_TILES != 0: ONE launch (k_act_step_general), any schedule, mirror allowed;
+ *   (b) every other shape: k_g_pack (reading the observation from the mailbox) + one k_g_linear per layer + one commit kernel (append, head, carry, echo) - several
+ *       launches, still no copy and no synchronisation. They read ONE post: the caller must not post to this mailbox again before the echo of this call (the exact and
+ *       fused schedules of ActingWorker). mirror_version != NULL is an argument error in this form (a snapshot read across several launches could tear). */
+int il_act_step_general(const float* actor, int32_t state_dim, int32_t action_dim, int32_t hidden, int32_t depth, int32_t activation, float* mailbox, float* carry, float* ring,
+                        int64_t* ring_state, uint64_t noise_seed, uint32_t noise_offset, const int32_t* mirror_version, int64_t mirror_stride, float* workspace,
+                        int64_t workspace_floats, il_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * GAIL discriminator (reference training.py:85-134 adversarial_imitation_update with loss_function=BCE;

@@ -171,7 +171,6 @@ def train(cfg, file_prefix: str = '') -> float:
   if cfg.algorithm == 'GAIL' and (mixed or cfg.imitation.bc_aux_loss):
     fusable = False   # a mix between the discriminator step and the relabel / an auxiliary actor step on the expert batch: per-function path. (Every discriminator variant -
     # loss functions, finite PUGAIL margin, subtract_log_policy, reward shaping, depth 2 / tanh, Mixup with any alpha - is captured by UpdatePlan.)
-  general = bool(getattr(actor, 'general', False) or getattr(critic, 'general', False))   # reinforcement.actor / critic outside depth 2 / relu / hidden <= 256 (csrc/general.hip): the plan runs them on one stream, captured as one graph
   if fusable:
     plan = il.UpdatePlan(cfg.algorithm, actor, critic, log_alpha, target_critic, memory, actor_optimiser, critic_optimiser, temperature_optimiser, B, cfg.reinforcement.discount,
                          entropy_target, cfg.reinforcement.polyak_factor, expert_memory=expert_memory, discriminator=discriminator, discriminator_optimiser=discriminator_optimiser,
@@ -187,7 +186,13 @@ def train(cfg, file_prefix: str = '') -> float:
   # acting (train.py:151-168): il_act_step through a pinned mailbox; PWIL computes its reward per step on the device and keeps the per-function path
   schedule = (cfg.get('acting', {}) or {}).get('schedule', 'exact')  # `+acting.schedule=fused|overlap`: see imitation_learning_amd/acting.py (behaviour policy lags 1-2 updates)
   assert schedule in ('exact', 'fused', 'overlap', 'per_function')
-  worker = il.ActingWorker(actor, memory, mirror=schedule == 'overlap') if cfg.algorithm != 'PWIL' and schedule != 'per_function' and not general else None
+  # general actor shapes (csrc/general.hip) take the same worker: one launch per step where the tile engine applies, else the layer-at-a-time launches + a commit kernel
+  worker = None
+  if cfg.algorithm != 'PWIL' and schedule != 'per_function':
+    try:
+      worker = il.ActingWorker(actor, memory, mirror=schedule == 'overlap')
+    except NotImplementedError as e:   # overlap with an actor outside the one-launch shapes: the per-function path, as before the worker covered general shapes
+      print(f'[train] +acting.schedule={schedule}: {e}; acting through the per-function path', file=sys.stderr)
   if worker is None: schedule = 'per_function'
   if schedule == 'overlap' and world > 1:
     raise NotImplementedError('+acting.schedule=overlap with distributed.world_size > 1: the overlap schedule captures the append in the update plan\'s hooks, which the '
@@ -255,7 +260,7 @@ def train(cfg, file_prefix: str = '') -> float:
             # this thread posts the next observation and steps the environment; every host-side read / launch of this learner below drains the launcher first. Opt-in: it pays
             # when an environment step costs more than the act launch's turn-around (a real simulator); on the synthetic environment it measured 10.3k against 11.5k
             # env-steps/s (profiles/r06_acting.json: the loop is bound by that turn-around, which then has nothing to hide behind).
-            use_thread = schedule == 'overlap' and not plan._direct_overlap and os.environ.get('IL_TRAIN_LAUNCH_THREAD', '0') == '1'
+            use_thread = schedule == 'overlap' and not plan._direct_overlap and not worker.general and os.environ.get('IL_TRAIN_LAUNCH_THREAD', '0') == '1'   # (il_act_step_general has more arguments than the launcher re-issues)
             step_update = plan.launch_async if use_thread else plan.launch_direct
           elif runner is not plan and runner.direct_launch_ok() and os.environ.get('IL_TRAIN_LAUNCH', 'direct') != 'graph':
             runner.record_direct()   # (round 6) data parallel with the exchanges inside the optimiser launches: the launch sequence of one GPU, issued the same way
