@@ -94,6 +94,10 @@ class Dril(C.Structure):
               ('depth', C.c_int32), ('reserved', C.c_int32), ('noise_counter', C.c_void_p)]
 
 
+class Epoch(C.Structure):   # il_epoch: a device-resident epoch of expert batches (the *_epoch_steps entry points)
+  _fields_ = [('cursor', C.c_void_p), ('n_batches', C.c_int64), ('noise_base', C.c_uint32)]
+
+
 class SampleArgs(C.Structure):
   _fields_ = [('state', C.c_void_p),
               ('ring_state_a', C.c_void_p), ('ring_a', C.c_void_p), ('capacity_a', C.c_int64), ('row_floats_a', C.c_int32), ('idx_a', C.c_void_p), ('rows_a', C.c_void_p),
@@ -229,6 +233,12 @@ _SIGNATURES = {
     'il_red_workspace_floats': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'il_red_step': (C.c_int, [C.POINTER(Red), C.POINTER(Batch), _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P]),
     'il_red_forward': (C.c_int, [C.POINTER(Red), C.POINTER(Batch), C.c_int32, _P, _P, _P, C.c_uint32, _P, _P, _P, _P]),
+    # device-resident expert epochs: the per-function sibling's arguments + (il_epoch*, steps)
+    'il_bc_epoch_steps': (C.c_int, [_P, _P, C.POINTER(Adam), C.c_int32, C.c_int32, C.c_int32, C.POINTER(Batch), _P, C.c_int64, _P, C.c_uint32, C.POINTER(Epoch), C.c_int32, _P]),
+    'il_bc_epoch_workspace_floats_general': (C.c_int64, [C.c_int32] * 5),
+    'il_bc_epoch_steps_general': (C.c_int, [_P, _P, C.POINTER(Adam), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Batch), _P, C.c_int64, _P, C.c_uint32, C.POINTER(Epoch), C.c_int32, _P]),
+    'il_dril_bc_epoch_steps': (C.c_int, [C.POINTER(Dril), C.POINTER(Batch), _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(Epoch), C.c_int32, _P]),
+    'il_red_epoch_steps': (C.c_int, [C.POINTER(Red), C.POINTER(Batch), _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(Epoch), C.c_int32, _P]),
 }
 
 

@@ -65,7 +65,7 @@ __device__ __forceinline__ void dril_forward(const il_dril& d, const il_batch& b
   for (int i = tid; i < rows * S; i += nthr) {
     const int v = i / S, k = i - v * S, r = row0 + v / rep;
     const size_t gv = (size_t)row0 * rep + v;   // global virtual row: index into the masks
-    L.X[v * ldx + k] = (r < b.n) ? b.states[(size_t)r * b.ld_states + k] * keep_scale(mk.in, gv * S + k, d.p_in, d.noise_seed, mk.ctr, IL_STREAM_DROP_IN) : 0.f;
+    L.X[v * ldx + k] = (r < b.n) ? b.states[brow(b, r) * b.ld_states + k] * keep_scale(mk.in, gv * S + k, d.p_in, d.noise_seed, mk.ctr, IL_STREAM_DROP_IN) : 0.f;
   }
   __syncthreads();
   for (int layer = 0; layer < depth; ++layer) {
@@ -103,7 +103,7 @@ __device__ __forceinline__ float dril_logp_row(const il_dril& d, const il_batch&
   for (int c = 0; c < A; ++c) {
     const float mean = Orow[c], lsr = Orow[A + c];
     const float ls = fminf(fmaxf(lsr, -20.f), 2.f), sd = expf(ls);
-    const float a = fminf(fmaxf(b.actions[(size_t)r * b.ld_actions + c], -1.f + 1e-6f), 1.f - 1e-6f);   // models.py:98
+    const float a = fminf(fmaxf(b.actions[brow(b, r) * b.ld_actions + c], -1.f + 1e-6f), 1.f - 1e-6f);   // models.py:98
     const float x = atanhf(a), dx = x - mean;
     sn += -(dx * dx) / (2.f * (sd * sd)) - logf(sd) - LOG_SQRT_2PI;
     sl += 2.f * (LOG_2 - x - softplus_f(-2.f * x));
@@ -118,8 +118,9 @@ __device__ __forceinline__ float dril_logp_row(const il_dril& d, const il_batch&
 }
 
 template <int DEPTH>
-__global__ __launch_bounds__(256) void k_dril_grad(il_dril d, il_batch b, DrilMasks mk) {
+__global__ __launch_bounds__(256) void k_dril_grad(il_dril d, il_batch b, DrilMasks mk, il_epoch ep) {
   if (d.noise_counter) mk.ctr += *d.noise_counter;   // captured plans: the per-update part of the Philox counter lives on the device
+  if (ep.cursor) mk.ctr += epoch_bind(ep, b, blockIdx.x == 0 && threadIdx.x == 0);   // device-resident epoch: this step's rows and Philox counter
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int depth = DEPTH;
   const int S = d.state_dim, A = d.action_dim, H = d.hidden, B = b.n, ldx = S + 1, ldh = H + 1, relu = d.activation == 1;
@@ -133,7 +134,7 @@ __global__ __launch_bounds__(256) void k_dril_grad(il_dril d, il_batch b, DrilMa
     const int r = row0 + tid;
     float l = 0.f;
     if (r < B) {
-      const float w = b.weights[(size_t)r * b.ld_weights];
+      const float w = b.weights[brow(b, r) * b.ld_weights];
       const float logp = dril_logp_row(d, b, r, O + tid * 17, true, -w / (float)B);
       l = w * -logp;
     } else {
@@ -213,7 +214,7 @@ __global__ __launch_bounds__(256) void k_dril_grad(il_dril d, il_batch b, DrilMa
   }
 }
 
-__global__ __launch_bounds__(256) void k_dril_apply(il_dril d, int nt, int apply, float* __restrict__ out_loss) {
+__global__ __launch_bounds__(256) void k_dril_apply(il_dril d, int nt, int apply, float* __restrict__ out_loss, int64_t* cursor) {
   const int64_t P = dril_layout(d.state_dim, d.action_dim, d.hidden, dril_depth(d)).P;
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e < P) {
@@ -232,6 +233,7 @@ __global__ __launch_bounds__(256) void k_dril_apply(il_dril d, int nt, int apply
     for (int t = 0; t < nt; ++t) s += d.workspace[(size_t)nt * P + t];
     out_loss[0] = s / (float)d.batch;
   }
+  if (e == 0 && cursor) epoch_advance(cursor);   // the last launch of an epoch step
 }
 
 template <int DEPTH>
@@ -279,9 +281,9 @@ static int dril_ensure_lds(const void* fn, size_t bytes) {
   return IL_OK;
 }
 
-extern "C" int il_dril_bc_step(const il_dril* d, const il_batch* expert, const float* mask_in, const float* mask_hidden, const float* mask_hidden2, uint32_t noise_offset,
-                               float* out_loss, uint32_t flags, il_stream_t stream_) {
-  IL_NO_GATHER(expert, "il_dril_bc_step");
+// il_dril_bc_step (ep == NULL, one step) and il_dril_bc_epoch_steps: the same two launches per step
+static int dril_bc_steps(const il_dril* d, const il_batch* expert, const float* mask_in, const float* mask_hidden, const float* mask_hidden2, uint32_t noise_offset,
+                         float* out_loss, uint32_t flags, const il_epoch* ep, int steps, il_stream_t stream_) {
   if (int rc = check_dril(d, expert)) return rc;
   IL_CHECK_ARG(d->grad && d->workspace && d->opt.m && d->opt.v && d->opt.step && expert->weights, "il_dril_bc_step: null optimiser / workspace / weights");
   IL_CHECK_ARG(d->batch == expert->n, "il_dril_bc_step: descriptor batch %d != batch rows %d", d->batch, expert->n);
@@ -292,10 +294,24 @@ extern "C" int il_dril_bc_step(const il_dril* d, const il_batch* expert, const f
   hipStream_t st = (hipStream_t)stream_;
   const int64_t P = dril_layout(d->state_dim, d->action_dim, d->hidden, depth).P;
   const DrilMasks mk = {mask_in, {mask_hidden, mask_hidden2}, noise_offset};
-  { IL_TRACE("k_dril_grad", st); grad<<<nt, 256, lds, st>>>(*d, *expert, mk); }
-  { IL_TRACE("k_dril_apply", st); k_dril_apply<<<(int)((P + 255) / 256), 256, 0, st>>>(*d, nt, (flags & IL_FLAG_GRADS_ONLY) ? 0 : 1, out_loss); }
+  const il_epoch e = ep ? *ep : il_epoch{};
+  for (int s = 0; s < steps; ++s) {
+    { IL_TRACE("k_dril_grad", st); grad<<<nt, 256, lds, st>>>(*d, *expert, mk, e); }
+    { IL_TRACE("k_dril_apply", st); k_dril_apply<<<(int)((P + 255) / 256), 256, 0, st>>>(*d, nt, (flags & IL_FLAG_GRADS_ONLY) ? 0 : 1, out_loss, e.cursor); }
+  }
   IL_CHECK_LAUNCH("il_dril_bc_step");
   return IL_OK;
+}
+extern "C" int il_dril_bc_step(const il_dril* d, const il_batch* expert, const float* mask_in, const float* mask_hidden, const float* mask_hidden2, uint32_t noise_offset,
+                               float* out_loss, uint32_t flags, il_stream_t stream_) {
+  IL_NO_GATHER(expert, "il_dril_bc_step");
+  return dril_bc_steps(d, expert, mask_in, mask_hidden, mask_hidden2, noise_offset, out_loss, flags, nullptr, 1, stream_);
+}
+// behavioural_cloning_update on the dropout policy x steps over a device-resident epoch of expert batches (include/il_hip.h il_epoch; train.py:114-123)
+extern "C" int il_dril_bc_epoch_steps(const il_dril* d, const il_batch* ring, const float* mask_in, const float* mask_hidden, const float* mask_hidden2, uint32_t noise_offset,
+                                      float* out_loss, uint32_t flags, const il_epoch* epoch, int32_t steps, il_stream_t stream_) {
+  IL_CHECK_EPOCH(epoch, ring, steps, "il_dril_bc_epoch_steps");
+  return dril_bc_steps(d, ring, mask_in, mask_hidden, mask_hidden2, noise_offset, out_loss, flags, epoch, steps, stream_);
 }
 
 extern "C" int il_dril_uncertainty(const il_dril* d, const il_batch* batch, const float* mask_in, const float* mask_hidden, const float* mask_hidden2, uint32_t noise_offset,

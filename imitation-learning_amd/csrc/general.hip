@@ -413,7 +413,8 @@ struct GtFwdPass {
   const float* eps; uint64_t seed; const uint32_t* ctr_ptr; uint32_t ctr; int stream_id; const float* absorbing; int ld_abs; int greedy;
   float* a_rows; int ld_a; float* xT; float* epsT; float* logp;
 };
-struct GtFwd { GtFwdPass p[4]; int n, Bp, npass; };
+struct GtFwd { GtFwdPass p[4]; int n, Bp, npass;
+               const int32_t* gather; int64_t gather_cap; il_epoch ep; };   // pass 0's f1 rows through an order table (il_batch.gather), bound to a device-resident epoch (NULL: dense rows)
 
 // The body of a forward pass on one 16-row tile: input rows cat(f1, f2) -> every hidden layer (g_act) -> the output layer; Os[r * 16 + c] = raw output c of row r.
 // Shared by k_gt_fwd and k_act_step_general, so an acting launch runs il_actor_act_general(n = 1)'s arithmetic by construction. LDS: gt_fwd_lds floats.
@@ -421,12 +422,12 @@ struct GtFwd { GtFwdPass p[4]; int n, Bp, npass; };
 // SGPRs across the layers and cost two more SGPR spills.)
 struct GtTile { float* Os; float* part; };
 __device__ __forceinline__ GtTile gt_fwd_tile(float* smem, const GtNet& nn, const float* const& f1, const int& ld1, const int& K1, const float* const& f2, const int& ld2, const int& K2, float* const& X0T, float* const& HT, int Bp, int row0, int nrows,
-                                              bool stamp) {
+                                              bool stamp, const int32_t* gather = nullptr, int64_t gather_cap = 0) {
   const int H = nn.H, in = nn.in, depth = nn.depth, out = nn.out, act = nn.act;
   const int inp = round_up16(in), ldx = inp + 4, ldh = H + 4;
   float* Xs = smem; float* A0 = Xs + 16 * ldx; float* A1 = A0 + 16 * ldh; float* part = A1 + 16 * ldh; float* Os = part + (H >> 4) * 256;
   const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4, tid = threadIdx.x;
-  load_rows_cat(Xs, ldx, inp, f1, ld1, K1, f2, ld2, K2, row0, nrows);
+  load_rows_cat(Xs, ldx, inp, f1, ld1, K1, f2, ld2, K2, row0, nrows, gather, gather_cap);
   __syncthreads();
   IL_STAMP(stamp, 1);
   if (X0T)
@@ -485,7 +486,12 @@ __global__ __launch_bounds__(512) void k_gt_fwd(GtFwd a) {
   const int tid = threadIdx.x;
   const bool stamp = tile_ == 0 && pass_ == 1;
   IL_STAMP(stamp, 0);
-  const GtTile t = gt_fwd_tile(smem, q.net, q.f1, q.ld1, q.K1, q.f2, q.ld2, q.K2, q.X0T, q.HT, Bp, row0, nrows, stamp);
+  const int32_t* gth = nullptr;
+  if (a.gather && pass_ == 0) {   // behavioural cloning over a device-resident epoch: this launch is the step's first - it reads the cursor and leaves k + 1 for the last one
+    gth = a.gather;
+    if (a.ep.cursor) { const int64_t k = a.ep.cursor[0]; gth += (k % a.ep.n_batches) * (int64_t)a.n; if (blockIdx.x == 0 && tid == 0) a.ep.cursor[1] = k + 1; }
+  }
+  const GtTile t = gt_fwd_tile(smem, q.net, q.f1, q.ld1, q.K1, q.f2, q.ld2, q.K2, q.X0T, q.HT, Bp, row0, nrows, stamp, gth, a.gather_cap);
   float* Os = t.Os; float* part = t.part;
   IL_STAMP(stamp, 10);
   if (q.OT)
@@ -533,6 +539,7 @@ struct GtBwd {
   const float* outT; const float* xT; const float* epsT; const float* logp; const float* dx0T; int64_t dx0_ns; float entropy_target; int S; float* alpha_rows; float* out_logp;   // actor head
   float* loss_rows;                                                                                           // behavioural cloning
   il_adam tick;                                                                                              // ticked by (tile 0, net 0): consumed by the k_gt_dw that follows (step == NULL: none)
+  il_epoch ep;                                                                                               // GT_SEED_BC with b.gather: the device-resident epoch b's order table belongs to
 };
 __global__ __launch_bounds__(512) void k_gt_bwd(GtBwd a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -583,12 +590,17 @@ __global__ __launch_bounds__(512) void k_gt_bwd(GtBwd a) {
     } else {   // GT_SEED_BC: d(-mean(w log pi(a | s))) / d(head outputs)
       const int A = out >> 1;
       if (live) {
-        const float wt = a.b.weights[(size_t)row * a.b.ld_weights], up = -wt / (float)n;
+        size_t sr = (size_t)row;   // source row: through the epoch's order table when the batch is the expert ring (rows >= n never read it)
+        if (a.b.gather) {
+          const int64_t s = a.b.gather[(a.ep.cursor ? (a.ep.cursor[0] % a.ep.n_batches) * (int64_t)n : 0) + row];
+          sr = (size_t)(s < 0 ? 0 : (s >= a.b.gather_capacity ? a.b.gather_capacity - 1 : s));
+        }
+        const float wt = a.b.weights[sr * a.b.ld_weights], up = -wt / (float)n;
         float sn = 0.f, sl = 0.f;
         for (int c = 0; c < A; ++c) {
           const float mean = a.outT[(size_t)c * Bp + row], lsr = a.outT[(size_t)(A + c) * Bp + row];
           const float sd = expf(fminf(fmaxf(lsr, -20.f), 2.f));
-          const float av = fminf(fmaxf(a.b.actions[(size_t)row * a.b.ld_actions + c], -1.f + 1e-6f), 1.f - 1e-6f);
+          const float av = fminf(fmaxf(a.b.actions[sr * a.b.ld_actions + c], -1.f + 1e-6f), 1.f - 1e-6f);
           const float x = atanhf(av), df = x - mean, var = sd * sd;
           sn += -(df * df) / (2.f * var) - logf(sd) - LOG_SQRT_2PI;
           sl += 2.f * (LOG_2 - x - softplus_f(-2.f * x));
@@ -680,6 +692,7 @@ struct GtDw {
   // tail (the actor's launch): temperature step (k_g_alpha), target update (k_polyak), Philox counter
   const float* alpha_rows; int n_rows; float* log_alpha; il_adam alpha_opt; float* alpha_grad; uint32_t* noise_counter;
   float* target; const float* polyak_src; int64_t polyak_n; double tau;
+  int64_t* cursor;   // behavioural cloning over a device-resident epoch: this launch is the step's last (il_epoch.cursor; NULL: none)
 };
 __device__ __forceinline__ void gt_dw_tail(const GtDw& a) {   // the workgroups behind the jobs: temperature step + Philox counter (workgroup 0), target update (all)
     const int tb = (int)blockIdx.x - a.n_job_wgs, ntb = (int)gridDim.x - a.n_job_wgs;
@@ -724,6 +737,7 @@ __device__ __forceinline__ void gt_dw_tail(const GtDw& a) {   // the workgroups 
 }
 __global__ __launch_bounds__(256) void k_gt_dw(GtDw a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
+  if (a.cursor && blockIdx.x == 0 && threadIdx.x == 0) epoch_advance(a.cursor);   // (no workgroup of this launch reads cursor[0])
   if ((int)blockIdx.x >= a.n_job_wgs) { gt_dw_tail(a); return; }
   int job = blockIdx.x * 4 + wave;
   if (job >= a.jobs_per_net * a.nets) return;
@@ -1108,10 +1122,11 @@ extern "C" int il_actor_log_prob_general(const float* actor, int32_t S, int32_t 
   return IL_OK;
 }
 // training.py:57-64 behavioural_cloning_update for general shapes (arguments of il_bc_step + depth, activation); out_loss [1] = mean(w * -log pi) or NULL
-extern "C" int il_bc_step_general(float* actor, float* actor_grad, const il_adam* opt, int32_t S, int32_t A, int32_t H, int32_t depth, int32_t activation, const il_batch* b, float* workspace,
-                                  int64_t workspace_floats, float* out_loss, uint32_t flags, il_stream_t stream_) {
+// ep != NULL (tile-engine shapes only): b is the expert ring read through a device-resident epoch's order table (il_bc_epoch_steps_general)
+static int bc_step_general(float* actor, float* actor_grad, const il_adam* opt, int32_t S, int32_t A, int32_t H, int32_t depth, int32_t activation, const il_batch* b, float* workspace,
+                           int64_t workspace_floats, float* out_loss, uint32_t flags, il_stream_t stream_, const il_epoch* ep = nullptr) {
   IL_CHECK_ARG(actor && b && workspace && b->n > 0 && (opt || (flags & IL_FLAG_GRADS_ONLY)), "il_bc_step_general: null argument");
-  IL_NO_GATHER(b, "il_bc_step_general");
+  if (!ep) IL_NO_GATHER(b, "il_bc_step_general");
   const GNet an = {S, H, depth, 2 * A, activation};
   if (int rc = g_check_shape(an, "il_bc_step_general")) return rc;
   const int n = b->n, Bp = g_bp(n);
@@ -1128,14 +1143,17 @@ extern "C" int il_bc_step_general(float* actor, float* actor_grad, const il_adam
     const GtNet net = {actor, S, H, depth, 2 * A, activation, nullptr, nullptr};
     GtFwd f = {}; f.n = n; f.Bp = Bp;
     GtFwdPass& p0 = f.p[0]; p0.net = net; p0.f1 = b->states; p0.ld1 = b->ld_states; p0.K1 = S; p0.X0T = workspace + ws.x; p0.HT = workspace + ws.h; p0.OT = workspace + ws.o;
+    if (ep) { f.gather = b->gather; f.gather_cap = b->gather_capacity; f.ep = *ep; }
     f.npass = 1; { IL_TRACE("k_gt_fwd", st); k_gt_fwd<<<Bp / 16, gt_threads(H), lds_f, st>>>(f); }
     GtBwd g = {}; g.net = net; g.HT = workspace + ws.h; g.dZT = workspace + ws.dz; g.dOT = workspace + ws.dout; g.seed = GT_SEED_BC; g.n = n; g.Bp = Bp; g.b = *b; g.outT = workspace + ws.o; g.loss_rows = workspace + ws.rows;
     if (!grads_only) g.tick = *opt;
+    if (ep) g.ep = *ep;
     g.nets = 1; { IL_TRACE("k_gt_bwd", st); k_gt_bwd<<<Bp / 16, gt_threads(H), lds_b, st>>>(g); }
     if (out_loss) { IL_TRACE("k_g_sum_rows", st); k_g_sum_rows<<<1, 64, 0, st>>>(workspace + ws.rows, n, out_loss); }
     GtDw w = {}; w.nets = 1; w.P = actor; w.G = G; if (opt) w.opt = *opt; w.grads_only = grads_only ? 1 : 0; w.Bp = Bp;
     w.jobs_per_net = gt_dw_layers(w, an, workspace + ws.x, 0, workspace + ws.h, 0, workspace + ws.dz, 0, workspace + ws.dout, 0, nullptr, nullptr, Bp);
     w.n_job_wgs = (w.jobs_per_net + 3) / 4;
+    if (ep) w.cursor = ep->cursor;
     { IL_TRACE("k_gt_dw", st); k_gt_dw<<<w.n_job_wgs, 256, 0, st>>>(w); }
     IL_CHECK_LAUNCH("il_bc_step_general (tile engine)");
     return IL_OK;
@@ -1147,6 +1165,67 @@ extern "C" int il_bc_step_general(float* actor, float* actor_grad, const il_adam
   if (int rc = g_backward(st, an, actor, 0, 1, workspace + ws.x, 0, workspace + ws.h, workspace + ws.dout, workspace + ws.dz, nullptr, G, 0, Bp)) return rc;
   if (!grads_only) { if (int rc = il_adam_step(actor, G, opt, g_numel(S, H, depth, 2 * A), IL_FLAG_TICK, stream_)) return rc; }
   IL_CHECK_LAUNCH("il_bc_step_general");
+  return IL_OK;
+}
+extern "C" int il_bc_step_general(float* actor, float* actor_grad, const il_adam* opt, int32_t S, int32_t A, int32_t H, int32_t depth, int32_t activation, const il_batch* b, float* workspace,
+                                  int64_t workspace_floats, float* out_loss, uint32_t flags, il_stream_t stream_) {
+  return bc_step_general(actor, actor_grad, opt, S, A, H, depth, activation, b, workspace, workspace_floats, out_loss, flags, stream_);
+}
+// ---------------------------------------------------------------------------------------------------------------------------------------------------------------
+// behavioural_cloning_update x steps over a device-resident epoch of expert batches (include/il_hip.h il_epoch; train.py:93-100) for general shapes.
+// Tile-engine shapes (gt_shape_ok, IL_GENERAL_TILES != 0): il_bc_step_general's three launches with the ring in place of the batch - k_gt_fwd gathers the states and
+// binds the step, the GT_SEED_BC prologue of k_gt_bwd reads actions and weights through the gathered row, k_gt_dw (which already reads X0T from the workspace) is the last
+// launch and advances the cursor. Every other shape, selected from the shape alone: k_epoch_stage
+// copies the step's rows - states | actions | weights of ring row order[(k % n_batches) * n + r] - into a dense slab behind il_bc_step_general's workspace, that entry
+// point's own launches run on the slab (so the step is its arithmetic by construction), and a one-workgroup tail advances the cursor.
+// slab: states [n][S], actions [n][A], weights [n]
+// ---------------------------------------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_epoch_stage(il_batch ring, il_epoch ep, int S, int A, float* __restrict__ slab) {
+  epoch_bind(ep, ring, blockIdx.x == 0 && threadIdx.x == 0);
+  const int n = ring.n, row = S + A + 1;
+  float* st = slab; float* ac = st + (size_t)n * S; float* wt = ac + (size_t)n * A;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n * row; i += gridDim.x * blockDim.x) {
+    const int r = i / row, c = i - r * row;
+    const size_t sr = brow(ring, r);
+    if (c < S) st[(size_t)r * S + c] = ring.states[sr * ring.ld_states + c];
+    else if (c < S + A) ac[(size_t)r * A + (c - S)] = ring.actions[sr * ring.ld_actions + (c - S)];
+    else wt[r] = ring.weights[sr * ring.ld_weights];
+  }
+}
+__global__ void k_epoch_tail(int64_t* cursor) { if (blockIdx.x == 0 && threadIdx.x == 0) epoch_advance(cursor); }
+static inline int64_t g_round4(int64_t n) { return (n + 3) & ~(int64_t)3; }
+extern "C" int64_t il_bc_epoch_workspace_floats_general(int32_t S, int32_t A, int32_t H, int32_t depth, int32_t n) {
+  return g_round4(il_actor_workspace_floats_general(S, A, H, depth, n)) + g_round4((int64_t)n * (S + A + 1));
+}
+extern "C" int il_bc_epoch_steps_general(float* actor, float* actor_grad, const il_adam* opt, int32_t S, int32_t A, int32_t H, int32_t depth, int32_t activation, const il_batch* ring,
+                                         float* workspace, int64_t workspace_floats, float* out_loss, uint32_t flags, const il_epoch* epoch, int32_t steps, il_stream_t stream_) {
+  IL_CHECK_EPOCH(epoch, ring, steps, "il_bc_epoch_steps_general");
+  IL_CHECK_ARG(actor && workspace && ring->n > 0 && ring->states && ring->actions && ring->weights && S >= 1 && A >= 1, "il_bc_epoch_steps_general: null argument");
+  const int n = ring->n;
+  IL_CHECK_ARG(opt || (flags & IL_FLAG_GRADS_ONLY), "il_bc_epoch_steps_general: null optimiser");
+  IL_CHECK_ARG(!(flags & IL_FLAG_GRADS_ONLY) || actor_grad, "il_bc_epoch_steps_general: IL_FLAG_GRADS_ONLY needs actor_grad");
+  const GNet an = {S, H, depth, 2 * A, activation};
+  if (int rc = g_check_shape(an, "il_bc_epoch_steps_general")) return rc;   // (everything il_bc_step_general refuses, ahead of the first staging launch)
+  IL_CHECK_ARG(workspace_floats >= il_bc_epoch_workspace_floats_general(S, A, H, depth, n), "il_bc_epoch_steps_general: workspace too small");
+  const int64_t inner = g_round4(il_actor_workspace_floats_general(S, A, H, depth, n));
+  float* slab = workspace + inner;
+  il_batch d = {};
+  d.states = d.next_states = slab; d.ld_states = d.ld_next_states = S;
+  d.actions = slab + (size_t)n * S; d.ld_actions = A;
+  d.weights = d.rewards = d.terminals = d.absorbing = d.actions + (size_t)n * A; d.ld_weights = d.ld_rewards = d.ld_terminals = d.ld_absorbing = 1;
+  d.n = n;
+  hipStream_t st = (hipStream_t)stream_;
+  if (gt_env() && gt_shape_ok(an)) {
+    for (int s = 0; s < steps; ++s)
+      if (int rc = bc_step_general(actor, actor_grad, opt, S, A, H, depth, activation, ring, workspace, inner, out_loss, flags, stream_, epoch)) return rc;
+    return IL_OK;
+  }
+  for (int s = 0; s < steps; ++s) {
+    { IL_TRACE("k_epoch_stage", st); k_epoch_stage<<<ceil_div(n * (S + A + 1), 256), 256, 0, st>>>(*ring, *epoch, S, A, slab); }
+    if (int rc = bc_step_general(actor, actor_grad, opt, S, A, H, depth, activation, &d, workspace, inner, out_loss, flags, stream_)) return rc;   // (refuses before its first launch, i.e. in step 0)
+    { IL_TRACE("k_epoch_tail", st); k_epoch_tail<<<1, 64, 0, st>>>(epoch->cursor); }
+  }
+  IL_CHECK_LAUNCH("il_bc_epoch_steps_general");
   return IL_OK;
 }
 // ---------------------------------------------------------------------------------------------------------------------------------------------------------------

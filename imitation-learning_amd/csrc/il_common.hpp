@@ -70,6 +70,25 @@ __device__ __forceinline__ size_t brow(const il_batch& b, int row) {
   const int64_t s = b.gather[row];
   return (size_t)(s < 0 ? 0 : (s >= b.gather_capacity ? b.gather_capacity - 1 : s));
 }
+// Device-resident expert epochs (il_epoch, include/il_hip.h). A step kernel that is NOT the last launch of its step binds the epoch: k = cursor[0] selects batch k % n_batches
+// of the order table behind b.gather; the step's leader thread (workgroup 0, one lane) leaves k + 1 in cursor[1] for the step's last launch, which stores it into
+// cursor[0] without reading that word (epoch_advance). Returns the step's Philox counter. e.cursor == NULL: no epoch - the per-function entry points, b untouched.
+__device__ __forceinline__ uint32_t epoch_bind(const il_epoch& e, il_batch& b, bool leader) {
+  if (!e.cursor) return 0u;
+  const int64_t k = e.cursor[0];
+  b.gather += (k % e.n_batches) * (int64_t)b.n;
+  if (leader) e.cursor[1] = k + 1;
+  return e.noise_base + (uint32_t)k;
+}
+__device__ __forceinline__ void epoch_advance(int64_t* cursor) { cursor[0] = cursor[1]; }   // one lane of the LAST launch of a step
+// the host-side refusals every *_epoch_steps entry point shares
+#define IL_CHECK_EPOCH(ep, ring, steps, who)                                                                                                          \
+  do {                                                                                                                                                \
+    IL_CHECK_ARG((ep) && (ep)->cursor, who ": null epoch / cursor");                                                                                  \
+    IL_CHECK_ARG((steps) >= 1, who ": steps=%d must be >= 1", (int)(steps));                                                                          \
+    IL_CHECK_ARG((ep)->n_batches >= 1, who ": n_batches=%lld must be >= 1", (long long)(ep)->n_batches);                                              \
+    IL_CHECK_ARG((ring) && (ring)->gather && (ring)->gather_capacity >= 1, who ": the ring needs its order table (il_batch.gather) and gather_capacity >= 1"); \
+  } while (0)
 template <class T>
 __device__ __forceinline__ T* as_global(T* p) { auto g = (__attribute__((address_space(1))) T*)p; asm volatile("" : "+s"(g)); return (T*)g; }
 __device__ __forceinline__ void globalize(il_adam& o) { o.m = as_global(o.m); o.v = as_global(o.v); o.step = as_global(o.step); }

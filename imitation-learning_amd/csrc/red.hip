@@ -46,7 +46,8 @@ __device__ __forceinline__ RedLds red_carve(float* smem, int D, int H, int depth
 }
 
 __device__ __forceinline__ float red_in(const il_batch& b, int S, int r, int k) {
-  return k < S ? b.states[(size_t)r * b.ld_states + k] : b.actions[(size_t)r * b.ld_actions + (k - S)];
+  const size_t sr = brow(b, r);   // (il_batch.gather: the expert ring through an epoch's order table; identity otherwise)
+  return k < S ? b.states[sr * b.ld_states + k] : b.actions[sr * b.ld_actions + (k - S)];
 }
 __device__ __forceinline__ float red_act(float z, int tanh_) { return tanh_ ? tanhf(z) : fmaxf(z, 0.f); }
 __device__ __forceinline__ float red_act_grad(float h, int tanh_) { return tanh_ ? 1.f - h * h : (h > 0.f ? 1.f : 0.f); }   // in terms of the activation's output
@@ -121,7 +122,8 @@ __device__ __forceinline__ void red_forward_tile(const RedLds& l, const il_red& 
 }
 
 template <int DEPTH>
-__global__ __launch_bounds__(256) void k_red_grad(il_red d, il_batch b, RedMasks mk) {
+__global__ __launch_bounds__(256) void k_red_grad(il_red d, il_batch b, RedMasks mk, il_epoch ep) {
+  if (ep.cursor) mk.ctr += epoch_bind(ep, b, blockIdx.x == 0 && threadIdx.x == 0);   // device-resident epoch: this step's rows and Philox counter
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int D = d.state_dim + (d.state_only ? 0 : d.action_dim), H = d.hidden, B = b.n;
   constexpr int depth = DEPTH;
@@ -136,7 +138,7 @@ __global__ __launch_bounds__(256) void k_red_grad(il_red d, il_batch b, RedMasks
   // loss partial and G = dLoss/dpred = 2 w_r E / (B D)   (training.py:72: (w * err^2.mean(1)).mean())
   if (tid < RT) {
     const int r = tid;
-    const float w = (row0 + r < B) ? b.weights[(size_t)(row0 + r) * b.ld_weights] : 0.f;
+    const float w = (row0 + r < B) ? b.weights[brow(b, row0 + r) * b.ld_weights] : 0.f;
     float s = 0.f;
     for (int c = 0; c < D; ++c) { const float e = l.E[r * l.ldx + c]; s = fmaf(e, e, s); }
     rowsum[r] = w * (s / (float)D);
@@ -215,7 +217,7 @@ __global__ __launch_bounds__(256) void k_red_grad(il_red d, il_batch b, RedMasks
   }
 }
 
-__global__ __launch_bounds__(256) void k_red_apply(il_red d, int nt, int apply, float* __restrict__ out_loss) {
+__global__ __launch_bounds__(256) void k_red_apply(il_red d, int nt, int apply, float* __restrict__ out_loss, int64_t* cursor) {
   const int D = d.state_dim + (d.state_only ? 0 : d.action_dim);
   const int64_t P = red_layout(D, d.hidden, red_depth(d)).P;
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -235,6 +237,7 @@ __global__ __launch_bounds__(256) void k_red_apply(il_red d, int nt, int apply, 
     for (int t = 0; t < nt; ++t) s += d.workspace[(size_t)nt * P + t];
     out_loss[0] = s / (float)d.batch;
   }
+  if (e == 0 && cursor) epoch_advance(cursor);   // the last launch of an epoch step
 }
 
 template <int DEPTH>
@@ -271,9 +274,9 @@ static int red_ensure_lds(const void* fn, size_t bytes) {
   return IL_OK;
 }
 
-extern "C" int il_red_step(const il_red* d, const il_batch* expert, const float* mask_in, const float* mask_h1, const float* mask_h2, uint32_t noise_offset, float* out_loss,
-                           uint32_t flags, il_stream_t stream_) {
-  IL_NO_GATHER(expert, "il_red_step");
+// il_red_step (ep == NULL, one step) and il_red_epoch_steps: the same two launches per step
+static int red_steps(const il_red* d, const il_batch* expert, const float* mask_in, const float* mask_h1, const float* mask_h2, uint32_t noise_offset, float* out_loss,
+                     uint32_t flags, const il_epoch* ep, int steps, il_stream_t stream_) {
   if (int rc = check_red(d, expert)) return rc;
   IL_CHECK_ARG(d->grad && d->workspace && d->opt.m && d->opt.v && d->opt.step && expert->weights, "il_red_step: null optimiser / workspace / weights");
   IL_CHECK_ARG(d->batch == expert->n, "il_red_step: descriptor batch %d != batch rows %d", d->batch, expert->n);
@@ -284,10 +287,24 @@ extern "C" int il_red_step(const il_red* d, const il_batch* expert, const float*
   hipStream_t st = (hipStream_t)stream_;
   const int64_t P = red_layout(D, d->hidden, depth).P;
   const RedMasks mk = {mask_in, {mask_h1, mask_h2}, noise_offset, 1};   // target_estimation_update runs in train mode (train.py:115-123 precede :147)
-  { IL_TRACE("k_red_grad", st); grad<<<nt, 256, lds, st>>>(*d, *expert, mk); }
-  { IL_TRACE("k_red_apply", st); k_red_apply<<<(int)((P + 255) / 256), 256, 0, st>>>(*d, nt, (flags & IL_FLAG_GRADS_ONLY) ? 0 : 1, out_loss); }
+  const il_epoch e = ep ? *ep : il_epoch{};
+  for (int s = 0; s < steps; ++s) {
+    { IL_TRACE("k_red_grad", st); grad<<<nt, 256, lds, st>>>(*d, *expert, mk, e); }
+    { IL_TRACE("k_red_apply", st); k_red_apply<<<(int)((P + 255) / 256), 256, 0, st>>>(*d, nt, (flags & IL_FLAG_GRADS_ONLY) ? 0 : 1, out_loss, e.cursor); }
+  }
   IL_CHECK_LAUNCH("il_red_step");
   return IL_OK;
+}
+extern "C" int il_red_step(const il_red* d, const il_batch* expert, const float* mask_in, const float* mask_h1, const float* mask_h2, uint32_t noise_offset, float* out_loss,
+                           uint32_t flags, il_stream_t stream_) {
+  IL_NO_GATHER(expert, "il_red_step");
+  return red_steps(d, expert, mask_in, mask_h1, mask_h2, noise_offset, out_loss, flags, nullptr, 1, stream_);
+}
+// target_estimation_update x steps over a device-resident epoch of expert batches (include/il_hip.h il_epoch; train.py:114-123)
+extern "C" int il_red_epoch_steps(const il_red* d, const il_batch* ring, const float* mask_in, const float* mask_h1, const float* mask_h2, uint32_t noise_offset, float* out_loss,
+                                  uint32_t flags, const il_epoch* epoch, int32_t steps, il_stream_t stream_) {
+  IL_CHECK_EPOCH(epoch, ring, steps, "il_red_epoch_steps");
+  return red_steps(d, ring, mask_in, mask_h1, mask_h2, noise_offset, out_loss, flags, epoch, steps, stream_);
 }
 
 extern "C" int il_red_forward(const il_red* d, const il_batch* batch, int32_t training, const float* mask_in, const float* mask_h1, const float* mask_h2, uint32_t noise_offset,

@@ -2931,7 +2931,8 @@ extern "C" int il_sac_apply_actor_grads(const il_sac* d, il_stream_t stream_) {
 // shared k_dw_adam.  grid = nt
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void k_bc_tile(const float* __restrict__ actor, il_adam opt, int S, int A, int H, il_batch b, float* __restrict__ W,
-                                                 float* __restrict__ loss_part) {
+                                                 float* __restrict__ loss_part, il_epoch ep) {
+  if (ep.cursor) epoch_bind(ep, b, blockIdx.x == 0 && threadIdx.x == 0);   // device-resident epoch: b is the expert ring, this step's rows through the order table
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int B = b.n, tile = blockIdx.x, row0 = tile * IL_TILE_R, tid = threadIdx.x;
   const int Sp = round_up16(S), ldx = Sp + 4, ldh = H + 4, ldz = 20;
@@ -2940,8 +2941,10 @@ __global__ __launch_bounds__(1024) void k_bc_tile(const float* __restrict__ acto
   float* DZ3s = part;  // reused after the head
   const SacWs ws = sac_ws(S, A, H, B);
   const MlpView net = mlp_view(actor, S, H, 2 * A);
-  load_rows_cat(Xs, ldx, Sp, b.states, b.ld_states, S, nullptr, 0, 0, row0, IL_TILE_R);
+  load_rows_cat(Xs, ldx, Sp, b.states, b.ld_states, S, nullptr, 0, 0, row0, IL_TILE_R, b.gather, b.gather_capacity);
   __syncthreads();
+  if (b.gather)   // gathered rows: the layer-1 dW reads s^T [S][B] from the workspace, like the SAC actor's (k_actor_tile)
+    for (int i = tid; i < IL_TILE_R * S; i += blockDim.x) { const int c = i >> 4, r = i & 15; W[ws.a_x0 + (size_t)c * B + row0 + r] = Xs[r * ldx + c]; }
   const int lane = tid & 63, j = lane & 15, g = lane >> 4;
   tile_fwd(Xs, ldx, Sp, net.W1, S, S, H, [&](int c0, f32x4 acc) {
     const int col = c0 + j; const float bb = net.b1[col];
@@ -2961,11 +2964,13 @@ __global__ __launch_bounds__(1024) void k_bc_tile(const float* __restrict__ acto
   __syncthreads();
   tile_fwd_small(H2s, ldh, H, net.W3, H, 2 * A, net.b3, Os, part);
   // head
-  float lp_term = 0.f, dmean = 0.f, dls = 0.f; int hr = 0, hc = 0;
+  float lp_term = 0.f, dmean = 0.f, dls = 0.f, hw = 0.f; int hr = 0, hc = 0;
   const bool head = tid < IL_TILE_R * A;
   if (head) {
     hr = tid / A; hc = tid - hr * A; const int row = row0 + hr;
-    const float a = fminf(fmaxf(b.actions[(size_t)row * b.ld_actions + hc], -1.f + 1e-6f), 1.f - 1e-6f);
+    const size_t srow = brow(b, row);
+    hw = b.weights[srow * b.ld_weights];
+    const float a = fminf(fmaxf(b.actions[srow * b.ld_actions + hc], -1.f + 1e-6f), 1.f - 1e-6f);
     const float x = atanhf(a);
     const float mean = Os[hr * 16 + hc], lsr = Os[hr * 16 + A + hc];
     const float sd = expf(fminf(fmaxf(lsr, -20.f), 2.f));
@@ -2973,7 +2978,7 @@ __global__ __launch_bounds__(1024) void k_bc_tile(const float* __restrict__ acto
     const float nlp = -(df * df) / (2.f * var) - logf(sd) - LOG_SQRT_2PI;
     const float ladj = 2.f * (LOG_2 - x - softplus_f(-2.f * x));
     lp_term = nlp - ladj;
-    const float up = -b.weights[(size_t)row * b.ld_weights] / (float)B;
+    const float up = -hw / (float)B;
     dmean = up * df / var;
     const float dsd = up * (df * df / (var * sd) - 1.f / sd);
     dls = (lsr >= -20.f && lsr <= 2.f) ? dsd * sd : 0.f;
@@ -2982,7 +2987,7 @@ __global__ __launch_bounds__(1024) void k_bc_tile(const float* __restrict__ acto
   for (int i = tid; i < IL_TILE_R * ldz; i += blockDim.x) DZ3s[i] = 0.f;
   __syncthreads();
   if (head) { DZ3s[hr * ldz + hc] = dmean; DZ3s[hr * ldz + A + hc] = dls; }
-  const float lsum = block_sum(head ? -b.weights[(size_t)(row0 + hr) * b.ld_weights] * lp_term : 0.f, red);
+  const float lsum = block_sum(head ? -hw * lp_term : 0.f, red);
   if (tid == 0) { if (loss_part) loss_part[tile] = lsum; if (tile == 0) adam_tick(opt); }
   for (int i = tid; i < IL_TILE_R * 16; i += blockDim.x) W[ws.a_dz3 + (size_t)(i >> 4) * B + row0 + (i & 15)] = DZ3s[(i & 15) * ldz + (i >> 4)];
   float* DZ2s = H1s;  // h1 lives in the workspace copy from here on
@@ -3005,9 +3010,14 @@ __global__ __launch_bounds__(1024) void k_bc_tile(const float* __restrict__ acto
   });
 }
 
-extern "C" int il_bc_step(float* actor, float* actor_grad, const il_adam* opt, int32_t S, int32_t A, int32_t H, const il_batch* b, float* workspace,
-                          int64_t workspace_floats, float* out_loss_partials, uint32_t flags, il_stream_t stream_) {
-  IL_NO_GATHER(b, "il_bc_step");
+__global__ __launch_bounds__(256) void k_dw_adam_tiles_epoch(DwArgs a, int64_t* cursor) {   // k_dw_adam_tiles as the last launch of an epoch step
+  __shared__ __attribute__((aligned(16))) float smem[2 * DWS * DWS_LD];
+  dw_adam_kernel<false>(a, nullptr, smem);
+  if (blockIdx.x == 0 && threadIdx.x == 0) epoch_advance(cursor);
+}
+// il_bc_step (ep == NULL, one step) and il_bc_epoch_steps: the same three launches per step
+static int bc_steps(float* actor, float* actor_grad, const il_adam* opt, int32_t S, int32_t A, int32_t H, const il_batch* b, float* workspace,
+                    int64_t workspace_floats, float* out_loss_partials, uint32_t flags, const il_epoch* ep, int steps, il_stream_t stream_) {
   IL_CHECK_ARG(actor && opt && b && workspace, "il_bc_step: null argument");
   IL_CHECK_ARG(H % 64 == 0 && H >= 64 && H <= 256, "il_bc_step: hidden=%d must be a multiple of 64 in [64,256]", H);
   IL_CHECK_ARG(b->n > 0 && b->n % IL_TILE_R == 0, "il_bc_step: batch=%d must be a positive multiple of %d", b->n, IL_TILE_R);
@@ -3017,22 +3027,37 @@ extern "C" int il_bc_step(float* actor, float* actor_grad, const il_adam* opt, i
   if (workspace_floats < ws.total) return il_set_error(IL_ERR_WORKSPACE, "il_bc_step: workspace too small (%lld < %lld floats)", (long long)workspace_floats, (long long)ws.total);
   hipStream_t st = (hipStream_t)stream_;
   const int nt = b->n / IL_TILE_R;
-  {
-    il_sac tmp = {};  // k_repack only needs the dims, the actor arena and the workspace
-    tmp.state_dim = S; tmp.action_dim = A; tmp.hidden = H; tmp.batch = b->n; tmp.actor = actor; tmp.workspace = workspace;
-    IL_TRACE("k_repack", st); k_repack<<<dim3(repack_blocks(H), 1), 256, 0, st>>>(tmp, 0x1u, nullptr);
-  }
-  { IL_TRACE("k_bc_tile", st); k_bc_tile<<<nt, tile_threads(H), tile_lds_bytes(round_up16(S + A), H), st>>>(actor, *opt, S, A, H, *b, workspace, out_loss_partials); }
+  il_sac tmp = {};  // k_repack only needs the dims, the actor arena and the workspace
+  tmp.state_dim = S; tmp.action_dim = A; tmp.hidden = H; tmp.batch = b->n; tmp.actor = actor; tmp.workspace = workspace;
   DwArgs a = {};
   a.params = actor; a.grads = actor_grad; a.opt = *opt; a.grads_only = (flags & IL_FLAG_GRADS_ONLY) ? 1 : 0;
   a.n_nets = 1; a.in_dim = S; a.hidden = H; a.out_dim = 2 * A; a.batch = b->n;
-  a.x0 = b->states; a.ld_x0 = b->ld_states; a.x0_transposed = 0;
+  if (ep) { a.x0 = workspace + ws.a_x0; a.ld_x0 = 0; a.x0_transposed = 1; }   // gathered rows: s^T as k_bc_tile left it (dw_tile<true> / <false>: the same MFMAs in the same order)
+  else { a.x0 = b->states; a.ld_x0 = b->ld_states; a.x0_transposed = 0; }
   a.h1 = workspace + ws.a_h1; a.h2 = workspace + ws.a_h2; a.dz1 = workspace + ws.a_dz1; a.dz2 = workspace + ws.a_dz2;
   a.dz3 = workspace + ws.a_dz3;
   a.n_dw_blocks = dw_blocks(S, H, 2 * A, 1);
-  { IL_TRACE("k_dw_adam_bc", st); launch_dw_adam(a, a.n_dw_blocks, st); }
+  const il_epoch e = ep ? *ep : il_epoch{};
+  for (int s = 0; s < steps; ++s) {
+    // (k_repack stays in every step: k_dw_adam_tiles does not keep the lane-ordered copies of the actor's W2 in step - DwArgs::pk_f / pk_b are the block form's)
+    { IL_TRACE("k_repack", st); k_repack<<<dim3(repack_blocks(H), 1), 256, 0, st>>>(tmp, 0x1u, nullptr); }
+    { IL_TRACE("k_bc_tile", st); k_bc_tile<<<nt, tile_threads(H), tile_lds_bytes(round_up16(S + A), H), st>>>(actor, *opt, S, A, H, *b, workspace, out_loss_partials, e); }
+    if (ep) { IL_TRACE("k_dw_adam_bc", st); k_dw_adam_tiles_epoch<<<a.n_dw_blocks, 256, 0, st>>>(a, e.cursor); }
+    else { IL_TRACE("k_dw_adam_bc", st); launch_dw_adam(a, a.n_dw_blocks, st); }
+  }
   IL_CHECK_LAUNCH("il_bc_step");
   return IL_OK;
+}
+extern "C" int il_bc_step(float* actor, float* actor_grad, const il_adam* opt, int32_t S, int32_t A, int32_t H, const il_batch* b, float* workspace,
+                          int64_t workspace_floats, float* out_loss_partials, uint32_t flags, il_stream_t stream_) {
+  IL_NO_GATHER(b, "il_bc_step");
+  return bc_steps(actor, actor_grad, opt, S, A, H, b, workspace, workspace_floats, out_loss_partials, flags, nullptr, 1, stream_);
+}
+// behavioural_cloning_update x steps over a device-resident epoch of expert batches (include/il_hip.h il_epoch; train.py:93-100)
+extern "C" int il_bc_epoch_steps(float* actor, float* actor_grad, const il_adam* opt, int32_t S, int32_t A, int32_t H, const il_batch* ring, float* workspace,
+                                 int64_t workspace_floats, float* out_loss_partials, uint32_t flags, const il_epoch* epoch, int32_t steps, il_stream_t stream_) {
+  IL_CHECK_EPOCH(epoch, ring, steps, "il_bc_epoch_steps");
+  return bc_steps(actor, actor_grad, opt, S, A, H, ring, workspace, workspace_floats, out_loss_partials, flags, epoch, steps, stream_);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1303,6 +1303,138 @@ class UpdatePlan:
     self.graph.replay()
 
 
+class PretrainPlan:
+  """The expert-data loops of reference train.py:93-123 - `algorithm=BC` / `bc_pretraining.iterations` (kind 'BC': a SoftActor of any shape), the DRIL policy ensemble
+  (kind 'DRIL': DropoutSoftActor) and the RED predictor (kind 'RED': REDDiscriminator) - as a device-resident epoch (include/il_hip.h il_epoch): the shuffled minibatch
+  order of thousands of iterations sits in a device table, the step kernels read the expert ring through it, and ONE library call enqueues a table half's iterations.
+  Per iteration there is no host-to-device copy, no allocation, no descriptor, no synchronisation and no Python.
+
+  run(iterations) draws `torch.randperm(expert_memory.size, generator=generator)` per epoch, drop-last - the batches of train.py's cycle(DataLoader(shuffle=True,
+  drop_last=True)) - and concatenates the batches of consecutive epochs in a table of two halves of `chunk_batches` batches: a half is filled through a pinned staging
+  buffer with an asynchronous copy, refilled only behind the steps that read it (stream order) while the staging buffer is rewritten only behind its copy (an event).
+  `orders` [K][B] (ring rows) instead of `generator`: batch i of the plan is orders[i % K].
+  The model's own Philox call counter (`_act_calls` of the DRIL ensemble, `_noise_calls` of the RED predictor) advances by `iterations` and the steps draw the masks the
+  per-function calls would have drawn: what follows (set_uncertainty_threshold / set_sigma, per-function steps, another run) sees the loop's state, bit for bit.
+  `loss` is the last step's, in the form the per-function call returns it. Everything runs on the stream that is current when run() is called."""
+
+  def __init__(self, kind: str, model, optimiser, expert_memory: ReplayMemory, batch_size: int, generator=None, *, chunk_batches: int = 4096, orders: Optional[Tensor] = None):
+    from .models import REDDiscriminator
+    if kind not in ('BC', 'DRIL', 'RED'):
+      raise ValueError(f"PretrainPlan: kind {kind!r} is not one of 'BC', 'DRIL', 'RED'")
+    want = dict(BC=SoftActor, DRIL=DropoutSoftActor, RED=REDDiscriminator)[kind]
+    if not isinstance(model, want) or (kind == 'BC' and isinstance(model, DropoutSoftActor)):
+      raise TypeError(f'PretrainPlan({kind!r}): the model must be a {want.__name__} (got {type(model).__name__})')
+    if (generator is None) == (orders is None):
+      raise ValueError('PretrainPlan: exactly one of generator / orders')
+    B, mem, dev = int(batch_size), expert_memory, model.flat.device
+    if mem.size < B or B < 1:
+      raise RuntimeError(f'PretrainPlan: pretraining needs at least one full batch of expert data ({mem.size} rows < batch size {B})')
+    if chunk_batches < 1:
+      raise ValueError('PretrainPlan: chunk_batches must be >= 1')
+    if (mem.state_size, mem.action_size) != (model.state_size, model.action_size):
+      raise ValueError(f'PretrainPlan: the expert memory holds ({mem.state_size}, {mem.action_size})-dimensional rows, the model takes ({model.state_size}, {model.action_size})')
+    self.kind, self.model, self.optimiser, self.memory, self.B, self.chunk = kind, model, optimiser, mem, B, int(chunk_batches)
+    self.generator, self.orders = generator, None
+    if orders is not None:
+      self.orders = orders.to('cpu', torch.int32).reshape(-1, B).contiguous()
+      if self.orders.size(0) < 1: raise ValueError('PretrainPlan: empty orders')
+    self.general = kind == 'BC' and _general_shape(model)
+    # ---- the ring as an il_batch read through the order table (the form UpdatePlan._ring_batches builds for il_sac_update_gather)
+    self.table = torch.zeros(2 * self.chunk, B, dtype=torch.int32, device=dev)
+    self.staging = torch.zeros(self.chunk, B, dtype=torch.int32).pin_memory()
+    self.cursor = torch.zeros(2, dtype=torch.int64, device=dev)
+    self._views = batch_views(mem.ring, mem.state_size, mem.action_size, True)   # (`absorbing` is not read by these kernels; il_batch wants valid pointers)
+    self.ring = batch_desc(self._views)
+    self.ring.n, self.ring.gather, self.ring.gather_capacity = B, self.table.data_ptr(), mem.size
+    self.epoch = _lib.Epoch(self.cursor.data_ptr(), 2 * self.chunk, 0)
+    # ---- descriptors with a workspace of the plan's own (the shared arenas of the per-function calls may be replaced under a raw pointer)
+    L, S, A, H = _lib.lib(), model.state_size, model.action_size, model.hidden
+    if kind == 'BC':
+      if optimiser.grad.numel() < model.flat.numel(): raise ValueError('PretrainPlan: optimiser state arena shorter than its network')
+      floats = L.il_bc_epoch_workspace_floats_general(S, A, H, model.depth, B) if self.general else L.il_sac_workspace_floats(S, A, H, B)
+      self.ws = torch.empty(int(floats), dtype=torch.float32, device=dev)
+      self.od = optimiser.desc()
+      self._loss = torch.zeros(1 if self.general else max(B // 16, 1), dtype=torch.float32, device=dev)
+    else:
+      floats = L.il_dril_workspace_floats(S, A, H, B, model.depth) if kind == 'DRIL' else L.il_red_workspace_floats(model.in_dim, H, B, model.depth)
+      self.ws = torch.empty(int(floats), dtype=torch.float32, device=dev)
+      self.desc = model._desc(B, optimiser)
+      self.desc.workspace = self.ws.data_ptr()
+      self._loss = torch.zeros(1, dtype=torch.float32, device=dev)
+    self.done = 0          # iterations issued = the cursor's value once the stream has drained
+    self.filled = 0        # batches written to the table so far (batch i lives in slot i % (2 * chunk))
+    self._pending = None   # batches of the current epoch that no table half has taken yet
+    self._copied = None    # event behind the last staging -> table copy
+
+  # ---- the order of the batches
+  def _take(self, count: int) -> Tensor:
+    """The next `count` batches [count][B] of ring rows."""
+    if self.orders is not None:
+      K = self.orders.size(0)
+      return self.orders[(torch.arange(self.filled, self.filled + count) % K)]
+    out, have = [], 0
+    while have < count:
+      if self._pending is None or self._pending.size(0) == 0:
+        n = self.memory.size
+        perm = torch.randperm(n, generator=self.generator).to(torch.int32)
+        self._pending = perm[:(n // self.B) * self.B].view(-1, self.B)
+      take = self._pending[:count - have]
+      self._pending = self._pending[take.size(0):]
+      out.append(take); have += take.size(0)
+    return torch.cat(out) if len(out) > 1 else out[0]
+
+  def _fill_half(self):
+    half = (self.filled // self.chunk) % 2
+    batches = self._take(self.chunk)
+    if self._copied is not None: self._copied.synchronize()   # the staging buffer is rewritten only behind its copy
+    self.staging.copy_(batches)
+    # stream order: this copy sits behind every step that read the half's previous contents
+    self.table[half * self.chunk:(half + 1) * self.chunk].copy_(self.staging, non_blocking=True)
+    self._copied = torch.cuda.Event()
+    self._copied.record()
+    self.filled += self.chunk
+
+  def _noise_base(self) -> int:
+    calls = self.model._act_calls if self.kind == 'DRIL' else self.model._noise_calls
+    return (calls + 1 - self.done) & 0xFFFFFFFF   # the step at cursor k = done + j is per-function call number calls + 1 + j
+
+  def _issue(self, steps: int):
+    L, m, st = _lib.lib(), self.model, _lib.stream_ptr()
+    ep = C.byref(self.epoch)
+    if self.kind == 'BC':
+      S, A, H = m.state_size, m.action_size, m.hidden
+      if self.general:
+        from .models import ACTIVATION_IDS
+        _lib.check(L.il_bc_epoch_steps_general(_lib.ptr(m.flat), _lib.ptr(self.optimiser.grad), C.byref(self.od), S, A, H, m.depth, ACTIVATION_IDS[m.activation], C.byref(self.ring),
+                                               _lib.ptr(self.ws), self.ws.numel(), _lib.ptr(self._loss), 0, ep, steps, st))
+      else:
+        _lib.check(L.il_bc_epoch_steps(_lib.ptr(m.flat), _lib.ptr(self.optimiser.grad), C.byref(self.od), S, A, H, C.byref(self.ring), _lib.ptr(self.ws), self.ws.numel(),
+                                       _lib.ptr(self._loss), 0, ep, steps, st))
+      return
+    self.epoch.noise_base = self._noise_base()
+    self.desc.noise_seed = torch.initial_seed() & (2**64 - 1)   # read per call, like the per-function descriptors
+    fn =L.il_dril_bc_epoch_steps if self.kind == 'DRIL' else L.il_red_epoch_steps
+    _lib.check(fn(C.byref(self.desc), C.byref(self.ring), None, None, None, 0, _lib.ptr(self._loss), 0, ep, steps, st))
+    if self.kind == 'DRIL': m._act_calls += steps
+    else: m._noise_calls += steps
+
+  def run(self, iterations: int):
+    """`iterations` more steps, enqueued on the current stream; returns without synchronising."""
+    remaining = int(iterations)
+    while remaining > 0:
+      if self.filled <= self.done: self._fill_half()
+      steps = min(remaining, self.filled - self.done)
+      self._issue(steps)
+      self.done += steps; remaining -= steps
+    return self
+
+  @property
+  def loss(self) -> Tensor:
+    """The last step's loss, as behavioural_cloning_update / target_estimation_update(want_loss=True) return it."""
+    if self.kind == 'BC': return self._loss[0] if self.general else self._loss.sum() / self.B
+    return self._loss
+
+
 class PopulationPlan:
   """N independent learners (seeds / hyper-parameter trials: how the reference is actually used, README.md:96-99, train_all.py) advanced
   by ONE hipGraph replay: every learner's update block is a branch of the graph on its own stream, so their latency-bound kernels

@@ -743,8 +743,47 @@ int il_launcher_submit(void* launcher);
 int il_launcher_wait(void* launcher);
 int64_t il_launcher_pending(void* launcher);
 
+/* ------------------------------------------------------------------------------------------
+ * Device-resident expert epochs (reference train.py:93-123: `algorithm=BC`, `bc_pretraining.iterations`, the DRIL / RED "discriminator" pretraining - loops of
+ * behavioural_cloning_update / target_estimation_update over cycle(DataLoader(expert_memory, shuffle=True, drop_last=True))). The shuffled minibatch order of
+ * many iterations lives on the device as a table of ring rows, the step kernels read their rows straight from the expert ring through it, and ONE call enqueues
+ * `steps` identical step sequences: per iteration no host-to-device copy, no allocation, no descriptor, no synchronisation.
+ *   ring:   an il_batch that describes the expert RING (fields at ring row 0, ld = ring row floats, n = batch rows), as il_sac_update_gather takes it;
+ *           gather = base of a device int32 order table [n_batches][n], gather_capacity = ring rows. Batch row r of the step at cursor k is ring row
+ *           gather[(k % n_batches) * n + r], clamped to [0, gather_capacity) like every il_batch.gather. Rows >= n of a padded tile never read the table.
+ *   noise:  on-chip dropout masks of that step use Philox counter noise_base + (uint32_t)k (+ the call's noise_offset); Adam's step counter ticks as in the sibling.
+ *   cursor: device int64[2], zero-initialised once. [0] = iterations done (monotone across calls); the LAST launch of every step stores k + 1 there (workgroup 0, one
+ *           lane, an ordinary store) and no workgroup of that launch reads [0]. [1] belongs to the library: the first launch of a step, which reads k = [0], leaves
+ *           k + 1 there for the last one. Everything is plain stream order on one stream: no device-side wait, no in-launch hand-off.
+ * Each entry point takes the arguments of its per-function sibling (which keeps refusing il_batch.gather) and runs the sibling's kernels with the epoch bound:
+ * the results are the sibling's bits on the same rows. steps < 1, n_batches < 1, a NULL epoch / cursor / order table are IL_ERR_ARG before any launch.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct il_epoch {
+  int64_t* cursor;     /* device int64[2], zero-initialised: [0] = iterations done (monotone). Advanced by 1 by the LAST launch of every step. */
+  int64_t  n_batches;  /* the order table is a ring of n_batches batches */
+  uint32_t noise_base; /* Philox counter of the step at cursor 0 */
+} il_epoch;
+/* il_bc_step (fused actor shape): k_repack + k_bc_tile (rows through the table; leaves s^T in the workspace for the layer-1 dW) + the dW / AdamW launch, per step.
+ * out_loss_partials [B/16] holds the LAST step's partial sums. */
+int il_bc_epoch_steps(float* actor, float* actor_grad, const il_adam* opt, int32_t state_dim, int32_t action_dim, int32_t hidden, const il_batch* ring, float* workspace,
+                      int64_t workspace_floats, float* out_loss_partials, uint32_t flags, const il_epoch* epoch, int32_t steps, il_stream_t stream);
+/* il_bc_step_general. Tile-engine shapes (hidden a multiple of 16 up to 512, state <= 512, 2A <= 16, IL_GENERAL_TILES != 0): its three launches on the ring - k_gt_fwd
+ * gathers the states, k_gt_bwd's behavioural-cloning prologue reads actions and weights through the gathered row, k_gt_dw advances the cursor. Every other shape (chosen
+ * from the shape, not by a switch): one staging launch copies the step's rows (states | actions | weights) into a dense slab at the end of the workspace, the layer-at-a-time
+ * launches run on the slab, a one-workgroup tail advances the cursor. workspace >= il_bc_epoch_workspace_floats_general floats. out_loss [1]: the last step's. */
+int64_t il_bc_epoch_workspace_floats_general(int32_t state_dim, int32_t action_dim, int32_t hidden, int32_t depth, int32_t n);
+int il_bc_epoch_steps_general(float* actor, float* actor_grad, const il_adam* opt, int32_t state_dim, int32_t action_dim, int32_t hidden, int32_t depth, int32_t activation,
+                              const il_batch* ring, float* workspace, int64_t workspace_floats, float* out_loss, uint32_t flags, const il_epoch* epoch, int32_t steps,
+                              il_stream_t stream);
+/* il_dril_bc_step / il_red_step: k_*_grad reads states, actions (unless state_only) and weights through the table, k_*_apply advances the cursor. Supplied keep-masks
+ * are the same for every step of the call; NULL = on chip, a fresh draw per step. out_loss [1]: the last step's. */
+int il_dril_bc_epoch_steps(const il_dril* d, const il_batch* ring, const float* mask_in, const float* mask_hidden, const float* mask_hidden2, uint32_t noise_offset,
+                           float* out_loss, uint32_t flags, const il_epoch* epoch, int32_t steps, il_stream_t stream);
+int il_red_epoch_steps(const il_red* d, const il_batch* ring, const float* mask_in, const float* mask_h1, const float* mask_h2, uint32_t noise_offset, float* out_loss,
+                       uint32_t flags, const il_epoch* epoch, int32_t steps, il_stream_t stream);
+
 /* sizeof() of the descriptor structs in this build (0 il_batch, 1 il_adam, 2 il_sac, 3 il_disc, 4 il_pwil, 5 il_sample_args, 6 il_red,
- * 7 il_dril, 8 il_disc_shaped, 9 il_disc_deep, 10 il_peer_bucket, 11 il_disc_shaped_deep; -1 otherwise): lets a binding verify its own struct definitions. */
+ * 7 il_dril, 8 il_disc_shaped, 9 il_disc_deep, 10 il_peer_bucket, 11 il_disc_shaped_deep, 12 il_epoch; -1 otherwise): lets a binding verify its own struct definitions. */
 int32_t il_struct_size(int32_t which);
 
 #ifdef __cplusplus

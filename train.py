@@ -35,9 +35,20 @@ def expert_batches(cfg, expert_memory, state_size, action_size, count):
       count -= 1
 
 
+def pretraining_schedule(cfg) -> str:
+  """'plan' (default): the expert-data loops run as a device-resident epoch (il.PretrainPlan: one library call per few thousand iterations). `+pretraining.schedule=per_function`
+  keeps the loop over `expert_batches` below - one gather and one per-function update per iteration - as the reference and for A/B runs; both leave the same bits."""
+  schedule = (cfg.get('pretraining', {}) or {}).get('schedule', 'plan')
+  assert schedule in ('plan', 'per_function')
+  return schedule
+
+
 def pretrain_bc(cfg, actor, expert_memory, state_size, action_size):
-  """cfg.bc_pretraining.iterations steps of il_bc_step (train.py:93-100)."""
+  """cfg.bc_pretraining.iterations steps of behavioural cloning (train.py:93-100)."""
   optimiser = il.AdamW(actor, lr=cfg.bc_pretraining.learning_rate, weight_decay=cfg.bc_pretraining.weight_decay)
+  if pretraining_schedule(cfg) == 'plan':
+    il.PretrainPlan('BC', actor, optimiser, expert_memory, cfg.training.batch_size, torch.Generator().manual_seed(cfg.seed)).run(cfg.bc_pretraining.iterations)
+    return
   for batch in expert_batches(cfg, expert_memory, state_size, action_size, cfg.bc_pretraining.iterations):
     il.behavioural_cloning_update(actor, batch, optimiser)
 
@@ -143,9 +154,12 @@ def train(cfg, file_prefix: str = '') -> float:
       return float(np.mean(normalised))
 
   if cfg.algorithm in ('DRIL', 'RED'):  # train.py:114-134: pretrain the "discriminator" on expert data, then fix its reward threshold / bandwidth
-    for batch in expert_batches(cfg, expert_memory, state_size, action_size, cfg.imitation.pretraining.iterations):
-      if cfg.algorithm == 'DRIL': il.behavioural_cloning_update(discriminator, batch, discriminator_optimiser)
-      else: il.target_estimation_update(discriminator, batch, discriminator_optimiser)
+    if pretraining_schedule(cfg) == 'plan' and cfg.imitation.pretraining.iterations > 0:
+      il.PretrainPlan(cfg.algorithm, discriminator, discriminator_optimiser, expert_memory, B, torch.Generator().manual_seed(cfg.seed)).run(cfg.imitation.pretraining.iterations)
+    else:
+      for batch in expert_batches(cfg, expert_memory, state_size, action_size, cfg.imitation.pretraining.iterations):
+        if cfg.algorithm == 'DRIL': il.behavioural_cloning_update(discriminator, batch, discriminator_optimiser)
+        else: il.target_estimation_update(discriminator, batch, discriminator_optimiser)
     if cfg.algorithm == 'DRIL': discriminator.set_uncertainty_threshold(expert_memory['states'][:expert_memory.size], expert_memory['actions'][:expert_memory.size], cfg.imitation.quantile_cutoff)
     else: discriminator.set_sigma(expert_memory['states'][:B], expert_memory['actions'][:B])
     if cfg.check_time_usage: metrics['pre_training_time'], start_time = time.time() - start_time, time.time()
