@@ -225,6 +225,9 @@ _SIGNATURES = {
     'il_pwil_reset': (C.c_int, [C.POINTER(Pwil), _P]),
     'il_pwil_scratch_floats': (C.c_int64, [C.c_int32, C.c_double]),
     'il_pwil_reward': (C.c_int, [C.POINTER(Pwil), _P, _P, _P, _P]),
+    'il_pwil_couple_supported': (C.c_int32, [C.c_int32, C.c_double]),
+    'il_pwil_act_reward': (C.c_int, [C.POINTER(Pwil), _P, _P, _P]),
+    'il_pwil_relabel_rows': (C.c_int, [C.POINTER(Pwil), _P, C.c_int64, C.c_int64, C.c_int64, _P]),
     'il_dril_numel': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'il_dril_workspace_floats': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'il_dril_bc_step': (C.c_int, [C.POINTER(Dril), C.POINTER(Batch), _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P]),

@@ -17,6 +17,11 @@ Schedules:
             slots + a version word), so the host gets its action in ~15 us and steps the environment WHILE the GPU runs the update;
             the append and the publish ride in the update's stream / hipGraph (UpdatePlan.pre_hooks / post_hooks). The behaviour
             policy lags the learner by one to two updates (what a host-side actor mirror would do).
+
+PWIL (`ActingWorker(..., reward_model=PWILDiscriminator)`): the reward of a transition is the greedy coupling of its (state, action) against the expert atoms
+(models.py:216-249), which the per-function loop computes with a launch and a `.item()` per step. Here every launch that appends is preceded, on the same stream, by ONE
+coupling launch (`il_pwil_act_reward`) that reads the pending transition where the append reads it, leaves the reward in the carry and - at an episode end - sets the
+atom weights back itself: the reward never visits the host, and the caller issues no `reset()`.
 """
 from __future__ import annotations
 
@@ -28,7 +33,7 @@ import torch
 
 from . import _lib
 
-PENDING, WRAP_ABSORBING, GREEDY, NO_ACTION, CARRY_FROM_MAILBOX = 1, 2, 4, 8, 16  # IL_ACT_* (include/il_hip.h)
+PENDING, WRAP_ABSORBING, GREEDY, NO_ACTION, CARRY_FROM_MAILBOX, REWARD_ON_DEVICE = 1, 2, 4, 8, 16, 32  # IL_ACT_* (include/il_hip.h)
 _HEADER = 8
 _SEQ_MOD = 1 << 17  # the commit word (sequence * 64 + flags) travels as fp32: < 2^23
 
@@ -92,7 +97,7 @@ def general_one_launch(actor) -> bool:
 class ActingWorker:
   """One environment worker feeding one `ReplayMemory` from one `SoftActor` (train.py:151-168)."""
 
-  def __init__(self, actor, memory, mirror: bool = False):
+  def __init__(self, actor, memory, mirror: bool = False, reward_model=None):
     assert _lib.on_device(actor.flat) and _lib.on_device(memory.ring), 'ActingWorker needs the actor and the ring on the GPU (there is no CPU path)'
     assert actor.state_size == memory.state_size and actor.action_size == memory.action_size
     self.general = bool(getattr(actor, 'general', False))
@@ -103,6 +108,12 @@ class ActingWorker:
                                 'several launches per step (csrc/general.hip): use the exact or the fused schedule')
     self.actor, self.memory = actor, memory
     self.S, self.A = memory.state_size, memory.action_size
+    self.reward_model = reward_model   # a PWILDiscriminator: its coupling launch precedes every appending launch, and the append stores the reward that launch left in the carry
+    if reward_model is not None:
+      assert hasattr(reward_model, 'require_device_coupling'), 'ActingWorker(reward_model=...): a PWILDiscriminator (the one reward computed per environment step)'
+      assert (reward_model.state_size, reward_model.action_size) == (self.S, self.A) and _lib.on_device(reward_model.expert_atoms)
+      reward_model.require_device_coupling('ActingWorker(reward_model=...)')   # NotImplementedError outside the one-launch coupling's sizes
+    self._reward_flag = REWARD_ON_DEVICE if reward_model is not None else 0
     self._act_box, self._append_box = _Mailbox(self.S, self.A), _Mailbox(self.S, self.A)
     dev = memory.ring.device
     self.carry = torch.zeros(self.S + self.A + 4, dtype=torch.float32, device=dev)
@@ -125,7 +136,8 @@ class ActingWorker:
       self.enqueue_publish()
       torch.cuda.current_stream().synchronize()
 
-  def _launch(self, box: _Mailbox, acts: bool = True, stream=None, snapshot: bool = False):
+  def _launch(self, box: _Mailbox, acts: bool = True, stream=None, snapshot: bool = False, appends: bool = False):
+    """`appends`: the launch may find a pending transition in `box` - with a reward model its coupling launch goes first (library call, fixed pointers: recordable)."""
     a = self.actor
     a._act_calls += int(acts)  # the Philox offset is shared with SoftActor._act, so the two entry points never reuse noise
     key = (id(box), snapshot)
@@ -138,6 +150,9 @@ class ActingWorker:
     _, _, p_actor, p_box, p_carry, p_ring, p_state, p_version, stride = fixed
     L = _lib.lib()   # (looked up per call: UpdatePlan.record_direct walks the hooks with a recording stand-in for the library)
     st = (stream or torch.cuda.current_stream()).cuda_stream
+    if appends and self.reward_model is not None:
+      rc = L.il_pwil_act_reward(C.byref(self.reward_model._desc), p_box, p_carry, st)   # (the descriptor lives with the discriminator, which this worker keeps alive)
+      if rc: _lib.check(rc)
     if self.general:
       rc = L.il_act_step_general(p_actor, self.S, self.A, a.hidden, self._depth, self._activation, p_box, p_carry, p_ring, p_state, self._seed, a._act_calls & 0xFFFFFFFF, p_version, stride,
                                  _lib.ptr(self._workspace), self._workspace.numel(), st)
@@ -190,13 +205,14 @@ class ActingWorker:
 
   def append(self, step, next_obs, reward, terminal: bool, timeout: bool):
     """`memory.append(step, state, action, reward, next_state, terminal, timeout)` for the (state, action) of the last `act`, plus the
-    absorbing wrap when the episode ended by true termination (train.py:157,161). Asynchronous: nothing is waited for."""
+    absorbing wrap when the episode ended by true termination (train.py:157,161). Asynchronous: nothing is waited for.
+    With a reward model the ring's reward is the device's (`reward` is the caller's, e.g. for its train_return), here and in `step` / `post`."""
     assert self.mirror is None, 'with a mirror the act launches run ahead of the appends: use post() + enqueue_append()'
     wrap = bool(self.memory.absorbing and terminal and not timeout)
     box = self._append_box
     if box.word: box.wait(box.word, 'il_act_step(append)')  # normally already echoed: the act in between ran after it on the same stream
-    box.post(self._next_seq(), PENDING | NO_ACTION | (WRAP_ABSORBING if wrap else 0), float(reward), float(terminal), float(timeout), float(step), next_obs=_row(next_obs))
-    self._launch(box, acts=False)
+    box.post(self._next_seq(), PENDING | NO_ACTION | self._reward_flag | (WRAP_ABSORBING if wrap else 0), float(reward), float(terminal), float(timeout), float(step), next_obs=_row(next_obs))
+    self._launch(box, acts=False, appends=True)
     self._mirror_append(bool(terminal), bool(timeout), wrap)
 
   # --- fused schedule
@@ -207,9 +223,9 @@ class ActingWorker:
     wrap = bool(self.memory.absorbing and terminal and not timeout)
     box = self._act_box
     nxt = _row(next_obs)
-    seq = box.post(self._next_seq(), PENDING | (WRAP_ABSORBING if wrap else 0) | (GREEDY if greedy else 0), float(reward), float(terminal), float(timeout), float(step), next_obs=nxt,
-                   obs=nxt if obs is None else _row(obs))
-    self._launch(box)
+    seq = box.post(self._next_seq(), PENDING | self._reward_flag | (WRAP_ABSORBING if wrap else 0) | (GREEDY if greedy else 0), float(reward), float(terminal), float(timeout), float(step),
+                   next_obs=nxt, obs=nxt if obs is None else _row(obs))
+    self._launch(box, appends=True)
     self._mirror_append(bool(terminal), bool(timeout), wrap)
     return self._collect(box, seq)
 
@@ -221,13 +237,13 @@ class ActingWorker:
     box = self._append_box
     if box.word: box.wait(box.word, 'il_act_step(append)', timeout_s=30.0)
     wrap = bool(self.memory.absorbing and terminal and not timeout)
-    box.post(self._next_seq(), PENDING | NO_ACTION | CARRY_FROM_MAILBOX | (WRAP_ABSORBING if wrap else 0), float(reward), float(terminal), float(timeout), float(step), next_obs=_row(next_obs),
+    box.post(self._next_seq(), PENDING | NO_ACTION | CARRY_FROM_MAILBOX | self._reward_flag | (WRAP_ABSORBING if wrap else 0), float(reward), float(terminal), float(timeout), float(step), next_obs=_row(next_obs),
              obs=_row(obs), action=_row(action))
     self._mirror_append(bool(terminal), bool(timeout), wrap)
 
   def enqueue_append(self):
     """Launch the append kernel on the current stream (capturable: every argument is a fixed pointer; what to append is read from the mailbox)."""
-    self._launch(self._append_box, acts=False)
+    self._launch(self._append_box, acts=False, appends=True)
 
   def enqueue_publish(self):
     """Snapshot the actor arena for the act stream; enqueue after anything that changes the actor (capturable)."""

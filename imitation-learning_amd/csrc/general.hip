@@ -1240,7 +1240,7 @@ struct GActStep {
   const float* outT; int Bp;   // commit form only: the head outputs [2A][Bp] that g_forward left in the workspace
 };
 struct GActPost {
-  float commit; unsigned word, flags; bool pending, wrap; long long cursor, cap;
+  float commit; unsigned word, flags; bool pending, wrap, uncoupled; long long cursor, cap;
   const float* m_next; const float* m_obs; float* m_act; float* m_echo;
 };
 // what this launch has to do: the commit word (the LAST thing the host writes), whether its transition is still to be appended (carry[S + A] holds the commit word of the
@@ -1254,6 +1254,8 @@ __device__ __forceinline__ GActPost g_act_post(const GActStep& a) {
   p.cursor = a.ring_state[0]; p.cap = a.ring_state[2];
   p.pending = (p.flags & IL_ACT_PENDING) && __float_as_uint(a.carry[a.S + a.A]) != p.word;
   p.wrap = p.pending && (p.flags & IL_ACT_WRAP_ABSORBING);
+  // (k_act_step) a pending post whose reward il_pwil_act_reward has not computed - carry[S + A + 2] holds another commit word - is left to the pair enqueued behind it
+  p.uncoupled = p.pending && (p.flags & IL_ACT_REWARD_ON_DEVICE) && __float_as_uint(a.carry[a.S + a.A + 2]) != p.word;
   return p;
 }
 // memory.py:40-44 append (+ memory.py:65-68 absorbing wrap) of the pending transition: k_act_step's row, one column per thread per trip
@@ -1265,7 +1267,7 @@ __device__ __forceinline__ void g_act_append(const GActStep& a, const GActPost& 
     float v = 0.f;
     if (c < o_next) v = (p.flags & IL_ACT_CARRY_FROM_MAILBOX) ? (c < S ? p.m_obs[c] : p.m_act[c - S]) : a.carry[c];   // state | action of the transition
     else if (c < o_rew) v = p.wrap ? (c == o_rew - 1 ? 1.f : 0.f) : p.m_next[c - o_next];    // next_state, or the absorbing state (memory.py:67)
-    else if (c == o_rew) v = mail[2];                                                        // reward
+    else if (c == o_rew) v = (p.flags & IL_ACT_REWARD_ON_DEVICE) ? a.carry[o_next + 1] : mail[2];   // reward (posted, or left by il_pwil_act_reward ahead of this launch)
     else if (c == o_rew + 1) v = p.wrap ? 0.f : mail[3];                                     // terminal (cleared by the wrap)
     else if (c == o_rew + 2) v = mail[4];                                                    // timeout
     else if (c == o_rew + 3) v = 1.f;                                                        // weight
@@ -1306,6 +1308,7 @@ __global__ __launch_bounds__(512) void k_act_step_general(GActStep a) {
   if (a.version) actor += (size_t)a.version[0] * a.mirror_stride;   // published snapshot (il_act_publish), selected ONCE: never the arena an update is rewriting
   const int tid = threadIdx.x, S = a.S, A = a.A;
   const GActPost p = g_act_post(a);
+  if (p.uncoupled) return;   // block-uniform: no row, no action, no echo
   g_act_append(a, p);
   if (!(p.flags & IL_ACT_NO_ACTION)) {  // block-uniform
     const GtNet nn = {actor, S, a.H, a.depth, 2 * A, a.act, nullptr, nullptr};
@@ -1326,6 +1329,7 @@ __global__ __launch_bounds__(512) void k_act_step_general(GActStep a) {
 __global__ __launch_bounds__(256) void k_act_commit_general(GActStep a) {
   const int tid = threadIdx.x, S = a.S, A = a.A;
   const GActPost p = g_act_post(a);
+  if (p.uncoupled) return;   // block-uniform: no row, no action, no echo
   g_act_append(a, p);
   if (!(p.flags & IL_ACT_NO_ACTION)) {  // block-uniform
     __syncthreads();   // every carry[] read of the append precedes the writes below

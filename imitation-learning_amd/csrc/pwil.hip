@@ -115,8 +115,9 @@ __device__ __forceinline__ int pw_rank256(unsigned long long key, unsigned long 
   return rank;
 }
 // WT: the candidates leave with sc0 sc1 (write-through) stores - k_pwil_step's arrival ticket then needs no release (an L2 write-back per workgroup), only drained stores
+// tag: travels in the candidates' spare word (k_pwil_couple: the commit word its workgroup selected for; 0 everywhere else)
 template <bool WT>
-__device__ __forceinline__ void pwil_select_block(const il_pwil& d, const float* __restrict__ state, const float* __restrict__ action, int K, PwCand* __restrict__ cand) {
+__device__ __forceinline__ void pwil_select_block(const il_pwil& d, const float* __restrict__ state, const float* __restrict__ action, int K, PwCand* __restrict__ cand, float tag = 0.f) {
   __shared__ float z[512];
   __shared__ unsigned long long sk[4][128];   // each wave's 64 keys in ascending order, padded with the largest key (binary searches over 128 slots need no bounds)
   const int tid = threadIdx.x, N = d.n_atoms, D = d.dim, S = d.state_dim;
@@ -158,7 +159,7 @@ __device__ __forceinline__ void pwil_select_block(const il_pwil& d, const float*
   const int rank = pw_rank256(pw_key(dist, tid), sk);
   IL_TL(0, 2);
   if (rank < K) {
-    PwCand c; c.dist = dist; c.idx = dist < FLT_MAX ? i : INT_MAX; c.w = dist < FLT_MAX ? wi : 0.f; c.pad = 0.f;
+    PwCand c; c.dist = dist; c.idx = dist < FLT_MAX ? i : INT_MAX; c.w = dist < FLT_MAX ? wi : 0.f; c.pad = tag;
     if (WT) {
       const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(cand, 0, 0x7ffffff0, 0x00020000);   // raw buffer, byte offsets
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(pw_u32x4, c), rs, (int)(((size_t)blockIdx.x * K + rank) * sizeof(PwCand)), 0, 17);   // sc0 | sc1
@@ -416,6 +417,68 @@ __global__ __launch_bounds__(PW_CHUNK) void k_pwil_step(il_pwil d, const float* 
   IL_TL(1, 7);
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_pwil_step's coupling for a transition that is already on the device - no state / action / reward pointer comes from the host per step:
+//   acting form  (mail != NULL): the pending transition of an acting-worker post (include/il_hip.h il_act_step). state | action = carry[0 .. S+A), or the mailbox's
+//                observation / action slots under IL_ACT_CARRY_FROM_MAILBOX; the reward goes to carry[S + A + 1], where the append launch that follows on the same stream
+//                picks it up (IL_ACT_REWARD_ON_DEVICE); the episode-end words are the post's terminal / timeout.
+//   relabel form (mail == NULL): one ring row (train.py:135-141). state | action, the reward column and the terminals / timeouts columns are the row's own.
+// Selecting is idempotent; the merge consumes atom weight, so in the acting form it is gated like the append: the last arriver merges only if the post is pending and its
+// commit word is not the one carry[S + A] remembers (a replayed update graph, a launch still queued behind the append that consumed the post). A replayed launch may also
+// run WHILE the host posts again (the host waits for the echo of the previous post only). Every workgroup therefore reads the commit word first, waits for it, selects for
+// the payload it then finds - the host writes the word last, so a workgroup that read a word read that word's payload - and stamps the word into its list's head; lists
+// stamped with different words are not merged. A merge that did happen leaves its commit word in carry[S + A + 2], and under IL_ACT_REWARD_ON_DEVICE an append launch does
+// nothing at all - no row, no echo - for a pending post whose word is not there: a post is appended only with the reward of its own coupling, by the replayed pair if that
+// one coupled it whole, else by the pair the host enqueues behind the post. After the merge of an episode's last transition the same workgroup sets every atom weight back
+// to 1 / N (k_pwil_reset's value): a reset() issued by the host at the episode end would run AHEAD of a coupling that rides in the update's graph. The arrival ticket ends
+// at zero whatever the gate says.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(PW_CHUNK) void k_pwil_couple(il_pwil d, int K, PwCand* __restrict__ cand, unsigned* __restrict__ ticket, const float* mail, float* carry, float* row) {
+  __shared__ unsigned last, go;
+  const int tid = threadIdx.x, S = d.state_dim, A = d.action_dim;
+  const float* state; const float* action; float* out; const float* ends;
+  float commit = 0.f; unsigned word = 0u;
+  if (mail) {   // kernel-uniform
+    commit = mail[0];   // the LAST thing the host writes: it has arrived before anything of its payload is requested
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    word = (unsigned)commit;
+    const int Sp4 = (S + 3) & ~3;
+    const bool posted = (word & IL_ACT_CARRY_FROM_MAILBOX) != 0u;
+    state = posted ? mail + IL_MAIL_HEADER + Sp4 : carry; action = posted ? mail + IL_MAIL_HEADER + 2 * Sp4 : carry + S;
+    out = carry + S + A + 1; ends = mail + 3;
+  } else {
+    state = row; action = row + S; out = row + 2 * S + A; ends = out + 1;
+  }
+  pwil_select_block<true>(d, state, action, K, cand, commit);
+  // k_pwil_step's hand-off: write-through candidates, every wave drains its own, then a RELAXED ticket; only the last arriver acquires
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) {
+    const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last = t == gridDim.x - 1 ? 1u : 0u;
+    if (last) {
+      __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch (stream-ordered behind this one), merged or not
+    }
+  }
+  __syncthreads();
+  if (last) sync_acquire_all();
+  if (!last) return;
+  if (mail) {
+    if (tid == 0) go = ((word & IL_ACT_PENDING) && __float_as_uint(carry[S + A]) != word) ? 1u : 0u;
+    __syncthreads();
+    for (int g = tid; g < (int)gridDim.x; g += PW_CHUNK) if (cand[(size_t)g * K].pad != commit) go = 0u;   // (rank 0 of every chunk is always written)
+    __syncthreads();
+    if (!go) return;   // workgroup-uniform
+  }
+  const bool episode_end = ends[0] != 0.f || ends[1] != 0.f;   // (requested ahead of the merge: the acting form reads it from host memory)
+  pwil_merge_block(d, (int)gridDim.x, K, cand, out);   // ends behind a barrier: wave 0's weight stores precede the reset below
+  if (episode_end) {
+    const float w = (float)(1.0 / (double)d.n_atoms);
+    for (int i = tid; i < d.n_atoms; i += PW_CHUNK) d.weights[i] = w;
+  }
+  if (mail && tid == 0) carry[S + A + 2] = __uint_as_float(word);   // what carry[S + A + 1] is the reward of: the append stores it for this post only
+}
+
 __global__ __launch_bounds__(256) void k_pwil_merge_serial(il_pwil d, int G, int K, const PwCand* __restrict__ cand, float* __restrict__ out) {
   __shared__ PwCand sc[PW_LDS_CAND];
   const int tid = threadIdx.x;
@@ -467,6 +530,44 @@ extern "C" int il_pwil_reward(const il_pwil* d, const float* state, const float*
     IL_TRACE("k_pwil_reward", (hipStream_t)stream_); k_pwil_reward<<<1, 1024, 0, (hipStream_t)stream_>>>(*d, state, action, out_reward);
   }
   IL_CHECK_LAUNCH("il_pwil_reward");
+  return IL_OK;
+}
+
+// the one-launch path of il_pwil_reward (k_pwil_step), which is all k_pwil_couple covers
+static bool pwil_one_launch(int32_t n_atoms, double agent_weight) {
+  const int m = (int)ceil(agent_weight * (double)n_atoms) + 2, G = ceil_div(n_atoms, PW_CHUNK);
+  return n_atoms > 0 && m <= PW_CHUNK && G <= 64 * PW_MAXQ && G * m <= PW_LDS_CAND;
+}
+extern "C" int32_t il_pwil_couple_supported(int32_t n_atoms, double agent_weight) { return pwil_one_launch(n_atoms, agent_weight) ? 1 : 0; }
+static int pwil_couple_check(const il_pwil* d, const char* who) {
+  IL_CHECK_ARG(d && d->atoms && d->weights && d->dists && d->scale && d->offset, "%s: bad arguments", who);
+  IL_CHECK_ARG(d->dim >= 1 && d->dim <= 512 && d->n_atoms > 0, "%s: dim=%d out of range [1,512]", who, d->dim);
+  IL_CHECK_ARG(d->state_dim >= 1 && d->action_dim >= 0 && (d->dim == d->state_dim || d->dim == d->state_dim + d->action_dim), "%s: dim=%d is neither state_dim=%d nor state_dim + action_dim=%d",
+               who, d->dim, d->state_dim, d->state_dim + d->action_dim);
+  if (!pwil_one_launch(d->n_atoms, d->agent_weight))
+    return il_set_error(IL_ERR_UNSUPPORTED, "%s: covers the one-launch coupling only - m = ceil(agent_weight * n_atoms) + 2 <= %d and ceil(n_atoms / %d) * m <= %d (got n_atoms=%d, m=%d, chunks=%d); "
+                        "use il_pwil_reward", who, PW_CHUNK, PW_CHUNK, PW_LDS_CAND, d->n_atoms, pwil_take(d), ceil_div(d->n_atoms, PW_CHUNK));
+  return IL_OK;
+}
+
+extern "C" int il_pwil_act_reward(const il_pwil* d, const float* mailbox, float* carry, il_stream_t stream_) {
+  if (int rc = pwil_couple_check(d, "il_pwil_act_reward")) return rc;
+  IL_CHECK_ARG(mailbox && carry, "il_pwil_act_reward: null mailbox / carry");
+  { IL_TRACE("k_pwil_couple", (hipStream_t)stream_);
+    k_pwil_couple<<<ceil_div(d->n_atoms, PW_CHUNK), PW_CHUNK, 0, (hipStream_t)stream_>>>(*d, pwil_take(d), reinterpret_cast<PwCand*>(d->dists), pwil_ticket(d), mailbox, carry, nullptr); }
+  IL_CHECK_LAUNCH("il_pwil_act_reward");
+  return IL_OK;
+}
+
+extern "C" int il_pwil_relabel_rows(const il_pwil* d, float* ring, int64_t capacity, int64_t first, int64_t count, il_stream_t stream_) {
+  if (int rc = pwil_couple_check(d, "il_pwil_relabel_rows")) return rc;
+  IL_CHECK_ARG(ring && first >= 0 && count >= 0 && first + count <= capacity, "il_pwil_relabel_rows: rows [%lld, %lld) outside a ring of %lld", (long long)first, (long long)(first + count), (long long)capacity);
+  const int64_t row = il_ring_row_floats(d->state_dim, d->action_dim);
+  for (int64_t i = 0; i < count; ++i) {   // one coupling per row, in stream order: row i + 1 meets the weights row i left (or reset)
+    IL_TRACE("k_pwil_couple", (hipStream_t)stream_);
+    k_pwil_couple<<<ceil_div(d->n_atoms, PW_CHUNK), PW_CHUNK, 0, (hipStream_t)stream_>>>(*d, pwil_take(d), reinterpret_cast<PwCand*>(d->dists), pwil_ticket(d), nullptr, nullptr, ring + (first + i) * row);
+  }
+  IL_CHECK_LAUNCH("il_pwil_relabel_rows");
   return IL_OK;
 }
 

@@ -3170,12 +3170,15 @@ __global__ __launch_bounds__(1024) void k_act_step(const float* __restrict__ act
   const long long cursor = ring_state[0], cap = ring_state[2];
   const bool pending = (flags & IL_ACT_PENDING) && __float_as_uint(consumed[0]) != word, wrap = pending && (flags & IL_ACT_WRAP_ABSORBING);
   const int o_next = S + A, o_rew = 2 * S + A;
+  // a reward computed on the device belongs to the post whose commit word il_pwil_act_reward left in carry[S + A + 2]: a pending post it has not coupled (a replayed launch
+  // overtaken by the host's next post) is left alone - no row, no action, no echo - for the coupling + append pair the host enqueues behind that post
+  if (pending && (flags & IL_ACT_REWARD_ON_DEVICE) && __float_as_uint(carry[o_next + 2]) != word) return;   // block-uniform
   if (pending && tid < row) {
     const int c = tid;
     float v = 0.f;
     if (c < o_next) v = (flags & IL_ACT_CARRY_FROM_MAILBOX) ? (c < S ? m_obs[c] : m_act[c - S]) : carry[c];   // state | action of the transition
     else if (c < o_rew) v = wrap ? (c == o_rew - 1 ? 1.f : 0.f) : m_next[c - o_next];    // next_state, or the absorbing state (memory.py:67)
-    else if (c == o_rew) v = mail[2];                                                    // reward
+    else if (c == o_rew) v = (flags & IL_ACT_REWARD_ON_DEVICE) ? carry[o_next + 1] : mail[2];   // reward (posted, or left by il_pwil_act_reward ahead of this launch)
     else if (c == o_rew + 1) v = wrap ? 0.f : mail[3];                                   // terminal (cleared by the wrap)
     else if (c == o_rew + 2) v = mail[4];                                                // timeout
     else if (c == o_rew + 3) v = 1.f;                                                    // weight

@@ -10,7 +10,7 @@ from __future__ import annotations
 import copy
 import ctypes as C
 import os
-from math import sqrt
+from math import ceil, sqrt
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -662,6 +662,23 @@ class PWILDiscriminator(nn.Module):
 
   def compute_reward(self, state: Tensor, action: Tensor) -> float:
     return float(self.compute_reward_async(state, action).item())
+
+  def require_device_coupling(self, who: str):
+    """The device-resident couplings (il_pwil_act_reward, il_pwil_relabel_rows) cover the one-launch path of il_pwil_reward; anything else is refused loudly."""
+    n, aw = self.expert_atoms.size(0), 1 / self.time_horizon - 1e-6
+    if not _lib.lib().il_pwil_couple_supported(n, aw):
+      m = int(ceil(aw * n)) + 2
+      raise NotImplementedError(f'{who}: the device-resident PWIL coupling is one launch per transition, which needs m = ceil(N / T) + 2 <= 256 consumable atoms per step and '
+                                f'ceil(N / 256) * m <= 4096 candidates (got N = {n} atoms, T = {self.time_horizon}: m = {m}, {-(-n // 256)} chunks); use compute_reward per step')
+
+  def relabel_memory(self, memory, first: int = 0, count=None):
+    """train.py:135-141 on the device: rows first .. first + count of `memory` get their coupling reward in row order, and the atom weights are set back after every row
+    whose terminals / timeouts flag is set - `count` launches enqueued by one library call, no host read in between (asynchronous: nothing is waited for)."""
+    self.require_device_coupling('PWILDiscriminator.relabel_memory')
+    assert (memory.state_size, memory.action_size) == (self.state_size, self.action_size) and _lib.on_device(memory.ring)
+    count = memory.size - first if count is None else count
+    assert 0 <= first and 0 <= count and first + count <= memory.size, f'relabel_memory: rows [{first}, {first + count}) outside the {memory.size} stored rows'
+    _lib.check(_lib.lib().il_pwil_relabel_rows(C.byref(self._desc), _lib.ptr(memory.ring), memory.ring.size(0), first, count, _lib.stream_ptr()))
 
 
 class REDDiscriminator(_FlatModule):

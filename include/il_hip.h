@@ -379,7 +379,8 @@ int il_bc_step_general(float* actor, float* actor_grad, const il_adam* opt, int3
  *   device -> host  [8+2Sp, +A)    action;   [8+2Sp+Ap] echo of the commit word, stored last with system-scope release
  *                   (the host spins on it instead of synchronising the stream).
  * carry (device, S+A+4 floats, zero-initialised): state | action of the pending transition written by the previous call, then the
- *   commit word of the last appended transition: a launch that runs again without a new post appends nothing (exactly-once).
+ *   commit word of the last appended transition: a launch that runs again without a new post appends nothing (exactly-once); then
+ *   the reward slot of IL_ACT_REWARD_ON_DEVICE and the commit word it belongs to.
  * ring_state (device int64[3] = cursor, full, capacity) is advanced on the device (by 2 when the wrap is requested). */
 #define IL_MAIL_HEADER 8
 #define IL_ACT_PENDING 1u        /* a transition (carry, mailbox) is waiting to be appended */
@@ -388,6 +389,11 @@ int il_bc_step_general(float* actor, float* actor_grad, const il_adam* opt, int3
 #define IL_ACT_NO_ACTION 8u      /* append only: no policy evaluation, carry left untouched */
 #define IL_ACT_CARRY_FROM_MAILBOX 16u /* the pending transition's state | action come from the mailbox's observation / action slots
                                        * (written back by the host) instead of `carry`: for a worker whose act launches run ahead of its appends */
+#define IL_ACT_REWARD_ON_DEVICE 32u /* the pending transition's reward is carry[S + A + 1], left there by il_pwil_act_reward on the same stream ahead of this launch,
+                                    * instead of mailbox[2] (the last of the six flag bits of the commit word). carry stays S + A + 4 floats: [S + A] the consumed
+                                    * commit word, [S + A + 1] that reward, [S + A + 2] the commit word that reward was computed for, [S + A + 3] unused.
+                                    * A launch that finds a pending post with this flag whose word is NOT in carry[S + A + 2] does nothing at all (no row, no action,
+                                    * no echo): the post is appended by the il_pwil_act_reward + append pair enqueued behind it */
 int32_t il_act_mailbox_floats(int32_t state_dim, int32_t action_dim);
 /* mirror_version != NULL: `actor` is the base of 3 parameter snapshots `mirror_stride` floats apart and *mirror_version selects one
  * (see il_act_publish); NULL: `actor` is the live arena (launch on the stream the updates run on). */
@@ -598,6 +604,28 @@ int64_t il_pwil_scratch_floats(int32_t n_atoms, double agent_weight);
 int il_pwil_reset(const il_pwil* d, il_stream_t stream);
 /* compute_reward for one (state, action); writes the reward (double precision accumulate like the reference's Python floats) to out_reward[0]. */
 int il_pwil_reward(const il_pwil* d, const float* state, const float* action, float* out_reward, il_stream_t stream);
+/* The two entry points below run il_pwil_reward's one-launch coupling (every workgroup selects its chunk's candidates, the last to arrive merges: the same reward and
+ * atom weights, bit for bit) on a transition that is already on the device. They cover that path's sizes - m = ceil(agent_weight * N) + 2 <= 256 and
+ * ceil(N / 256) * m <= 4096, every shipped configuration - and return IL_ERR_UNSUPPORTED, naming the limits, for any other (il_pwil_couple_supported: 1 / 0).
+ * d->state_dim / d->action_dim must be the ring's (also for a state-only discriminator, whose dim is state_dim). */
+int32_t il_pwil_couple_supported(int32_t n_atoms, double agent_weight);
+/* compute_reward for the PENDING transition of an acting-worker post (il_act_step's mailbox and carry), ONE launch, nothing returned to the host:
+ *   state | action = carry[0 .. S+A), or the mailbox's observation / action slots when the post carries IL_ACT_CARRY_FROM_MAILBOX;
+ *   reward -> carry[S + A + 1], which the append of a post that also carries IL_ACT_REWARD_ON_DEVICE stores instead of mailbox[2].
+ * Exactly once: the merge consumes atom weight, so it is gated like the append - it runs only if the commit word has IL_ACT_PENDING and is not the word carry[S + A]
+ * remembers; a launch replayed without a new post (a captured update graph), or one whose workgroups read two different posts (the host posting while it runs), changes
+ * nothing. A merge leaves its commit word in carry[S + A + 2]; the append stores a device reward for that post only (IL_ACT_REWARD_ON_DEVICE), so a replayed pair that
+ * the host's next post overtakes between its two launches neither appends that post with the previous reward nor echoes it.
+ * Episode end: if the post's terminal or timeout word is non-zero, the merging workgroup sets every atom weight back to 1 / N after its merge (what il_pwil_reset
+ * writes) - a host-issued il_pwil_reset would run ahead of a coupling that rides in an update graph; callers on this path issue none.
+ * Ordering contract: enqueue this launch on the stream of, and AHEAD of, the il_act_step / il_act_step_general launch that appends the same post. That launch's echo is
+ * what hands the mailbox back to the host, so the mailbox words read here cannot change under a launch that was enqueued for them; and it is the launch that moves
+ * carry[S + A], so this one always sees the post as pending. */
+int il_pwil_act_reward(const il_pwil* d, const float* mailbox, float* carry, il_stream_t stream);
+/* train.py:135-141 as one call: `count` coupling launches on `stream`, launch i reading state | action from ring row first + i (rows of
+ * il_ring_row_floats(state_dim, action_dim) floats), writing the reward into that row's reward column and - when the row's terminals or timeouts column is non-zero -
+ * setting the weights back to 1 / N after its merge. No host read and no synchronisation between rows. 0 <= first, first + count <= capacity; count = 0 launches nothing. */
+int il_pwil_relabel_rows(const il_pwil* d, float* ring, int64_t capacity, int64_t first, int64_t count, il_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * RED (reference models.py:252-284 REDDiscriminator, training.py:68-75 target_estimation_update).

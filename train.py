@@ -5,6 +5,9 @@ Drives the loop of reference train.py:26-243 (act -> store -> [update block] -> 
 the update block (train.py:171-203) is `UpdatePlan` (one captured hipGraph replay per step, every algorithm) or the per-function HIP entry
 points (GAIL variants with per-update host inputs, batch sizes that are not a multiple of 16).  Hydra is replaced by `imitation_learning_amd.config.compose`
 (same keys, same precedence).  Supported on the HIP path: SAC, GAIL (BCE loss), GMMIL, PWIL, AdRIL (and SQIL via update_freq=0), RED, DRIL, BC - every algorithm= of the reference.
+Acting goes through `il.ActingWorker` for every algorithm (`+acting.schedule=exact|fused|overlap`, default exact; `per_function` keeps the reference's call sequence). PWIL's
+reward is computed on the device in front of each append and its expert relabel (mix_expert_data != none) is one library call; `+pretraining.schedule=per_function` keeps
+the row-by-row loop.
 """
 import os
 import sys
@@ -171,7 +174,14 @@ def train(cfg, file_prefix: str = '') -> float:
     if cfg.algorithm == 'RED': discriminator.sigma_1, = parallel.broadcast_scalars([discriminator.sigma_1])
 
   if cfg.algorithm == 'PWIL' and cfg.imitation.mix_expert_data != 'none':  # train.py:135-141
-    for i in range(expert_memory.size):
+    relabelled = False
+    if pretraining_schedule(cfg) == 'plan':   # one library call: a coupling launch per row, the weights set back on the device after every trajectory's last row
+      try:
+        discriminator.relabel_memory(expert_memory)
+        relabelled = True
+      except NotImplementedError as e:   # an atom set outside the one-launch coupling's sizes: the loop below
+        print(f'[train] {e}; relabelling the expert memory row by row', file=sys.stderr)
+    for i in range(0 if relabelled else expert_memory.size):   # `+pretraining.schedule=per_function`: the reference's loop, a host round trip per row (A/B runs; the same bits)
       tr = expert_memory[i]
       expert_memory.rewards[i] = discriminator.compute_reward(tr['states'].unsqueeze(0), tr['actions'].unsqueeze(0))
       if tr['terminals'] or tr['timeouts']: discriminator.reset()
@@ -197,15 +207,16 @@ def train(cfg, file_prefix: str = '') -> float:
       raise NotImplementedError('distributed.world_size > 1 needs the captured update plan (a GAIL variant with per-update host inputs, or a batch size that is not a multiple of 16, has no data-parallel path)')
     runner = parallel.DataParallelUpdate(plan)   # grads-only kernels -> all-reduce(mean) of one flat bucket per sync point -> apply kernels
 
-  # acting (train.py:151-168): il_act_step through a pinned mailbox; PWIL computes its reward per step on the device and keeps the per-function path
+  # acting (train.py:151-168): il_act_step through a pinned mailbox. PWIL's per-step reward (models.py:216-249) is one more launch in front of the append, which stores it
+  # from the device (ActingWorker(reward_model=...)): no compute_reward, and no reset() at episode ends - the coupling kernel sets the atom weights back itself
   schedule = (cfg.get('acting', {}) or {}).get('schedule', 'exact')  # `+acting.schedule=fused|overlap`: see imitation_learning_amd/acting.py (behaviour policy lags 1-2 updates)
   assert schedule in ('exact', 'fused', 'overlap', 'per_function')
   # general actor shapes (csrc/general.hip) take the same worker: one launch per step where the tile engine applies, else the layer-at-a-time launches + a commit kernel
   worker = None
-  if cfg.algorithm != 'PWIL' and schedule != 'per_function':
+  if schedule != 'per_function':
     try:
-      worker = il.ActingWorker(actor, memory, mirror=schedule == 'overlap')
-    except NotImplementedError as e:   # overlap with an actor outside the one-launch shapes: the per-function path, as before the worker covered general shapes
+      worker = il.ActingWorker(actor, memory, mirror=schedule == 'overlap', reward_model=discriminator if cfg.algorithm == 'PWIL' else None)
+    except NotImplementedError as e:   # overlap with an actor outside the one-launch shapes, PWIL atoms outside the one-launch coupling: the per-function path
       print(f'[train] +acting.schedule={schedule}: {e}; acting through the per-function path', file=sys.stderr)
   if worker is None: schedule = 'per_function'
   if schedule == 'overlap' and world > 1:
@@ -245,7 +256,7 @@ def train(cfg, file_prefix: str = '') -> float:
           worker.enqueue_append()   # otherwise the update graph carries it
     train_return += reward
     if terminal:
-      if cfg.algorithm == 'PWIL': discriminator.reset()
+      if cfg.algorithm == 'PWIL' and schedule == 'per_function': discriminator.reset()   # (through the worker the coupling launch of the episode's last transition has done it)
       metrics['train_steps'].append(step); metrics['train_returns'].append([train_return])
       t, train_return = 0, 0
       state = env.reset() if schedule == 'per_function' else following
