@@ -14,6 +14,7 @@
 #include "il_common.hpp"
 #include "mlp_tile.hpp"
 #include "dw_block.hpp"
+#include "act_mail.hpp"
 
 enum { G_ACT_NONE = -1, G_ACT_RELU = 0, G_ACT_TANH = 1, G_ACT_SIGMOID = 2 };
 
@@ -186,15 +187,6 @@ __global__ __launch_bounds__(256) void k_g_pack_sac(GPackSac a) {
 }
 
 // ---- per-row pieces ---------------------------------------------------------------------------------------------------------------------------------------------
-// models.py:90-94 + torch.distributions: the tanh-Gaussian head of one row (op order of oracle/nets.py tanh_gaussian_logp)
-__device__ __forceinline__ void g_head(float mean, float ls_raw, float eps, float& x, float& a, float& nlp, float& ladj) {
-  const float sd = expf(fminf(fmaxf(ls_raw, -20.f), 2.f));
-  x = __fadd_rn(__fmul_rn(eps, sd), mean);
-  a = tanhf(x);
-  const float d = __fsub_rn(x, mean);
-  nlp = -(d * d) / (2.f * (sd * sd)) - logf(sd) - LOG_SQRT_2PI;
-  ladj = 2.f * (LOG_2 - x - softplus_f(-2.f * x));
-}
 struct GSample {
   const float* outT; int Bp, n, A;                       // actor output [2A][Bp]
   const float* eps; uint64_t seed; const uint32_t* ctr_ptr; uint32_t ctr; int stream_id;   // eps [n][A] or Philox(seed, ctr_ptr ? *ctr_ptr : ctr, stream_id)
@@ -218,7 +210,7 @@ __global__ __launch_bounds__(256) void k_g_sample(GSample a) {
     if (a.greedy) { act = tanhf(mean); x = mean; nlp = 0.f; ladj = 0.f; }
     else {
       e = a.eps ? a.eps[(size_t)row * a.A + c] : philox_normal(a.seed, ctr, a.stream_id, (uint32_t)(row * a.A + c));
-      g_head(mean, lsr, e, x, act, nlp, ladj);
+      head_sample(mean, lsr, e, x, act, nlp, ladj);
     }
     sn += nlp; sl += ladj;
     if (a.aT) a.aT[(size_t)c * a.Bp + row] = m * act;
@@ -509,7 +501,7 @@ __global__ __launch_bounds__(512) void k_gt_fwd(GtFwd a) {
         if (q.greedy) { av = tanhf(mean); x = mean; nlp = 0.f; ladj = 0.f; }
         else {
           e = q.eps ? q.eps[(size_t)row * A + c] : philox_normal(q.seed, ctr, q.stream_id, (uint32_t)(row * A + c));
-          g_head(mean, lsr, e, x, av, nlp, ladj);
+          head_sample(mean, lsr, e, x, av, nlp, ladj);
         }
         nl[r * 16 + c] = nlp; la[r * 16 + c] = ladj;
         if (q.a_rows) q.a_rows[(size_t)row * q.ld_a + c] = m * av;
@@ -1230,7 +1222,7 @@ extern "C" int il_bc_epoch_steps_general(float* actor, float* actor_grad, const 
 }
 // ---------------------------------------------------------------------------------------------------------------------------------------------------------------
 // One environment step of the acting worker (train.py:151-168) for general actor shapes (models.py:48-69, 90-94): il_act_step's contract - mailbox, IL_ACT_* flags, carry,
-// exactly-once append by commit word, ring_state, mirror selection (include/il_hip.h) - with the append, the carry copy and the mailbox reads STRIDED over the workgroup:
+// exactly-once append by commit word, ring_state, mirror selection (include/il_hip.h; act_mail.hpp) - with the carry copy and the mailbox reads STRIDED over the workgroup:
 // a ring row is 2S + A + 5 floats (up to ~1,040 at S = 512) against 256 - 512 threads, where k_act_step relies on row <= threads and 64 + S <= threads.
 // ---------------------------------------------------------------------------------------------------------------------------------------------------------------
 struct GActStep {
@@ -1239,65 +1231,6 @@ struct GActStep {
   uint64_t seed; uint32_t offset; const int* version; long long mirror_stride;
   const float* outT; int Bp;   // commit form only: the head outputs [2A][Bp] that g_forward left in the workspace
 };
-struct GActPost {
-  float commit; unsigned word, flags; bool pending, wrap, uncoupled; long long cursor, cap;
-  const float* m_next; const float* m_obs; float* m_act; float* m_echo;
-};
-// what this launch has to do: the commit word (the LAST thing the host writes), whether its transition is still to be appended (carry[S + A] holds the commit word of the
-// last appended one), and the cursor - every thread reads them here, before anything below is written
-__device__ __forceinline__ GActPost g_act_post(const GActStep& a) {
-  GActPost p;
-  const int Sp4 = (a.S + 3) & ~3, Ap4 = (a.A + 3) & ~3;
-  p.m_next = a.mail + IL_MAIL_HEADER; p.m_obs = p.m_next + Sp4; p.m_act = a.mail + IL_MAIL_HEADER + 2 * Sp4; p.m_echo = p.m_act + Ap4;
-  p.commit = a.mail[0];
-  p.word = (unsigned)p.commit; p.flags = p.word & 63u;
-  p.cursor = a.ring_state[0]; p.cap = a.ring_state[2];
-  p.pending = (p.flags & IL_ACT_PENDING) && __float_as_uint(a.carry[a.S + a.A]) != p.word;
-  p.wrap = p.pending && (p.flags & IL_ACT_WRAP_ABSORBING);
-  // (k_act_step) a pending post whose reward il_pwil_act_reward has not computed - carry[S + A + 2] holds another commit word - is left to the pair enqueued behind it
-  p.uncoupled = p.pending && (p.flags & IL_ACT_REWARD_ON_DEVICE) && __float_as_uint(a.carry[a.S + a.A + 2]) != p.word;
-  return p;
-}
-// memory.py:40-44 append (+ memory.py:65-68 absorbing wrap) of the pending transition: k_act_step's row, one column per thread per trip
-__device__ __forceinline__ void g_act_append(const GActStep& a, const GActPost& p) {
-  if (!p.pending) return;
-  const int S = a.S, A = a.A, row = a.row, o_next = S + A, o_rew = 2 * S + A;
-  const float* mail = a.mail;
-  for (int c = threadIdx.x; c < row; c += blockDim.x) {
-    float v = 0.f;
-    if (c < o_next) v = (p.flags & IL_ACT_CARRY_FROM_MAILBOX) ? (c < S ? p.m_obs[c] : p.m_act[c - S]) : a.carry[c];   // state | action of the transition
-    else if (c < o_rew) v = p.wrap ? (c == o_rew - 1 ? 1.f : 0.f) : p.m_next[c - o_next];    // next_state, or the absorbing state (memory.py:67)
-    else if (c == o_rew) v = (p.flags & IL_ACT_REWARD_ON_DEVICE) ? a.carry[o_next + 1] : mail[2];   // reward (posted, or left by il_pwil_act_reward ahead of this launch)
-    else if (c == o_rew + 1) v = p.wrap ? 0.f : mail[3];                                     // terminal (cleared by the wrap)
-    else if (c == o_rew + 2) v = mail[4];                                                    // timeout
-    else if (c == o_rew + 3) v = 1.f;                                                        // weight
-    else if (c == o_rew + 4) v = mail[5];                                                    // step
-    a.ring[p.cursor * row + c] = v;
-    if (p.wrap) {  // absorbing -> absorbing row (memory.py:68)
-      float w = 0.f;
-      if (c < S) w = (c == S - 1) ? 1.f : 0.f;
-      else if (c >= o_next && c < o_rew) w = (c == o_rew - 1) ? 1.f : 0.f;
-      else if (c == o_rew + 3) w = 1.f;
-      else if (c == o_rew + 4) w = mail[5];
-      a.ring[((p.cursor + 1) % p.cap) * row + c] = w;
-    }
-  }
-}
-// the cursor, the `full` flag and the consumed commit word move only here, by one thread behind the launch's LAST barrier: an append-only launch (IL_ACT_NO_ACTION) has no
-// other barrier between the waves' loads of ring_state[0] / carry[S + A] in g_act_post and these stores (the race the emulator found in k_act_step). Then the echo.
-__device__ __forceinline__ void g_act_commit(const GActStep& a, const GActPost& p) {
-  __threadfence_system();
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (p.pending) {
-      const long long adv = p.wrap ? 2 : 1, nc = p.cursor + adv;
-      a.ring_state[0] = nc % p.cap;
-      if (nc >= p.cap) a.ring_state[1] = 1;
-      a.carry[a.S + a.A] = __uint_as_float(p.word);
-    }
-    __hip_atomic_store(p.m_echo, p.commit, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-}
 
 // Tile-engine shapes (gt_shape_ok): the whole step in ONE launch of one workgroup of gt_threads(H) threads. The actor runs as k_gt_fwd runs a tile with one valid row
 // (gt_fwd_tile, weights read directly), so the action is bit-identical to il_actor_act_general(n = 1) at the same Philox offset. The head keeps its values in registers:
@@ -1307,42 +1240,42 @@ __global__ __launch_bounds__(512) void k_act_step_general(GActStep a) {
   const float* actor = a.actor;
   if (a.version) actor += (size_t)a.version[0] * a.mirror_stride;   // published snapshot (il_act_publish), selected ONCE: never the arena an update is rewriting
   const int tid = threadIdx.x, S = a.S, A = a.A;
-  const GActPost p = g_act_post(a);
+  const ActPost p = act_post(a.mail, a.carry, a.ring_state, S, A);
   if (p.uncoupled) return;   // block-uniform: no row, no action, no echo
-  g_act_append(a, p);
+  act_append(p, a.carry, a.ring, a.row, S, A);
   if (!(p.flags & IL_ACT_NO_ACTION)) {  // block-uniform
     const GtNet nn = {actor, S, a.H, a.depth, 2 * A, a.act, nullptr, nullptr};
-    const GtTile t = gt_fwd_tile(smem, nn, p.m_obs, (S + 3) & ~3, S, nullptr, 0, 0, nullptr, nullptr, 16, 0, 1, false);   // barriers inside: every carry[] read above precedes the writes below
+    const GtTile t = gt_fwd_tile(smem, nn, p.m.obs(), p.m.ld, S, nullptr, 0, 0, nullptr, nullptr, 16, 0, 1, false);   // barriers inside: every carry[] read above precedes the writes below
     if (tid < A) {   // row 0 of k_gt_fwd's head: Philox index row * A + c = c
       const float mean = t.Os[tid], lsr = t.Os[A + tid];
       float x, av, nlp, ladj;
       if (p.flags & IL_ACT_GREEDY) av = tanhf(mean);
-      else g_head(mean, lsr, philox_normal(a.seed, a.offset, IL_STREAM_ACT, (uint32_t)tid), x, av, nlp, ladj);
-      p.m_act[tid] = av; a.carry[S + tid] = av;
+      else head_sample(mean, lsr, philox_normal(a.seed, a.offset, IL_STREAM_ACT, (uint32_t)tid), x, av, nlp, ladj);
+      p.m.act()[tid] = av; a.carry[S + tid] = av;
     }
-    for (int c = tid; c < S; c += blockDim.x) a.carry[c] = p.m_obs[c];
+    for (int c = tid; c < S; c += blockDim.x) a.carry[c] = p.m.obs()[c];
   }
-  g_act_commit(a, p);
+  act_commit(p, a.carry, a.ring_state, S, A);
 }
 // Every other shape g_check_shape admits: the commit that follows the layer-at-a-time forward (k_g_pack from the mailbox's observation, k_g_linear per layer) of the same
 // step - the append, k_g_sample's head for row 0 from the workspace, the carry and the echo.
 __global__ __launch_bounds__(256) void k_act_commit_general(GActStep a) {
   const int tid = threadIdx.x, S = a.S, A = a.A;
-  const GActPost p = g_act_post(a);
+  const ActPost p = act_post(a.mail, a.carry, a.ring_state, S, A);
   if (p.uncoupled) return;   // block-uniform: no row, no action, no echo
-  g_act_append(a, p);
+  act_append(p, a.carry, a.ring, a.row, S, A);
   if (!(p.flags & IL_ACT_NO_ACTION)) {  // block-uniform
     __syncthreads();   // every carry[] read of the append precedes the writes below
     for (int c = tid; c < A; c += blockDim.x) {
       const float mean = a.outT[(size_t)c * a.Bp], lsr = a.outT[(size_t)(A + c) * a.Bp];
       float x, av, nlp, ladj;
       if (p.flags & IL_ACT_GREEDY) av = tanhf(mean);
-      else g_head(mean, lsr, philox_normal(a.seed, a.offset, IL_STREAM_ACT, (uint32_t)c), x, av, nlp, ladj);
-      p.m_act[c] = av; a.carry[S + c] = av;
+      else head_sample(mean, lsr, philox_normal(a.seed, a.offset, IL_STREAM_ACT, (uint32_t)c), x, av, nlp, ladj);
+      p.m.act()[c] = av; a.carry[S + c] = av;
     }
-    for (int c = tid; c < S; c += blockDim.x) a.carry[c] = p.m_obs[c];
+    for (int c = tid; c < S; c += blockDim.x) a.carry[c] = p.m.obs()[c];
   }
-  g_act_commit(a, p);
+  act_commit(p, a.carry, a.ring_state, S, A);
 }
 
 // train.py:151-168 per environment step - `actor(state).sample()` (models.py:48-69 any depth / activation, models.py:90-94 the tanh-Gaussian sample), memory.append and
@@ -1372,7 +1305,8 @@ extern "C" int il_act_step_general(const float* actor, int32_t S, int32_t A, int
                "action_dim=%d%s): the layer-at-a-time form reads the parameters in several launches", S, H, A, gt_env() ? "" : ", IL_GENERAL_TILES=0");
   const int Bp = 16;
   const GActWs ws = g_act_ws(S, A, H, depth, Bp);
-  g_pack(st, mailbox + IL_MAIL_HEADER + ((S + 3) & ~3), (S + 3) & ~3, S, nullptr, 0, 0, 1, Bp, workspace + ws.x);   // (an append-only post runs the forward too: what a launch does is decided on the device, from the commit word)
+  const ActMail<float> m = act_mail(mailbox, S, A);
+  g_pack(st, m.obs(), m.ld, S, nullptr, 0, 0, 1, Bp, workspace + ws.x);   // (an append-only post runs the forward too: what a launch does is decided on the device, from the commit word)
   if (int rc = g_forward(st, an, actor, 0, 1, workspace + ws.x, 0, workspace + ws.h, workspace + ws.o, Bp)) return rc;
   a.outT = workspace + ws.o; a.Bp = Bp;
   { IL_TRACE("k_act_commit_general", st); k_act_commit_general<<<1, 256, 0, st>>>(a); }

@@ -394,6 +394,15 @@ __device__ __forceinline__ void ov_done(long long* sync, int stage) {
 #define LOG_2 0.69314718055994530942f
 __device__ __forceinline__ float softplus_f(float z) { return z > 20.f ? z : log1pf(expf(z)); }
 __device__ __forceinline__ float sigmoid_f(float z) { return 1.f / (1.f + expf(-z)); }
+// models.py:90-94 + torch.distributions: the tanh-Gaussian head for one (row, action component); op order of oracle/nets.py tanh_gaussian_logp
+__device__ __forceinline__ void head_sample(float mean, float ls_raw, float eps, float& x, float& a, float& nlp, float& ladj) {
+  const float sd = expf(fminf(fmaxf(ls_raw, -20.f), 2.f));
+  x = __fadd_rn(__fmul_rn(eps, sd), mean);
+  a = tanhf(x);
+  const float d = __fsub_rn(x, mean);
+  nlp = -(d * d) / (2.f * (sd * sd)) - logf(sd) - LOG_SQRT_2PI;
+  ladj = 2.f * (LOG_2 - x - softplus_f(-2.f * x));
+}
 
 // Developer-only phase timing (build with -DIL_PHASE_STAMPS): thread 0 of one chosen block stores s_memtime at phase boundaries.
 #ifdef IL_PHASE_STAMPS

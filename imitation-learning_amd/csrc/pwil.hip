@@ -10,6 +10,7 @@
 #include <limits.h>
 
 #include "il_common.hpp"
+#include "act_mail.hpp"
 
 __global__ __launch_bounds__(1024) void k_pwil_reset(il_pwil d, unsigned* ticket) {
   const float w = (float)(1.0 / (double)d.n_atoms);
@@ -392,27 +393,32 @@ __global__ __launch_bounds__(256) void k_pwil_merge(il_pwil d, int G, int K, con
   pwil_merge_block(d, G, K, cand, out);
 }
 
-// One launch per environment step: every workgroup selects its chunk's candidates, takes a ticket, and the LAST one to arrive runs the merge (nobody waits: no
-// co-residency requirement). A step was two launches of ~5 us of work each; at 19 us per step the launches themselves were what was left.
-__global__ __launch_bounds__(PW_CHUNK) void k_pwil_step(il_pwil d, const float* __restrict__ state, const float* __restrict__ action, int K, PwCand* __restrict__ cand,
-                                                        unsigned* __restrict__ ticket, float* __restrict__ out) {
+// The arrival hand-off of the one-launch kernels below: every workgroup calls it behind its candidate stores; true in the LAST workgroup to arrive, which may then read
+// every list. The candidates left with write-through stores: once every wave has drained its own (acknowledged by the memory side) and the workgroup has met, a RELAXED
+// ticket is enough - no release, i.e. no write-back of the XCD's L2 per workgroup; only the last arriver pays an acquire (an invalidate) before it reads the lists.
+__device__ __forceinline__ bool pwil_arrive_last(unsigned* __restrict__ ticket) {
   __shared__ unsigned last;
-  pwil_select_block<true>(d, state, action, K, cand);
-  // The candidates left with write-through stores: once every wave has drained its own (acknowledged by the memory side) and the workgroup has met, a RELAXED ticket is
-  // enough - no release, i.e. no write-back of the XCD's L2 per workgroup; only the last arriver pays an acquire (an invalidate) before it reads the lists.
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (threadIdx.x == 0) {
     const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     last = t == gridDim.x - 1 ? 1u : 0u;
     if (last) {
-      __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next step's launch (stream-ordered behind this one)
+      __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch (stream-ordered behind this one), whatever the last arriver goes on to do
     }
   }
   IL_TL(0, 4);   // ticket taken
   __syncthreads();
   if (last) sync_acquire_all();
-  if (!last) return;
+  return last != 0u;
+}
+
+// One launch per environment step: every workgroup selects its chunk's candidates, takes a ticket, and the LAST one to arrive runs the merge (nobody waits: no
+// co-residency requirement). A step was two launches of ~5 us of work each; at 19 us per step the launches themselves were what was left.
+__global__ __launch_bounds__(PW_CHUNK) void k_pwil_step(il_pwil d, const float* __restrict__ state, const float* __restrict__ action, int K, PwCand* __restrict__ cand,
+                                                        unsigned* __restrict__ ticket, float* __restrict__ out) {
+  pwil_select_block<true>(d, state, action, K, cand);
+  if (!pwil_arrive_last(ticket)) return;
   pwil_merge_block(d, (int)gridDim.x, K, cand, out);
   IL_TL(1, 7);
 }
@@ -434,37 +440,25 @@ __global__ __launch_bounds__(PW_CHUNK) void k_pwil_step(il_pwil d, const float* 
 // at zero whatever the gate says.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(PW_CHUNK) void k_pwil_couple(il_pwil d, int K, PwCand* __restrict__ cand, unsigned* __restrict__ ticket, const float* mail, float* carry, float* row) {
-  __shared__ unsigned last, go;
+  __shared__ unsigned go;
   const int tid = threadIdx.x, S = d.state_dim, A = d.action_dim;
-  const float* state; const float* action; float* out; const float* ends;
+  const float* state; const float* action; float* out; const float* ends;   // ends[0 .. 1]: terminal, timeout
   float commit = 0.f; unsigned word = 0u;
   if (mail) {   // kernel-uniform
-    commit = mail[0];   // the LAST thing the host writes: it has arrived before anything of its payload is requested
+    commit = mail[ACT_MAIL_COMMIT];   // the LAST thing the host writes: it has arrived before anything of its payload is requested
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     word = (unsigned)commit;
-    const int Sp4 = (S + 3) & ~3;
+    const ActMail<const float> m = act_mail(mail, S, A);
     const bool posted = (word & IL_ACT_CARRY_FROM_MAILBOX) != 0u;
-    state = posted ? mail + IL_MAIL_HEADER + Sp4 : carry; action = posted ? mail + IL_MAIL_HEADER + 2 * Sp4 : carry + S;
-    out = carry + S + A + 1; ends = mail + 3;
+    state = posted ? m.obs() : carry; action = posted ? m.act() : carry + S;
+    out = carry + act_carry_reward(S, A); ends = mail + ACT_MAIL_TERMINAL;
   } else {
     state = row; action = row + S; out = row + 2 * S + A; ends = out + 1;
   }
   pwil_select_block<true>(d, state, action, K, cand, commit);
-  // k_pwil_step's hand-off: write-through candidates, every wave drains its own, then a RELAXED ticket; only the last arriver acquires
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last = t == gridDim.x - 1 ? 1u : 0u;
-    if (last) {
-      __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch (stream-ordered behind this one), merged or not
-    }
-  }
-  __syncthreads();
-  if (last) sync_acquire_all();
-  if (!last) return;
+  if (!pwil_arrive_last(ticket)) return;
   if (mail) {
-    if (tid == 0) go = ((word & IL_ACT_PENDING) && __float_as_uint(carry[S + A]) != word) ? 1u : 0u;
+    if (tid == 0) go = act_pending(word, carry, S, A) ? 1u : 0u;
     __syncthreads();
     for (int g = tid; g < (int)gridDim.x; g += PW_CHUNK) if (cand[(size_t)g * K].pad != commit) go = 0u;   // (rank 0 of every chunk is always written)
     __syncthreads();
@@ -476,7 +470,7 @@ __global__ __launch_bounds__(PW_CHUNK) void k_pwil_couple(il_pwil d, int K, PwCa
     const float w = (float)(1.0 / (double)d.n_atoms);
     for (int i = tid; i < d.n_atoms; i += PW_CHUNK) d.weights[i] = w;
   }
-  if (mail && tid == 0) carry[S + A + 2] = __uint_as_float(word);   // what carry[S + A + 1] is the reward of: the append stores it for this post only
+  if (mail && tid == 0) carry[act_carry_coupled(S, A)] = __uint_as_float(word);   // what the reward slot holds the reward of: the append stores it for this post only
 }
 
 __global__ __launch_bounds__(256) void k_pwil_merge_serial(il_pwil d, int G, int K, const PwCand* __restrict__ cand, float* __restrict__ out) {

@@ -16,6 +16,7 @@
 #include "mlp_tile.hpp"
 #include "peer_device.hpp"
 #include "disc_reward.hpp"
+#include "act_mail.hpp"
 IL_ST_TABLE
 #ifdef IL_EXP_CHECK   // developer build (profiles/tools/direct_soak_matrix.py): what the consumers of the fence-free hand-offs READ against what their producers finally WROTE
 static __device__ unsigned il_chk[16];
@@ -58,19 +59,6 @@ static inline int tile_threads(int H) { return H * 4 < 256 ? 256 : H * 4; }
 // LDS bytes needed by the tile kernels
 static inline size_t tile_lds_bytes(int in_pad, int H) {
   return sizeof(float) * ((size_t)IL_TILE_R * (in_pad + 4) + 2 * (size_t)IL_TILE_R * (H + 4) + (size_t)(tile_threads(H) / 64) * 256 + 256 + 64);
-}
-
-// ---------------------------------------------------------------------------------------------
-// tanh-Gaussian head for one (row, action component); op order follows torch.distributions (see oracle/nets.py)
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void head_sample(float mean, float ls_raw, float eps, float& x, float& a, float& nlp, float& ladj) {
-  const float ls = fminf(fmaxf(ls_raw, -20.f), 2.f);
-  const float sd = expf(ls);
-  x = __fadd_rn(__fmul_rn(eps, sd), mean);
-  a = tanhf(x);
-  const float d = __fsub_rn(x, mean);
-  nlp = -(d * d) / (2.f * (sd * sd)) - logf(sd) - LOG_SQRT_2PI;
-  ladj = 2.f * (LOG_2 - x - softplus_f(-2.f * x));
 }
 
 // il_sac.debug_masks (tests only; include/il_hip.h): hv = 4 consecutive rows (row .. row + 3) of hidden column `col` after the ReLU
@@ -3159,64 +3147,21 @@ __global__ __launch_bounds__(1024) void k_act_step(const float* __restrict__ act
   if (version) actor += (size_t)version[0] * mirror_stride;   // published parameter snapshot (il_act_publish): never the arena an update is rewriting
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x;
-  const int Sp4 = (S + 3) & ~3, Ap4 = (A + 3) & ~3;
-  const float* m_next = mail + IL_MAIL_HEADER; const float* m_obs = m_next + Sp4; float* m_act = mail + IL_MAIL_HEADER + 2 * Sp4; float* m_echo = m_act + Ap4;
-  // mail[0] is the commit word (sequence << 6 | IL_ACT_* flags), the LAST thing the host writes: one 4-byte store publishes the post.
-  // carry[S+A] remembers the commit word of the last appended transition, so a launch that runs again without a new post (a replayed
-  // graph, or a launch still queued when the host posts the next step) appends each transition exactly once.
-  const float commit = mail[0];
-  const unsigned word = (unsigned)commit, flags = word & 63u;
-  float* consumed = carry + S + A;
-  const long long cursor = ring_state[0], cap = ring_state[2];
-  const bool pending = (flags & IL_ACT_PENDING) && __float_as_uint(consumed[0]) != word, wrap = pending && (flags & IL_ACT_WRAP_ABSORBING);
-  const int o_next = S + A, o_rew = 2 * S + A;
-  // a reward computed on the device belongs to the post whose commit word il_pwil_act_reward left in carry[S + A + 2]: a pending post it has not coupled (a replayed launch
-  // overtaken by the host's next post) is left alone - no row, no action, no echo - for the coupling + append pair the host enqueues behind that post
-  if (pending && (flags & IL_ACT_REWARD_ON_DEVICE) && __float_as_uint(carry[o_next + 2]) != word) return;   // block-uniform
-  if (pending && tid < row) {
-    const int c = tid;
-    float v = 0.f;
-    if (c < o_next) v = (flags & IL_ACT_CARRY_FROM_MAILBOX) ? (c < S ? m_obs[c] : m_act[c - S]) : carry[c];   // state | action of the transition
-    else if (c < o_rew) v = wrap ? (c == o_rew - 1 ? 1.f : 0.f) : m_next[c - o_next];    // next_state, or the absorbing state (memory.py:67)
-    else if (c == o_rew) v = (flags & IL_ACT_REWARD_ON_DEVICE) ? carry[o_next + 1] : mail[2];   // reward (posted, or left by il_pwil_act_reward ahead of this launch)
-    else if (c == o_rew + 1) v = wrap ? 0.f : mail[3];                                   // terminal (cleared by the wrap)
-    else if (c == o_rew + 2) v = mail[4];                                                // timeout
-    else if (c == o_rew + 3) v = 1.f;                                                    // weight
-    else if (c == o_rew + 4) v = mail[5];                                                // step
-    ring[cursor * row + c] = v;
-    if (wrap) {  // absorbing -> absorbing row (memory.py:68)
-      float w = 0.f;
-      if (c < S) w = (c == S - 1) ? 1.f : 0.f;
-      else if (c >= o_next && c < o_rew) w = (c == o_rew - 1) ? 1.f : 0.f;
-      else if (c == o_rew + 3) w = 1.f;
-      else if (c == o_rew + 4) w = mail[5];
-      ring[((cursor + 1) % cap) * row + c] = w;
-    }
-  }
-  if (!(flags & IL_ACT_NO_ACTION)) {  // block-uniform
-    const int greedy = flags & IL_ACT_GREEDY;
-    const ActTile t = actor_tile(smem, actor, S, A, H, m_obs, Sp4, 0, 1);   // barriers inside: every carry[] read above precedes the writes below
+  const ActPost p = act_post(mail, carry, ring_state, S, A);
+  if (p.uncoupled) return;   // block-uniform: no row, no action, no echo
+  act_append(p, carry, ring, row, S, A);
+  if (!(p.flags & IL_ACT_NO_ACTION)) {  // block-uniform
+    const int greedy = p.flags & IL_ACT_GREEDY;
+    const ActTile t = actor_tile(smem, actor, S, A, H, p.m.obs(), p.m.ld, 0, 1);   // barriers inside: every carry[] read above precedes the writes below
     if (tid < A) {
       const float mean = t.Os[tid], lsr = t.Os[A + tid];
       float x, a = tanhf(mean), nlp, ladj;
       if (!greedy) head_sample(mean, lsr, philox_normal(seed, offset, IL_STREAM_ACT, (uint32_t)tid), x, a, nlp, ladj);
-      m_act[tid] = a; carry[S + tid] = a;
+      p.m.act()[tid] = a; carry[S + tid] = a;
     }
-    if (tid >= 64 && tid < 64 + S) carry[tid - 64] = m_obs[tid - 64];
+    if (tid >= 64 && tid < 64 + S) carry[tid - 64] = p.m.obs()[tid - 64];
   }
-  __threadfence_system();
-  __syncthreads();   // every thread has read consumed[0], the cursor and the mailbox by now
-  if (tid == 0) {
-    if (pending) {
-      // the cursor moves only here, behind the barrier: an append-only launch (IL_ACT_NO_ACTION) has no other barrier between the waves' loads of ring_state[0] above and
-      // this store, and with rows wider than one wave (Ant: 240 floats) a wave that loaded late would have written its columns into the next row
-      const long long adv = wrap ? 2 : 1, nc = cursor + adv;
-      ring_state[0] = nc % cap;
-      if (nc >= cap) ring_state[1] = 1;
-      consumed[0] = __uint_as_float(word);
-    }
-    __hip_atomic_store(m_echo, commit, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  act_commit(p, carry, ring_state, S, A);
 }
 
 extern "C" int il_actor_act(const float* actor, int32_t S, int32_t A, int32_t H, const float* states, int32_t ld_states, int32_t n, const float* eps,
@@ -3256,7 +3201,7 @@ extern "C" int il_act_publish(const float* actor, int64_t n, float* mirror, int6
   return IL_OK;
 }
 
-extern "C" int32_t il_act_mailbox_floats(int32_t S, int32_t A) { return (IL_MAIL_HEADER + 2 * ((S + 3) & ~3) + ((A + 3) & ~3) + 1 + 15) & ~15; }
+extern "C" int32_t il_act_mailbox_floats(int32_t S, int32_t A) { return act_mail((const float*)nullptr, S, A).floats(); }
 
 extern "C" int il_act_step(const float* actor, int32_t S, int32_t A, int32_t H, float* mailbox, float* carry, float* ring, int64_t* ring_state, uint64_t noise_seed,
                            uint32_t noise_offset, const int32_t* mirror_version, int64_t mirror_stride, il_stream_t stream_) {

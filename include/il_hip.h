@@ -381,7 +381,8 @@ int il_bc_step_general(float* actor, float* actor_grad, const il_adam* opt, int3
  * carry (device, S+A+4 floats, zero-initialised): state | action of the pending transition written by the previous call, then the
  *   commit word of the last appended transition: a launch that runs again without a new post appends nothing (exactly-once); then
  *   the reward slot of IL_ACT_REWARD_ON_DEVICE and the commit word it belongs to.
- * ring_state (device int64[3] = cursor, full, capacity) is advanced on the device (by 2 when the wrap is requested). */
+ * ring_state (device int64[3] = cursor, full, capacity) is advanced on the device (by 2 when the wrap is requested).
+ * The kernels read all of this through the names of ONE header, csrc/act_mail.hpp (ACT_MAIL_*, ActMail, act_carry_*): a change to the layout is made there and here. */
 #define IL_MAIL_HEADER 8
 #define IL_ACT_PENDING 1u        /* a transition (carry, mailbox) is waiting to be appended */
 #define IL_ACT_WRAP_ABSORBING 2u /* episode ended by true termination with absorbing=true: rewrite + extra row */

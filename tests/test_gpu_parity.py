@@ -931,13 +931,19 @@ def _episode_script(rs, n, S, absorbing):
   return out
 
 
+# every schedule at (S, A, H) = (18, 6, 256), whose cases keep their ids, and at (111, 8, 64)
+ACTING_SCHEDULES_AND_SHAPES = [pytest.param(schedule, shape, id=schedule + tag) for tag, shape in (('', (18, 6, 256)), ('-S111-A8-H64', (111, 8, 64))) for schedule in ('exact', 'fused', 'overlap')]
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('absorbing', [True, False])
-@pytest.mark.parametrize('schedule', ['exact', 'fused', 'overlap'])
-def test_acting_worker_matches_separate_calls(absorbing, schedule):
+@pytest.mark.parametrize('schedule,shape', ACTING_SCHEDULES_AND_SHAPES)
+def test_acting_worker_matches_separate_calls(absorbing, schedule, shape):
   """One launch per env step (mailbox in pinned memory, cursor on the device) against the per-function path: same actions (same
-  Philox offsets), bit-identical ring including absorbing wraps and ring wrap-around, same host-side cursor / trajectory count."""
-  actor_a, actor_b, mem_a, mem_b = _acting_pair(absorbing)
+  Philox offsets), bit-identical ring including absorbing wraps and ring wrap-around, same host-side cursor / trajectory count.
+  S = 111, A = 8, H = 64: a ring row of 235 floats spread over the four waves of a 256-thread workgroup that it nearly fills, and 64 + S = 175 threads in the carry copy
+  (S = 18, A = 6: 47 floats, which one wave writes)."""
+  actor_a, actor_b, mem_a, mem_b = _acting_pair(absorbing, S=shape[0], A=shape[1], H=shape[2])
   S = mem_a.state_size
   rs = np.random.RandomState(5)
   script = _episode_script(rs, 60, S, absorbing)

@@ -656,14 +656,14 @@ def test_general_shape_update_plan_on_the_emulated_kernels(monkeypatch, algorith
 
 
 @pytest.mark.parametrize('absorbing', [True, False])
-@pytest.mark.parametrize('schedule', ['exact', 'fused', 'overlap'])
-def test_acting_worker_on_the_emulated_kernels(monkeypatch, absorbing, schedule):
+@pytest.mark.parametrize('schedule,shape', [pytest.param(schedule, shape, id=schedule + tag) for tag, shape in (('', (18, 6, 256)), ('-S111-A8-H64', (111, 8, 64))) for schedule in ('exact', 'fused', 'overlap')])   # test_gpu_parity.ACTING_SCHEDULES_AND_SHAPES
+def test_acting_worker_on_the_emulated_kernels(monkeypatch, absorbing, schedule, shape):
   """tests/test_gpu_parity.py::test_acting_worker_matches_separate_calls: the one-launch-per-env-step worker (mailbox, device-side cursor, absorbing wraps, ring
   wrap-around) against the per-function path - same actions, bit-identical ring. Round 3: the emulator, whose lanes do not run in lockstep, failed the append-only
   schedules here: k_act_step moved the ring cursor before every wave had read it (no barrier on that path; harmless within one wave on the device, a latent race for rows
   wider than a wave - Ant's 240 floats). The store now sits behind the kernel's barrier."""
   tgp = _emulated_product(monkeypatch, streams=True)
-  tgp.test_acting_worker_matches_separate_calls(absorbing, schedule)
+  tgp.test_acting_worker_matches_separate_calls(absorbing, schedule, shape)
 
 
 @pytest.mark.parametrize('schedule', ['exact', 'fused'])
