@@ -1,36 +1,29 @@
 // GMMIL pairwise-RBF reward (reference models.py:25-44, 183-201) for gfx950.
 //
 // reward_i = sum_gamma w~_i sum_j exp(-gamma d(x_i, e_j)) w~e_j  -  w~_i sum_j exp(-gamma d(x_i, x_j)) w~_j,   d(x, y) = (1/D) sum_k (x_k - y_k)^2.
-// Round 6: the reward launch for D <= 128 is k_gmmil_mfma (below): the distances as a CENTRED Gram product on the matrix pipes - as close to float64 as the direct
-// difference form whatever the data's offset. The kernels that follow first are the DIRECT difference forms of rounds 1-5 (3 VALU flop per pair-feature): they still
-// compute the distance matrix the bandwidths' medians come from (il_gmmil_sqdist), rewards for D > 128, and everything under IL_GMMIL_MFMA=0. (The UNcentred
-// ||x||^2+||y||^2-2xy form loses ~3 digits to cancellation once the data has an offset, and the reward is itself a difference of near-equal sums: never used.)
-// The reference materialises [B,B,D] temporaries (0.5 GB at B=1024, D=120); here nothing larger than a tile of pair distances ever exists, and it lives in registers:
-//   k_gmmil_pack   feature-major copies XT[D][B1], ET[D][B2] (so LDS tiles load coalesced and read conflict-free) and
-//                  the normalised weights;
-//   k_gmmil_tile   grid (i-tile, j-tile, matrix): 64x64 pairs per workgroup, 4x4 per thread, features streamed through
-//                  LDS in chunks of 32 (a ring of register slots keeps every chunk of D <= 128 in flight from the start;
-//                  LDS operands double-buffered in registers), two ds_read_b128 per 16 pair updates; epilogue exp +
-//                  weighted row sums; the row tile's last-arriving workgroup then sums the per-column-tile partials in
-//                  tile order (deterministic).
-// Measured anatomy at B = 1024, D = 120 (profiles/r02_gmmil_timeline.md; s_memtime per workgroup): the packed-op loop runs at the VALU issue rate
-// (4.3-4.9 ticks per v_pk instruction per SIMD); what the kernel time holds beyond it is the first fabric round trip, the exp epilogue, the
-// release ticket and the last arriver's sums.
+// The reference materialises [B,B,D] temporaries (0.5 GB at B=1024, D=120); here nothing larger than a tile of pair distances ever exists, and it lives in registers.
+// Three launch forms, each with a reach of its own:
+//   k_gmmil_mfma    the reward launch for D <= 128: the distances as a CENTRED Gram product on the matrix pipes - as close to float64 as the direct difference form
+//                   whatever the data's offset. (The UNcentred ||x||^2+||y||^2-2xy form loses ~3 digits to cancellation once the data has an offset, and the reward is
+//                   itself a difference of near-equal sums: never used.)
+//   k_gmmil_sx      the fast DIRECT difference form (3 VALU flop per pair-feature; the row operand in scalar registers) where its alignment conditions hold: whole
+//                   16-byte lanes along the rows, S and D multiples of 8, D <= 152.
+//   k_gmmil_direct  the general direct difference form - any row count, any alignment, any D >= 1 - wherever k_gmmil_sx is not eligible.
+// The two direct forms compute the distance matrix the bandwidths' medians come from (il_gmmil_sqdist: first call only), rewards for D > 128, and everything under
+// IL_GMMIL_MFMA=0. They keep every pair's accumulation order over the features, the 64-column partial sums and the tile-ordered final sums: bit-identical to each other
+// (tests/test_gpu_parity.py). Common to all three: a workgroup leaves its partial row sums in the workspace and takes a ticket on its row tile's arrival counter; the
+// last arriver adds the partials up in tile order (deterministic) and leaves the counter at zero for the next call.
+// Measured anatomy of the direct forms' pair loop at B = 1024, D = 120 (profiles/r02_gmmil_timeline.md): the packed-op loop runs at the VALU issue rate (4.3-4.9 ticks
+// per v_pk instruction per SIMD); what the kernel time holds beyond it is the first fabric round trip, the exp epilogue, the ticket and the last arriver's sums.
 #include "il_common.hpp"
 IL_ST_TABLE
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 #define GT 64   // tile edge (pairs): columns of a pair tile, rows of a pack tile
 #define GKC 32  // feature chunk
-#ifndef GMMIL_RB
-#define GMMIL_RB 4   // rows of a thread's register block (x 4 columns); a pair tile is GTR rows x GT columns
-#endif
-#ifndef GMMIL_GG
+#define GMMIL_RB 4   // rows of a thread's register block (x 4 columns); a pair tile is GTR rows x GT columns (8 x 4 lost: profiles/r05_gmmil_rb8_ab.txt)
 #define GMMIL_GG 2   // features per double-buffered group of LDS operand reads
-#endif
-#ifndef GMMIL_PF
 #define GMMIL_PF 4   // feature chunks in flight (register slots of the global -> LDS ring)
-#endif
 #define GTR (16 * GMMIL_RB)
 #define GCTR 32   // floats between two arrival counters: same-line atomics from 8 XCDs serialise at the memory side
 
@@ -43,13 +36,17 @@ struct GmmilExp { float c1, c2; };
 __host__ __device__ inline GmmilExp gmmil_exp_consts(float g1, float g2, int D) { return GmmilExp{-g1 * 1.44269504088896340736f / (float)D, -g2 * 1.44269504088896340736f / (float)D}; }
 __device__ __forceinline__ float gmmil_pair_kernel(float ssq, const GmmilExp& e) { return __builtin_amdgcn_exp2f(ssq * e.c1) + __builtin_amdgcn_exp2f(ssq * e.c2); }
 
-struct GmmilWs { int64_t xt, et, wn, wen, part, ctr, part2, total; int b1p, b2p, njt; };
+struct GmmilWs { int64_t rsv[4], part, ctr, part2, total; int b1p, b2p, njt; };
 __host__ __device__ inline GmmilWs gmmil_ws(int n1, int n2, int D) {
   GmmilWs w; w.b1p = (n1 + GTR - 1) / GTR * GTR; w.b2p = (n2 + GT - 1) / GT * GT;   // policy rows: whole row tiles (GTR is a multiple of GT); padded rows / columns carry weight 0
   const int nj1 = w.b2p / GT, nj2 = w.b1p / GT; w.njt = nj1 > nj2 ? nj1 : nj2;
   int64_t o = 0;
-  w.xt = o; o += (int64_t)D * w.b1p; w.et = o; o += (int64_t)D * w.b2p; w.wn = o; o += w.b1p; w.wen = o; o += w.b2p;
-  w.part = o; o += (int64_t)2 * w.njt * w.b1p; w.ctr = o; o += (int64_t)(w.b1p / 32) * GCTR;   // arrival counter per row tile (64 rows; k_gmmil_sx: 32 rows), one 128-byte line each (zeroed by k_gmmil_pack)
+  // reserved: the retired packing launch's operand copies (2 D B floats) and normalised weights. Nothing reads them. They stay, written as these four statements, so that
+  // k_gmmil_mfma and k_gmmil_sx compile to the code they had: without the gap six k_gmmil_mfma instantiations change their SGPR count, and the same sum written as one
+  // expression reorders their scalar address arithmetic (profiles/gmmil_forms_ab.txt).
+  w.rsv[0] = o; o += (int64_t)D * w.b1p; w.rsv[1] = o; o += (int64_t)D * w.b2p; w.rsv[2] = o; o += w.b1p; w.rsv[3] = o; o += w.b2p;
+  w.part = o; o += (int64_t)2 * w.njt * w.b1p;   // direct forms: one partial row sum per (matrix, column tile of 64, row)
+  w.ctr = o; o += (int64_t)(w.b1p / 32) * GCTR;   // arrival counter per row tile (64 rows; k_gmmil_sx: 32 rows), one 128-byte line each: zero at creation, left at zero by each row tile's last arriver
   w.part2 = o; o += (int64_t)((w.b2p + 31) / 32 + (w.b1p + 31) / 32) * w.b1p;   // k_gmmil_mfma: one partial row sum per (column block of >= 32, row)
   w.total = o;
   return w;
@@ -60,207 +57,20 @@ __device__ __forceinline__ float cat_at(const il_batch& b, int S, int r, int k) 
   return k < S ? b.states[(size_t)r * b.ld_states + k] : b.actions[(size_t)r * b.ld_actions + (k - S)];
 }
 
-// grid = (tiles of 64 rows over both sets: policy tiles first, then expert tiles; feature chunks of GKC): one workgroup transposes ONE 64 x 32 chunk, so the 1 MB of
-// inputs is spread over ~128 workgroups instead of 32 that each looped over four chunks behind barriers (12.7 us -> see profiles/r02_*); the chunk-0 workgroup of a
-// tile also normalises its 64 weights (every such workgroup sums the whole weight column: B strided loads, a few per thread).
-__global__ __launch_bounds__(256) void k_gmmil_pack(il_batch pol, il_batch exp, int S, int D, float* __restrict__ ws_) {
-  __shared__ float tile[GT][GKC + 1];
-  __shared__ float red[32];
-  const GmmilWs w = gmmil_ws(pol.n, exp.n, D);
-  const int nt1 = w.b1p / GT;
-  if (blockIdx.x == 0 && blockIdx.y == 0) for (int i = threadIdx.x; i < w.b1p / GTR; i += blockDim.x) reinterpret_cast<unsigned*>(ws_ + w.ctr)[i * GCTR] = 0u;
-  const bool is_exp = (int)blockIdx.x >= nt1;
-  const il_batch& b = is_exp ? exp : pol;
-  const int n = b.n, np = is_exp ? w.b2p : w.b1p, row0 = ((int)blockIdx.x - (is_exp ? nt1 : 0)) * GT;
-  float* T = ws_ + (is_exp ? w.et : w.xt);
-  const int k0 = (int)blockIdx.y * GKC;
-  float s = 0.f;
-  if (blockIdx.y == 0) for (int i = threadIdx.x; i < n; i += blockDim.x) s += b.weights[(size_t)i * b.ld_weights];   // requested before the transpose: in flight under it
-  for (int i = threadIdx.x; i < GT * GKC; i += blockDim.x) {
-    const int r = i / GKC, k = i - r * GKC;
-    tile[r][k] = (row0 + r < n && k0 + k < D) ? cat_at(b, S, row0 + r, k0 + k) : 0.f;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < GT * GKC; i += blockDim.x) {
-    const int k = i / GT, r = i - k * GT;
-    if (k0 + k < D) T[(size_t)(k0 + k) * np + row0 + r] = tile[r][k];
-  }
-  if (blockIdx.y != 0) return;
-  s = block_sum(s, red);
-  float* wn = ws_ + (is_exp ? w.wen : w.wn);
-  for (int r = threadIdx.x; r < GT; r += blockDim.x) wn[row0 + r] = (row0 + r < n) ? b.weights[(size_t)(row0 + r) * b.ld_weights] / s : 0.f;
-}
-
-// MODE 0: reward partials; MODE 1: write the distance matrix (out [n1][n2])
-template <int MODE>
-__global__ __launch_bounds__(256) void k_gmmil_tile(int n1, int n2, int D, float g1, float g2, float* __restrict__ ws_, float* __restrict__ dist_out, int self_second,
-                                                    float* __restrict__ out_r, float* __restrict__ out_sim, float* __restrict__ out_self) {
-  constexpr int RB = GMMIL_RB, RQ = RB / 4;   // a thread's block: RB rows (RQ 16-byte LDS reads) x 4 columns (one read)
-  __shared__ __attribute__((aligned(16))) float Xs[GKC][GTR];
-  __shared__ __attribute__((aligned(16))) float Ys[GKC][GT];
-  const GmmilWs w = gmmil_ws(n1, n2, D);
-  const int it = blockIdx.x, jt = blockIdx.y, mat = blockIdx.z;  // mat 0: policy vs expert, 1: policy vs policy
-  const bool vs_self = (mat == 1) || (MODE == 1 && self_second);
-  const int npy = vs_self ? w.b1p : w.b2p;
-  if (jt * GT >= npy) return;
-  const float* XT = ws_ + w.xt; const float* YT = ws_ + (vs_self ? w.xt : w.et);
-  const float* wy = ws_ + (vs_self ? w.wn : w.wen);
-  const int ti = threadIdx.x >> 4, tj = threadIdx.x & 15;
-  f32x2 acc2[RB][2];
-#pragma unroll
-  for (int a = 0; a < RB; ++a) { acc2[a][0] = f32x2{0.f, 0.f}; acc2[a][1] = f32x2{0.f, 0.f}; }
-  // Feature chunks of GKC through a ring of NPF register slots: the loads of chunks c+1 .. c+NPF-1 are in flight while chunk c is consumed, and a slot is
-  // refilled (chunk c+NPF) as soon as its values are in LDS. XT / ET were written by k_gmmil_pack a moment ago, mostly on other XCDs, so a load is a trip to
-  // the fabric: measured 1.7 us per chunk against 1 us of packed ops - with one chunk of look-ahead the loop waited 60 % of its time. D <= NPF * GKC (every
-  // shipped environment): all of a tile's operands are requested before the first barrier.
-  constexpr int PERX = GKC * GTR / 256, PERY = GKC * GT / 256, NPF = GMMIL_PF;
-  float xr[NPF][PERX], yr[NPF][PERY];
-  auto fetch = [&](float* xs_, float* ys_, int k0) {
-#pragma unroll
-    for (int u = 0; u < PERX; ++u) {
-      const int i = threadIdx.x + u * 256, k = i / GTR, c = i - k * GTR;
-      xs_[u] = XT[(size_t)min(k0 + k, D - 1) * w.b1p + it * GTR + c];   // clamped address, zeroed when it is stored to LDS: a predicated load is an exec-masked branch each,
-                                                                        // a select right here would wait for the load
-    }
-#pragma unroll
-    for (int u = 0; u < PERY; ++u) {
-      const int i = threadIdx.x + u * 256, k = i / GT, c = i - k * GT;
-      ys_[u] = YT[(size_t)min(k0 + k, D - 1) * npy + jt * GT + c];
-    }
-  };
-  const bool stamp = blockIdx.x == 3 && blockIdx.y == 5 && blockIdx.z == 0;
-  IL_STAMP(stamp, 0);
-#pragma unroll
-  for (int sl = 0; sl < NPF; ++sl) if (sl * GKC < D) fetch(xr[sl], yr[sl], sl * GKC);
-  for (int kk = 0; kk < D; kk += NPF * GKC) {
-#pragma unroll
-   for (int sl = 0; sl < NPF; ++sl) {
-    const int k0 = kk + sl * GKC;
-    if (k0 >= D) break;
-#pragma unroll
-    for (int u = 0; u < PERX; ++u) { const int i = threadIdx.x + u * 256, k = i / GTR, c = i - k * GTR; Xs[k][c] = (k0 + k < D) ? xr[sl][u] : 0.f; }
-#pragma unroll
-    for (int u = 0; u < PERY; ++u) { const int i = threadIdx.x + u * 256, k = i / GT, c = i - k * GT; Ys[k][c] = (k0 + k < D) ? yr[sl][u] : 0.f; }
-    __syncthreads();
-    if (k0 + NPF * GKC < D) fetch(xr[sl], yr[sl], k0 + NPF * GKC);
-    // all GKC features of the chunk (features >= D are staged as zeros on both sides: they add (0 - 0)^2), so the loop has a fixed trip count.
-    // The LDS operands are double-buffered in registers in groups of GG features: the ds_read_b128 of the NEXT group are issued (and pinned there by a
-    // scheduling barrier) before the packed ops of the current one. Left to itself hipcc sinks every read to its first use: read - s_waitcnt lgkmcnt(0) -
-    // 16 ops per feature, i.e. a full LDS round trip exposed per feature step with one or two waves per SIMD (measured 200 cycles per step against 68 of VALU issue).
-    constexpr int GG = GMMIL_GG;
-    f32x4 xa_[GG][RQ], ya_[GG], xb_[GG][RQ], yb_[GG];
-    auto lds_group = [&](f32x4 (*xg)[RQ], f32x4* yg, int kb) {
-#pragma unroll
-      for (int u = 0; u < GG; ++u) {
-#pragma unroll
-        for (int q = 0; q < RQ; ++q) xg[u][q] = *reinterpret_cast<const f32x4*>(&Xs[kb + u][ti * RB + 4 * q]);
-        yg[u] = *reinterpret_cast<const f32x4*>(&Ys[kb + u][tj * 4]);
-      }
-    };
-    auto fma_group = [&](const f32x4 (*xg)[RQ], const f32x4* yg) {
-#pragma unroll
-      for (int u = 0; u < GG; ++u) {
-        const f32x2 y01 = {yg[u][0], yg[u][1]}, y23 = {yg[u][2], yg[u][3]};
-#pragma unroll
-        for (int a = 0; a < RB; ++a) {   // two pairs per instruction: v_pk_add_f32 + v_pk_fma_f32 (same roundings as the scalar sub + fma)
-          const float xs = xg[u][a >> 2][a & 3];
-          const f32x2 xa = {xs, xs};
-          const f32x2 d0 = xa - y01, d1 = xa - y23;
-          acc2[a][0] = __builtin_elementwise_fma(d0, d0, acc2[a][0]);
-          acc2[a][1] = __builtin_elementwise_fma(d1, d1, acc2[a][1]);
-        }
-      }
-    };
-    lds_group(xa_, ya_, 0);
-#pragma unroll 1
-    for (int kb = 0; kb < GKC; kb += 2 * GG) {   // a rolled loop: unrolled, the copies do not share registers (296 VGPRs with four chunks in flight)
-      lds_group(xb_, yb_, kb + GG);
-      __builtin_amdgcn_sched_barrier(0);
-      fma_group(xa_, ya_);
-      __builtin_amdgcn_sched_barrier(0);
-      lds_group(xa_, ya_, (kb + 2 * GG) & (GKC - 1));   // the last trip re-reads group 0 (discarded) instead of branching
-      __builtin_amdgcn_sched_barrier(0);
-      fma_group(xb_, yb_);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    __syncthreads();
-   }
-  }
-  IL_STAMP(stamp, 1);
-  float acc[RB][4];
-#pragma unroll
-  for (int a = 0; a < RB; ++a) { acc[a][0] = acc2[a][0][0]; acc[a][1] = acc2[a][0][1]; acc[a][2] = acc2[a][1][0]; acc[a][3] = acc2[a][1][1]; }
-  const float fD = (float)D;
-  const GmmilExp gex = gmmil_exp_consts(g1, g2, D);
-  if (MODE == 1) {
-    const int n2e = vs_self ? n1 : n2;
-#pragma unroll
-    for (int a = 0; a < RB; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const int i = it * GTR + ti * RB + a, j = jt * GT + tj * 4 + b;
-        if (i < n1 && j < n2e) dist_out[(size_t)i * n2e + j] = acc[a][b] / fD;
-      }
-    return;
-  }
-  const f32x4 wv = *reinterpret_cast<const f32x4*>(wy + jt * GT + tj * 4);
-  float* part = ws_ + w.part + ((size_t)mat * w.njt + jt) * w.b1p + it * GTR;
-#pragma unroll
-  for (int a = 0; a < RB; ++a) {
-    float s = 0.f;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) s += wv[b] * gmmil_pair_kernel(acc[a][b], gex);
-    s = group16_sum(s);
-    if (tj == 0) part[ti * RB + a] = s;
-  }
-  IL_STAMP(stamp, 2);
-  if (!out_r) return;
-  // The row tile's reward needs the partial sums of every column tile of BOTH matrices: the workgroup that arrives last (one agent-scope release
-  // ticket per workgroup, after a barrier; only the last arriver pays for the acquire) adds them up in tile order - the separate, launch-bound
-  // "final" kernel this replaces cost 11 us.
-  __shared__ unsigned last;
-  sync_drain_stores();
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned expect = (unsigned)(w.b2p / GT + w.b1p / GT);
-    last = __hip_atomic_fetch_add(reinterpret_cast<unsigned*>(ws_ + w.ctr) + it * GCTR, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT) + 1u == expect;
-  }
-  __syncthreads();
-  if (last) sync_acquire_all();   // (every wave of the last arriver: il_common.hpp)
-  IL_STAMP(stamp, 3);
-  if (!last || threadIdx.x >= GTR) return;
-  const int i = it * GTR + threadIdx.x;
-  if (i >= n1) return;
-  // all partials of a matrix requested before the first add (a dependent load-add chain is one fabric round trip per column tile); added in tile order
-  auto ordered_sum = [&](const float* p, int nq) {
-    float s = 0.f;
-    for (int q0 = 0; q0 < nq; q0 += 16) {
-      float v[16];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) v[u] = p[(size_t)min(q0 + u, nq - 1) * w.b1p];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) if (q0 + u < nq) s += v[u];
-    }
-    return s;
-  };
-  const float s0 = ordered_sum(ws_ + w.part + i, w.b2p / GT);
-  const float s1 = ordered_sum(ws_ + w.part + (size_t)w.njt * w.b1p + i, w.b1p / GT);
-  const float wi = ws_[w.wn + i];
-  const float sim = wi * s0, self = wi * s1;
-  out_r[i] = sim - self;
-  if (out_sim) out_sim[i] = sim;
-  if (out_self) out_self[i] = self;
-}
-
 // ---------------------------------------------------------------------------------------------
-// k_gmmil_direct (round 4): k_gmmil_tile reading its operands straight from the two batches. k_gmmil_pack only existed to give the tile kernel feature-major operands; it
-// cost a 6 us launch plus a kernel boundary per reward call, and its output - written an instant earlier, mostly on other XCDs - made every operand load of the tile
-// kernel a fabric round trip. Here a thread loads 16-byte lanes ALONG a row (8 lanes cover the 32 features of a chunk: whole 128-byte lines of the row-major batch),
-// and transposes on its way into LDS: Xs[k][r ^ 4 ((k / 4) % 8)] - the XOR swizzle keeps every group of four consecutive rows aligned and contiguous (the inner loop's
-// ds_read_b128) and spreads the eight lanes that write one row's 32 features over eight banks (an unswizzled transposed store is an 8-way conflict). Each workgroup sums
-// the weight columns itself (k_gmmil_pack's chunk-0 workgroups did the same sums in the same order: same bits). Same pair arithmetic, same partial sums, same
-// last-arriver reduction: bit-identical rewards. The arrival counters are left at zero by the last arriver of each row tile: zero-initialise the workspace ONCE per shape
-// (include/il_hip.h). Rows that are not whole 16-byte lanes (S, A, strides or pointers not multiples of 4 floats) take the element-wise loads of cat_at.
+// k_gmmil_direct: the general direct difference form. grid (i-tile, j-tile, matrix): 64 x 64 pairs per workgroup, 4 x 4 per thread, both operands read straight from the
+// two row-major batches. A thread loads 16-byte lanes ALONG a row (8 lanes cover the 32 features of a chunk: whole 128-byte lines), and transposes on its way into LDS:
+// Xs[k][r ^ 4 ((k / 4) % 8)] - the XOR swizzle keeps every group of four consecutive rows aligned and contiguous (the inner loop's ds_read_b128) and spreads the eight
+// lanes that write one row's 32 features over eight banks (an unswizzled transposed store is an 8-way conflict). Rows that are not whole 16-byte lanes (S, A, strides or
+// pointers not multiples of 4 floats - every D < 4 among them) take the element-wise loads of cat_at. Features stream through LDS in chunks of 32: a ring of register
+// slots keeps every chunk of D <= 128 in flight from the start, two ds_read_b128 feed 16 pair updates, the LDS operands are double-buffered in registers. Epilogue:
+// exp + weighted row sums (each workgroup sums the weight columns itself); the row tile's last-arriving workgroup then sums the per-column-tile partials in tile order.
+// The arrival counters are left at zero by the last arriver of each row tile: zero-initialise the workspace ONCE per shape (include/il_hip.h).
+// (Earlier forms, retired with the same bits: a separate feature-major packing launch in front of the tile kernel - 6 us and a kernel boundary per call, and every operand
+// load a fabric round trip to lines written an instant before on other XCDs; and a variant with the whole feature range of both tiles resident in LDS behind one barrier
+// and a fence-free arrival, limited to D <= 160 - the same call rate at the timed size (profiles/r05_gmmil_ab_resident.txt), a launch 7 % shorter at D = 132 and 29 %
+// at B = 1024, D = 24, where this kernel runs a whole chunk of 32 features (profiles/gmmil_forms_ab.txt): the single-barrier loop is what to give this kernel if
+// a configuration ever depends on these shapes.)
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ f32x4 cat_lane(const il_batch& b, int S, int D, int r, int k, bool lanes) {   // features k .. k + 3 of row r (k % 4 == 0); beyond D: don't care (zeroed at the LDS store)
   if (lanes) {
@@ -279,13 +89,14 @@ __global__ __launch_bounds__(256) void k_gmmil_direct(il_batch pol, il_batch exp
   __shared__ __attribute__((aligned(16))) float Xs[GKC][GTR];
   __shared__ __attribute__((aligned(16))) float Ys[GKC][GT];
   __shared__ float red[32];
+  IL_ST_BEGIN(IL_ST_GMMIL);
   globalize(pol); globalize(exp);
   const int n1 = pol.n, n2 = exp.n;
   const GmmilWs w = gmmil_ws(n1, n2, D);
   const int it = blockIdx.x, jt = blockIdx.y, mat = blockIdx.z;  // mat 0: policy vs expert, 1: policy vs policy
   const bool vs_self = (mat == 1) || (MODE == 1 && self_second);
   const int npy = vs_self ? w.b1p : w.b2p;
-  if (jt * GT >= npy) return;
+  if (jt * GT >= npy) { IL_ST_END(IL_ST_GMMIL); return; }
   const il_batch& yb = vs_self ? pol : exp;
   const int ny = yb.n;
   const int ti = threadIdx.x >> 4, tj = threadIdx.x & 15;
@@ -298,6 +109,9 @@ __global__ __launch_bounds__(256) void k_gmmil_direct(il_batch pol, il_batch exp
   f32x2 acc2[RB][2];
 #pragma unroll
   for (int a = 0; a < RB; ++a) { acc2[a][0] = f32x2{0.f, 0.f}; acc2[a][1] = f32x2{0.f, 0.f}; }
+  // Feature chunks of GKC through a ring of NPF register slots: the loads of chunks c+1 .. c+NPF-1 are in flight while chunk c is consumed, and a slot is refilled
+  // (chunk c+NPF) as soon as its values are in LDS. D <= NPF * GKC (every shipped environment): all of a tile's operands are requested before the first barrier.
+  // (Addresses are clamped and the value zeroed when it is stored to LDS: a predicated load is an exec-masked branch each, a select at the load would wait for it.)
   constexpr int PX4 = GKC * GTR / 4 / 256, PY4 = GKC * GT / 4 / 256, NPF = GMMIL_PF;   // 16-byte lanes per thread and chunk
   f32x4 xr[NPF][PX4], yr[NPF][PY4];
   auto fetch = [&](f32x4* xs_, f32x4* ys_, int k0) {
@@ -329,6 +143,10 @@ __global__ __launch_bounds__(256) void k_gmmil_direct(il_batch pol, il_batch exp
     }
     __syncthreads();
     if (k0 + NPF * GKC < D) fetch(xr[sl], yr[sl], k0 + NPF * GKC);
+    // all GKC features of the chunk (features >= D are staged as zeros on both sides: they add (0 - 0)^2), so the loop has a fixed trip count.
+    // The LDS operands are double-buffered in registers in groups of GG features: the ds_read_b128 of the NEXT group are issued (and pinned there by a
+    // scheduling barrier) before the packed ops of the current one. Left to itself hipcc sinks every read to its first use: read - s_waitcnt lgkmcnt(0) -
+    // 16 ops per feature, i.e. a full LDS round trip exposed per feature step with one or two waves per SIMD (measured 200 cycles per step against 68 of VALU issue).
     constexpr int GG = GMMIL_GG;   // (2: both features of a group share the swizzle of their group of four)
     f32x4 xa_[GG][RQ], ya_[GG], xb_[GG][RQ], yb_[GG];
     auto lds_group = [&](f32x4 (*xg)[RQ], f32x4* yg, int kb) {
@@ -338,182 +156,6 @@ __global__ __launch_bounds__(256) void k_gmmil_direct(il_batch pol, il_batch exp
 #pragma unroll
         for (int q = 0; q < RQ; ++q) xg[u][q] = *reinterpret_cast<const f32x4*>(&Xs[kb + u][(ti * RB + 4 * q) ^ sw]);
         yg[u] = *reinterpret_cast<const f32x4*>(&Ys[kb + u][(tj * 4) ^ sw]);
-      }
-    };
-    auto fma_group = [&](const f32x4 (*xg)[RQ], const f32x4* yg) {
-#pragma unroll
-      for (int u = 0; u < GG; ++u) {
-        const f32x2 y01 = {yg[u][0], yg[u][1]}, y23 = {yg[u][2], yg[u][3]};
-#pragma unroll
-        for (int a = 0; a < RB; ++a) {
-          const float xs = xg[u][a >> 2][a & 3];
-          const f32x2 xa = {xs, xs};
-          const f32x2 d0 = xa - y01, d1 = xa - y23;
-          acc2[a][0] = __builtin_elementwise_fma(d0, d0, acc2[a][0]);
-          acc2[a][1] = __builtin_elementwise_fma(d1, d1, acc2[a][1]);
-        }
-      }
-    };
-    lds_group(xa_, ya_, 0);
-#pragma unroll 1
-    for (int kb = 0; kb < GKC; kb += 2 * GG) {
-      lds_group(xb_, yb_, kb + GG);
-      __builtin_amdgcn_sched_barrier(0);
-      fma_group(xa_, ya_);
-      __builtin_amdgcn_sched_barrier(0);
-      lds_group(xa_, ya_, (kb + 2 * GG) & (GKC - 1));
-      __builtin_amdgcn_sched_barrier(0);
-      fma_group(xb_, yb_);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    __syncthreads();
-   }
-  }
-  float acc[RB][4];
-#pragma unroll
-  for (int a = 0; a < RB; ++a) { acc[a][0] = acc2[a][0][0]; acc[a][1] = acc2[a][0][1]; acc[a][2] = acc2[a][1][0]; acc[a][3] = acc2[a][1][1]; }
-  const float fD = (float)D;
-  const GmmilExp gex = gmmil_exp_consts(g1, g2, D);
-  if (MODE == 1) {
-    const int n2e = vs_self ? n1 : n2;
-#pragma unroll
-    for (int a = 0; a < RB; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const int i = it * GTR + ti * RB + a, j = jt * GT + tj * 4 + b;
-        if (i < n1 && j < n2e) dist_out[(size_t)i * n2e + j] = acc[a][b] / fD;
-      }
-    return;
-  }
-  sx = block_sum(sx, red);
-  sy = vs_self ? sx : block_sum(sy, red);
-  f32x4 wv;
-#pragma unroll
-  for (int b = 0; b < 4; ++b) { const int j = jt * GT + tj * 4 + b; wv[b] = j < ny ? yb.weights[(size_t)j * yb.ld_weights] / sy : 0.f; }
-  float* part = ws_ + w.part + ((size_t)mat * w.njt + jt) * w.b1p + it * GTR;
-#pragma unroll
-  for (int a = 0; a < RB; ++a) {
-    float s = 0.f;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) s += wv[b] * gmmil_pair_kernel(acc[a][b], gex);
-    s = group16_sum(s);
-    if (tj == 0) part[ti * RB + a] = s;
-  }
-  if (!out_r) return;
-  __shared__ unsigned last;
-  sync_drain_stores();
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned expect = (unsigned)(w.b2p / GT + w.b1p / GT);
-    unsigned* ctr = reinterpret_cast<unsigned*>(ws_ + w.ctr) + it * GCTR;
-    last = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT) + 1u == expect;
-    if (last) __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // zero again for the next call
-  }
-  __syncthreads();
-  if (last) sync_acquire_all();
-  if (!last || threadIdx.x >= GTR) return;
-  const int i = it * GTR + threadIdx.x;
-  if (i >= n1) return;
-  auto ordered_sum = [&](const float* p, int nq) {
-    float s = 0.f;
-    for (int q0 = 0; q0 < nq; q0 += 16) {
-      float v[16];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) v[u] = p[(size_t)min(q0 + u, nq - 1) * w.b1p];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) if (q0 + u < nq) s += v[u];
-    }
-    return s;
-  };
-  const float s0 = ordered_sum(ws_ + w.part + i, w.b2p / GT);
-  const float s1 = ordered_sum(ws_ + w.part + (size_t)w.njt * w.b1p + i, w.b1p / GT);
-  const float wi = pol.weights[(size_t)i * pol.ld_weights] / sx;
-  const float sim = wi * s0, self = wi * s1;
-  out_r[i] = sim - self;
-  if (out_sim) out_sim[i] = sim;
-  if (out_self) out_self[i] = self;
-}
-// ---------------------------------------------------------------------------------------------
-// k_gmmil_resident (round 5): k_gmmil_direct with the WHOLE feature range of both operand tiles resident in LDS (64 rows x D features each: 2 x 30 KB at Ant dims, two
-// workgroups per CU) instead of a ring of 32-feature chunks. The chunked form paid two workgroup barriers and a burst of transposing LDS stores per chunk - phases in which
-// the SIMDs issue no pair arithmetic - and its feature loop ran at ~64 % of the packed-op issue rate with two co-resident workgroups (profiles/r02_gmmil_timeline.md: 27.5k
-// ticks for 2 x 4 chunks of 2.2k). Here: every operand lane is requested up front (as before: D <= 128 always had all chunks in flight), stored transposed with the same
-// XOR swizzle, ONE barrier, then a barrier-free loop over all features with the LDS operands double-buffered in registers. The arrival of a tile's partial row sums is
-// fence-free (the pair-mode kernels' mechanism, mlp_tile.hpp): partials written THROUGH (sc0 sc1), stores drained, barrier, one relaxed ticket; the last arriver reads them
-// below the caches - no agent-scope release (an L2 write-back per workgroup) and no acquire. Same pair arithmetic in the same feature order, same 64-column partial sums,
-// same tile-ordered final sums: bit-identical to k_gmmil_direct / k_gmmil_pack + k_gmmil_tile.
-// ---------------------------------------------------------------------------------------------
-__host__ __device__ inline int gmmil_kp4(int D) { return (D + 3) & ~3; }
-static size_t gmmil_resident_lds(int D) { return ((size_t)gmmil_kp4(D) * (GTR + GT) + 64) * sizeof(float); }
-template <int MODE>
-__global__ __launch_bounds__(256) void k_gmmil_resident(il_batch pol, il_batch exp, int S, int D, float g1, float g2, float* __restrict__ ws_, float* __restrict__ dist_out, int self_second,
-                                                        float* __restrict__ out_r, float* __restrict__ out_sim, float* __restrict__ out_self, int lanes) {
-  constexpr int RB = GMMIL_RB, RQ = RB / 4, GG = GMMIL_GG;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  IL_ST_BEGIN(IL_ST_GMMIL);
-  const int KP = gmmil_kp4(D);
-  float* Xs = smem;                       // [KP][GTR], column r of feature k at (r ^ 4 ((k / 4) % 8))
-  float* Ys = Xs + (size_t)KP * GTR;      // [KP][GT]
-  float* red = Ys + (size_t)KP * GT;      // [32] block_sum scratch, [32] = "last arriver" flag
-  globalize(pol); globalize(exp);
-  const int n1 = pol.n, n2 = exp.n;
-  const GmmilWs w = gmmil_ws(n1, n2, D);
-  const int it = blockIdx.x, jt = blockIdx.y, mat = blockIdx.z;  // mat 0: policy vs expert, 1: policy vs policy
-  const bool vs_self = (mat == 1) || (MODE == 1 && self_second);
-  const int npy = vs_self ? w.b1p : w.b2p;
-  if (jt * GT >= npy) { IL_ST_END(IL_ST_GMMIL); return; }
-  const il_batch& yb = vs_self ? pol : exp;
-  const int ny = yb.n;
-  const int ti = threadIdx.x >> 4, tj = threadIdx.x & 15;
-  float sx = 0.f, sy = 0.f;
-  if (MODE == 0) {
-    for (int i = threadIdx.x; i < n1; i += blockDim.x) sx += pol.weights[(size_t)i * pol.ld_weights];
-    if (!vs_self) for (int i = threadIdx.x; i < ny; i += blockDim.x) sy += yb.weights[(size_t)i * yb.ld_weights];
-  }
-  // every 16-byte operand lane of both tiles, requested before anything is consumed (chunks of 32 features = 8 lanes along a row, like k_gmmil_direct); NCH chunks in registers
-  constexpr int PX4 = GKC * GTR / 4 / 256, PY4 = GKC * GT / 4 / 256, NCH = 5;   // D <= 160 (the launcher checks)
-  f32x4 xr[NCH][PX4], yr[NCH][PY4];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    if (c * GKC < D) {
-#pragma unroll
-      for (int u = 0; u < PX4; ++u) { const int i = threadIdx.x + u * 256, r = i >> 3, kq = i & 7; xr[c][u] = cat_lane(pol, S, D, min(it * GTR + r, n1 - 1), c * GKC + 4 * kq, lanes != 0); }
-#pragma unroll
-      for (int u = 0; u < PY4; ++u) { const int i = threadIdx.x + u * 256, r = i >> 3, kq = i & 7; yr[c][u] = cat_lane(yb, S, D, min(jt * GT + r, ny - 1), c * GKC + 4 * kq, lanes != 0); }
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    if (c * GKC < D) {
-#pragma unroll
-      for (int u = 0; u < PX4; ++u) {
-        const int i = threadIdx.x + u * 256, r = i >> 3, kq = i & 7, col = r ^ (4 * kq);
-        const bool rv = it * GTR + r < n1;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { const int k = c * GKC + 4 * kq + q; if (k < KP) Xs[(size_t)k * GTR + col] = (rv && k < D) ? xr[c][u][q] : 0.f; }
-      }
-#pragma unroll
-      for (int u = 0; u < PY4; ++u) {
-        const int i = threadIdx.x + u * 256, r = i >> 3, kq = i & 7, col = r ^ (4 * kq);
-        const bool rv = jt * GT + r < ny;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { const int k = c * GKC + 4 * kq + q; if (k < KP) Ys[(size_t)k * GT + col] = (rv && k < D) ? yr[c][u][q] : 0.f; }
-      }
-    }
-  }
-  __syncthreads();
-  f32x2 acc2[RB][2];
-#pragma unroll
-  for (int a = 0; a < RB; ++a) { acc2[a][0] = f32x2{0.f, 0.f}; acc2[a][1] = f32x2{0.f, 0.f}; }
-  {
-    f32x4 xa_[GG][RQ], ya_[GG], xb_[GG][RQ], yb_[GG];
-    auto lds_group = [&](f32x4 (*xg)[RQ], f32x4* yg, int kb) {   // (both features of a group of GG = 2 share the swizzle of their group of four)
-      const int sw = ((kb >> 2) & 7) << 2;
-#pragma unroll
-      for (int u = 0; u < GG; ++u) {
-#pragma unroll
-        for (int q = 0; q < RQ; ++q) xg[u][q] = *reinterpret_cast<const f32x4*>(&Xs[(size_t)(kb + u) * GTR + ((ti * RB + 4 * q) ^ sw)]);
-        yg[u] = *reinterpret_cast<const f32x4*>(&Ys[(size_t)(kb + u) * GT + ((tj * 4) ^ sw)]);
       }
     };
     auto fma_group = [&](const f32x4 (*xg)[RQ], const f32x4* yg) {
@@ -532,16 +174,18 @@ __global__ __launch_bounds__(256) void k_gmmil_resident(il_batch pol, il_batch e
     };
     lds_group(xa_, ya_, 0);
 #pragma unroll 1
-    for (int kb = 0; kb < KP; kb += 2 * GG) {   // features kb .. kb + 3 (features >= D are zeros on both sides: they add (0 - 0)^2)
+    for (int kb = 0; kb < GKC; kb += 2 * GG) {   // a rolled loop: unrolled, the copies do not share registers (296 VGPRs with four chunks in flight)
       lds_group(xb_, yb_, kb + GG);
       __builtin_amdgcn_sched_barrier(0);
       fma_group(xa_, ya_);
       __builtin_amdgcn_sched_barrier(0);
-      lds_group(xa_, ya_, min(kb + 2 * GG, KP - GG));   // (the last trip re-reads a group that is discarded instead of branching)
+      lds_group(xa_, ya_, (kb + 2 * GG) & (GKC - 1));   // the last trip re-reads group 0 (discarded) instead of branching
       __builtin_amdgcn_sched_barrier(0);
       fma_group(xb_, yb_);
       __builtin_amdgcn_sched_barrier(0);
     }
+    __syncthreads();
+   }
   }
   float acc[RB][4];
 #pragma unroll
@@ -572,23 +216,22 @@ __global__ __launch_bounds__(256) void k_gmmil_resident(il_batch pol, il_batch e
 #pragma unroll
     for (int b = 0; b < 4; ++b) s += wv[b] * gmmil_pair_kernel(acc[a][b], gex);
     s = group16_sum(s);
-    if (tj == 0) wstore1(part, ti * RB + a, s);   // written through: the row tile's last arriver reads it below the caches
+    if (tj == 0) part[ti * RB + a] = s;
   }
   if (!out_r) { IL_ST_END(IL_ST_GMMIL); return; }
-  // The row tile's reward needs the partial sums of every column tile of BOTH matrices: the workgroup that arrives last adds them up in tile order. Every wave drains its
-  // write-through stores, barrier, ONE relaxed ticket (no release: nothing of this workgroup that another one reads sits in a cache); the counter is left at zero.
-  unsigned* lastp = reinterpret_cast<unsigned*>(red + 32);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  // The row tile's reward needs the partial sums of every column tile of BOTH matrices: the workgroup that arrives last (one agent-scope release ticket per workgroup,
+  // after a barrier; only the last arriver pays for the acquire) adds them up in tile order - a separate, launch-bound "final" kernel cost 11 us.
+  __shared__ unsigned last;
+  sync_drain_stores();
   __syncthreads();
   if (threadIdx.x == 0) {
     const unsigned expect = (unsigned)(w.b2p / GT + w.b1p / GT);
     unsigned* ctr = reinterpret_cast<unsigned*>(ws_ + w.ctr) + it * GCTR;
-    const unsigned last = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == expect;
+    last = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT) + 1u == expect;
     if (last) __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // zero again for the next call
-    *lastp = last;
   }
   __syncthreads();
-  const bool last = *lastp != 0u;
+  if (last) sync_acquire_all();
   const int i = it * GTR + threadIdx.x;
   if (last && threadIdx.x < GTR && i < n1) {
     // all partials of a matrix requested before the first add (a dependent load-add chain is one fabric round trip per column tile); added in tile order
@@ -597,14 +240,14 @@ __global__ __launch_bounds__(256) void k_gmmil_resident(il_batch pol, il_batch e
       for (int q0 = 0; q0 < nq; q0 += 16) {
         float v[16];
 #pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = sload1(p, (int64_t)min(q0 + u, nq - 1) * w.b1p + i);
+        for (int u = 0; u < 16; ++u) v[u] = p[(size_t)min(q0 + u, nq - 1) * w.b1p];
 #pragma unroll
         for (int u = 0; u < 16; ++u) if (q0 + u < nq) s += v[u];
       }
       return s;
     };
-    const float s0 = ordered_sum(ws_ + w.part, w.b2p / GT);
-    const float s1 = ordered_sum(ws_ + w.part + (size_t)w.njt * w.b1p, w.b1p / GT);
+    const float s0 = ordered_sum(ws_ + w.part + i, w.b2p / GT);
+    const float s1 = ordered_sum(ws_ + w.part + (size_t)w.njt * w.b1p + i, w.b1p / GT);
     const float wi = pol.weights[(size_t)i * pol.ld_weights] / sx;
     const float sim = wi * s0, self = wi * s1;
     out_r[i] = sim - self;
@@ -613,10 +256,6 @@ __global__ __launch_bounds__(256) void k_gmmil_resident(il_batch pol, il_batch e
   }
   IL_ST_END(IL_ST_GMMIL);
 }
-static int gmmil_resident_on(int D) {   // IL_GMMIL_RESIDENT=0: the chunked k_gmmil_direct (developer A/B; same bits). D <= 160: five chunks of operand lanes in registers
-  static const int on = [] { const char* e = getenv("IL_GMMIL_RESIDENT"); return e && e[0] == '0' ? 0 : 1; }();
-  return on != 0 && D >= 4 && D <= 160;
-}
 template <class K>
 static int gmmil_ensure_lds(K fn, size_t bytes) {
   if (bytes <= 64 * 1024) return IL_OK;
@@ -624,7 +263,7 @@ static int gmmil_ensure_lds(K fn, size_t bytes) {
   return e == hipSuccess ? IL_OK : il_set_error(IL_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", bytes, hipGetErrorString(e));
 }
 // ---------------------------------------------------------------------------------------------
-// k_gmmil_sx (round 5): the pair arithmetic with the ROW operand in scalar registers. In k_gmmil_direct / _resident a thread's 4 x 4 pairs need two ds_read_b128 per
+// k_gmmil_sx (round 5): the pair arithmetic with the ROW operand in scalar registers. In k_gmmil_direct a thread's 4 x 4 pairs need two ds_read_b128 per
 // feature (its 4 rows, its 4 columns) for 16 packed instructions: with two workgroups per CU the LDS pipe (8 waves x 16 clocks per feature) is as busy as the SIMDs
 // (2 waves x 64 clocks): neither reaches its rate (round-2 timeline: 64 % of the packed-op issue rate; 8 x 4 blocks halve the reads but leave one wave per SIMD and
 // lose, profiles/r05_gmmil_rb8_ab.txt). Here a WAVE owns 4 rows x 256 columns: its rows' features are wave-uniform, so they come through the scalar cache
@@ -632,7 +271,7 @@ static int gmmil_ensure_lds(K fn, size_t bytes) {
 // instruction; the lane's 4 columns stay ONE ds_read_b128 per feature. Workgroup = 8 waves = 32 rows x 256 columns with all D features of the 256 columns resident in
 // LDS (120 KB at Ant dims: one workgroup per CU, two waves per SIMD, 256 workgroups at B = 1024). Same pair arithmetic in the same feature order, the same 64-column
 // partial sums (a 16-lane group = one 64-column tile), the same tile-ordered final sums, the weight sums by the first 256 threads in the old order: bit-identical.
-// Needs whole 16-byte lanes, S and D multiples of 8 (a group of 8 features never straddles states | actions) and D <= 156 (LDS); other shapes keep k_gmmil_resident.
+// Needs whole 16-byte lanes, S and D multiples of 8 (a group of 8 features never straddles states | actions) and D <= 156 (LDS); other shapes keep k_gmmil_direct.
 // ---------------------------------------------------------------------------------------------
 #define GSX_ROWS 32
 #define GSX_COLS 256
@@ -850,7 +489,7 @@ __global__ __launch_bounds__(512) void k_gmmil_sx(il_batch pol, il_batch exp, in
   }
   IL_ST_END(IL_ST_GMMIL);
 }
-static int gmmil_sx_on(int S, int A, int D, int state_only, int lanes) {   // IL_GMMIL_SX=0: k_gmmil_resident (developer A/B; same bits)
+static int gmmil_sx_on(int S, int A, int D, int state_only, int lanes) {   // IL_GMMIL_SX=0: k_gmmil_direct everywhere (developer A/B; same bits)
   static const int on = [] { const char* e = getenv("IL_GMMIL_SX"); return e && e[0] == '0' ? 0 : 1; }();
   return on != 0 && lanes && D >= 8 && D % 8 == 0 && S % 8 == 0 && gmmil_sx_lds(D) <= (size_t)160 * 1024 && D <= 5 * GKC;
 }
@@ -1106,7 +745,7 @@ __global__ __launch_bounds__(256) void k_gmmil_mfma(il_batch pol, il_batch exp, 
   }
   IL_ST_END(IL_ST_GMMIL);
 }
-static int gmmil_mfma_on(int D) {   // IL_GMMIL_MFMA=0: the direct-difference launches (k_gmmil_sx and the forms behind it)
+static int gmmil_mfma_on(int D) {   // IL_GMMIL_MFMA=0: the direct-difference launches (k_gmmil_sx, k_gmmil_direct)
   static const int on = [] { const char* e = getenv("IL_GMMIL_MFMA"); return e && e[0] == '0' ? 0 : 1; }();
   return on != 0 && D >= 1 && D <= 128;
 }
@@ -1145,7 +784,6 @@ static int gmmil_mfma_launch(const il_batch* pol, const il_batch* exp, int S, in
   return lanes && D >= 4 ? gmmil_mfma_launch_l<NKQ, true>(pol, exp, S, D, g1, g2, workspace, out_r, out_sim, out_self, st)
                          : gmmil_mfma_launch_l<NKQ, false>(pol, exp, S, D, g1, g2, workspace, out_r, out_sim, out_self, st);
 }
-static bool gmmil_direct() { static const int on = [] { const char* e = getenv("IL_GMMIL_DIRECT"); return e && e[0] == '0' ? 0 : 1; }(); return on != 0; }   // IL_GMMIL_DIRECT=0: k_gmmil_pack + k_gmmil_tile (developer A/B; same bits)
 static int gmmil_lanes(const il_batch* a, const il_batch* b, int S, int A, int state_only) {   // whole 16-byte lanes along the rows of both batches?
   auto ok = [&](const il_batch* x) {
     const bool st = (reinterpret_cast<uintptr_t>(x->states) & 15) == 0 && x->ld_states % 4 == 0 && S % 4 == 0;
@@ -1163,42 +801,26 @@ extern "C" int il_gmmil_reward(const il_batch* pol, const il_batch* exp, int32_t
   const GmmilWs w = gmmil_ws(pol->n, exp->n, D);
   if (workspace_floats < w.total) return il_set_error(IL_ERR_WORKSPACE, "il_gmmil_reward: workspace too small (%lld < %lld floats)", (long long)workspace_floats, (long long)w.total);
   hipStream_t st = (hipStream_t)stream_;
+  const int lanes = gmmil_lanes(pol, exp, S, A, state_only);
   if (gmmil_mfma_on(D)) {
-    const int lanes = gmmil_lanes(pol, exp, S, A, state_only);
     if (D <= 32) return gmmil_mfma_launch<2>(pol, exp, S, D, g1, g2, workspace, out_rewards, out_sim, out_self, lanes, st);
     if (D <= 64) return gmmil_mfma_launch<4>(pol, exp, S, D, g1, g2, workspace, out_rewards, out_sim, out_self, lanes, st);
     return gmmil_mfma_launch<8>(pol, exp, S, D, g1, g2, workspace, out_rewards, out_sim, out_self, lanes, st);
   }
-  if (gmmil_direct() && gmmil_sx_on(S, A, D, state_only, gmmil_lanes(pol, exp, S, A, state_only))) {
+  if (gmmil_sx_on(S, A, D, state_only, lanes)) {
     const size_t lds = gmmil_sx_lds(D);
     if (int rc = gmmil_ensure_lds(k_gmmil_sx<0>, lds)) return rc;
-    IL_TRACE("k_gmmil_tile", st);
+    IL_TRACE("k_gmmil_tile", st);   // (the trace name of the pair launch, whichever kernel runs it)
     k_gmmil_sx<0><<<dim3(w.b1p / GSX_ROWS, (w.njt * GT + GSX_COLS - 1) / GSX_COLS, 2), 512, lds, st>>>(*pol, *exp, S, D, g1, g2, workspace, nullptr, 0, out_rewards, out_sim, out_self);
-    IL_CHECK_LAUNCH("il_gmmil_reward");
-    return IL_OK;
-  }
-  if (gmmil_direct() && gmmil_resident_on(D)) {
-    const size_t lds = gmmil_resident_lds(D);
-    if (int rc = gmmil_ensure_lds(k_gmmil_resident<0>, lds)) return rc;
+  } else {
     IL_TRACE("k_gmmil_tile", st);
-    k_gmmil_resident<0><<<dim3(w.b1p / GTR, w.njt, 2), 256, lds, st>>>(*pol, *exp, S, D, g1, g2, workspace, nullptr, 0, out_rewards, out_sim, out_self, gmmil_lanes(pol, exp, S, A, state_only));
-    IL_CHECK_LAUNCH("il_gmmil_reward");
-    return IL_OK;
+    k_gmmil_direct<0><<<dim3(w.b1p / GTR, w.njt, 2), 256, 0, st>>>(*pol, *exp, S, D, g1, g2, workspace, nullptr, 0, out_rewards, out_sim, out_self, lanes);
   }
-  if (gmmil_direct() && D >= 4) {
-    IL_TRACE("k_gmmil_tile", st);
-    k_gmmil_direct<0><<<dim3(w.b1p / GTR, w.njt, 2), 256, 0, st>>>(*pol, *exp, S, D, g1, g2, workspace, nullptr, 0, out_rewards, out_sim, out_self, gmmil_lanes(pol, exp, S, A, state_only));
-    IL_CHECK_LAUNCH("il_gmmil_reward");
-    return IL_OK;
-  }
-  { IL_TRACE("k_gmmil_pack", st); k_gmmil_pack<<<dim3(w.b1p / GT + w.b2p / GT, (D + GKC - 1) / GKC), 256, 0, st>>>(*pol, *exp, S, D, workspace); }
-  { IL_TRACE("k_gmmil_tile", st); k_gmmil_tile<0><<<dim3(w.b1p / GTR, w.njt, 2), 256, 0, st>>>(pol->n, exp->n, D, g1, g2, workspace, nullptr, 0, out_rewards, out_sim, out_self); }
   IL_CHECK_LAUNCH("il_gmmil_reward");
   return IL_OK;
 }
 
-// distance matrix between a and b ([na][nb]); needs a workspace of il_gmmil_workspace_floats(na, nb, D) floats appended after `out`?
-// No: to keep the ABI allocation-free the caller passes the same kind of workspace as for il_gmmil_reward.
+// distance matrix between a and b ([na][nb]). To keep the ABI allocation-free the caller passes the same kind of workspace as for il_gmmil_reward.
 extern "C" int il_gmmil_sqdist(const il_batch* a, const il_batch* b, int32_t S, int32_t A, int32_t state_only, float* out, float* workspace,
                                   int64_t workspace_floats, il_stream_t stream_) {
   IL_NO_GATHER(a, "il_gmmil_sqdist"); IL_NO_GATHER(b, "il_gmmil_sqdist");
@@ -1207,34 +829,19 @@ extern "C" int il_gmmil_sqdist(const il_batch* a, const il_batch* b, int32_t S, 
   const GmmilWs w = gmmil_ws(a->n, b->n, D);
   if (workspace_floats < w.total) return il_set_error(IL_ERR_WORKSPACE, "il_gmmil_sqdist: workspace too small");
   hipStream_t st = (hipStream_t)stream_;
-  if (gmmil_direct() && gmmil_sx_on(S, A, D, state_only, gmmil_lanes(a, b, S, A, state_only))) {
+  const int lanes = gmmil_lanes(a, b, S, A, state_only);
+  if (gmmil_sx_on(S, A, D, state_only, lanes)) {
     const size_t lds = gmmil_sx_lds(D);
     if (int rc = gmmil_ensure_lds(k_gmmil_sx<1>, lds)) return rc;
     IL_TRACE("k_gmmil_tile", st);
     k_gmmil_sx<1><<<dim3(w.b1p / GSX_ROWS, (w.b2p + GSX_COLS - 1) / GSX_COLS, 1), 512, lds, st>>>(*a, *b, S, D, 0.f, 0.f, workspace, out, 0, nullptr, nullptr, nullptr);
-    IL_CHECK_LAUNCH("il_gmmil_sqdist");
-    return IL_OK;
-  }
-  if (gmmil_direct() && gmmil_resident_on(D)) {
-    const size_t lds = gmmil_resident_lds(D);
-    if (int rc = gmmil_ensure_lds(k_gmmil_resident<1>, lds)) return rc;
+  } else {
     IL_TRACE("k_gmmil_tile", st);
-    k_gmmil_resident<1><<<dim3(w.b1p / GTR, w.b2p / GT, 1), 256, lds, st>>>(*a, *b, S, D, 0.f, 0.f, workspace, out, 0, nullptr, nullptr, nullptr, gmmil_lanes(a, b, S, A, state_only));
-    IL_CHECK_LAUNCH("il_gmmil_sqdist");
-    return IL_OK;
+    k_gmmil_direct<1><<<dim3(w.b1p / GTR, w.b2p / GT, 1), 256, 0, st>>>(*a, *b, S, D, 0.f, 0.f, workspace, out, 0, nullptr, nullptr, nullptr, lanes);
   }
-  if (gmmil_direct() && D >= 4) {
-    IL_TRACE("k_gmmil_tile", st);
-    k_gmmil_direct<1><<<dim3(w.b1p / GTR, w.b2p / GT, 1), 256, 0, st>>>(*a, *b, S, D, 0.f, 0.f, workspace, out, 0, nullptr, nullptr, nullptr, gmmil_lanes(a, b, S, A, state_only));
-    IL_CHECK_LAUNCH("il_gmmil_sqdist");
-    return IL_OK;
-  }
-  { IL_TRACE("k_gmmil_pack", st); k_gmmil_pack<<<dim3(w.b1p / GT + w.b2p / GT, (D + GKC - 1) / GKC), 256, 0, st>>>(*a, *b, S, D, workspace); }
-  { IL_TRACE("k_gmmil_tile", st); k_gmmil_tile<1><<<dim3(w.b1p / GTR, w.b2p / GT, 1), 256, 0, st>>>(a->n, b->n, D, 0.f, 0.f, workspace, out, 0, nullptr, nullptr, nullptr); }
   IL_CHECK_LAUNCH("il_gmmil_sqdist");
   return IL_OK;
 }
 
-IL_STAMP_READER(il_debug_stamps_gmmil)
 IL_ST_READER(il_stamps_gmmil)
 IL_TL_READER(il_debug_timeline_gmmil)

@@ -603,7 +603,7 @@ class DeepGAILDiscriminator(GAILDiscriminator):
 
 
 class GMMILDiscriminator(nn.Module):
-  """Kernel-mean-embedding reward (reference models.py:183-201); O(B^2 D) pair work runs in k_gmmil_tile."""
+  """Kernel-mean-embedding reward (reference models.py:183-201); O(B^2 D) pair work runs in one launch of csrc/gmmil.hip (k_gmmil_mfma for D <= 128)."""
 
   def __init__(self, state_size: int, action_size: int, imitation_cfg):
     super().__init__()

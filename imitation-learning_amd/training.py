@@ -394,7 +394,7 @@ def _sa_batch(state, action, weight):
 
 
 def embedding_sqdist(x: Tensor, y: Tensor) -> Tensor:
-  """models.py:25-29 `_squared_distance` between two sets of feature rows [n1, D], [n2, D] -> [n1, n2] (k_gmmil_tile, direct form)."""
+  """models.py:25-29 `_squared_distance` between two sets of feature rows [n1, D], [n2, D] -> [n1, n2] (il_gmmil_sqdist: the direct-difference kernels k_gmmil_sx / k_gmmil_direct)."""
   n1, n2, D = x.size(0), y.size(0), x.size(1)
   dev = x.device
   st = _lib.stream_ptr()   # (the workspace is keyed by the stream the launch goes to, not by torch's current stream: they differ when the caller passes a stream of its own)
@@ -444,7 +444,7 @@ class UpdatePlan:
   [behavioural-cloning auxiliary step] -> SAC update.  The reward step is
     SAC / PWIL  none (PWIL stores its rewards online, train.py:156),
     GAIL        discriminator step + reward relabel (two streams, device-side hand-off; see `_run_update`),
-    GMMIL       k_gmmil_tile on the two batches (bandwidths frozen by the first, eager, update: models.py:193-195),
+    GMMIL       il_gmmil_reward on the two batches (bandwidths frozen by the first, eager, update: models.py:193-195),
     RED         predictor / target forward (eval mode),   DRIL  5-member Monte-Carlo-dropout uncertainty (Philox counter on the device),
     AdRIL/SQIL  k_mix_relabel with the per-update scalars (round, trajectory count, balanced alternation) read from a device buffer (`relabel_args`),
   preceded by `mix_expert_agent_transitions` when imitation.mix_expert_data = mixed_batch (train.py:183; GAIL with mixing keeps the per-function path).

@@ -1,6 +1,6 @@
-"""Developer tool: A/B of k_gmmil_tile builds (same ABI, IL_HIP_LIBRARY selects the build). GMMIL.predict_reward at B = 1024, Ant dims, plus a ragged size;
+"""Developer tool: A/B of builds of the GMMIL reward launch (trace name k_gmmil_tile, whichever kernel of csrc/gmmil.hip runs it; same ABI, IL_HIP_LIBRARY selects the build). GMMIL.predict_reward at B = 1024, Ant dims, plus a ragged size;
 prints per-kernel average durations (HIP events on the launch stream, il_trace_*) and a digest of the rewards, which must not depend on the build
-(every variant keeps each pair's accumulation order over the features and the 64-column partial sums).
+(every direct-difference variant keeps each pair's accumulation order over the features and the 64-column partial sums; compare under IL_GMMIL_MFMA=0).
   IL_HIP_LIBRARY=imitation-learning_amd/csrc/build/ab/libil_hip_<v>.so python profiles/tools/gmmil_ab.py"""
 import ctypes as C
 import hashlib

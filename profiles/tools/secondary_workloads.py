@@ -1,5 +1,5 @@
 """Developer tool: runs the non-headline kernels for a rocprofv3 --kernel-trace pass:
-  gmmil       GMMIL.predict_reward at B = 1024, Ant dims (k_gmmil_pack / k_gmmil_tile), 300 calls
+  gmmil       GMMIL.predict_reward at B = 1024, Ant dims (k_gmmil_mfma; IL_GMMIL_MFMA=0: k_gmmil_sx), 300 calls
   pwil        PWIL compute_reward against 25,000 atoms, D = 24, T = 1000 (k_pwil_select / k_pwil_merge), 1,100 steps incl. a reset
   population  BatchedPopulationPlan, L learners (the *_pop launches), 40 eager updates
 Usage: rocprofv3 --kernel-trace --stats -d gpurun_out/prof_x -o x -- python profiles/tools/secondary_workloads.py gmmil|pwil|population [L]"""
@@ -17,7 +17,7 @@ if what == 'gmmil':
   w = torch.ones(Bg, device=dev)
   gm = il.GMMILDiscriminator(Sg, Ag, bench.Cfg(state_only=False))
   for _ in range(300): gm.predict_reward(xs, xa, es, ea, w, w)
-elif what == 'gmmil_rate':   # calls/s + the kernel's duration from its launch stamps (il_kernel_stamps): IL_GMMIL_RESIDENT / IL_GMMIL_DIRECT select the form
+elif what == 'gmmil_rate':   # calls/s + the kernel's duration from its launch stamps (il_kernel_stamps, every GMMIL kernel writes them): IL_GMMIL_MFMA / IL_GMMIL_SX select the form
   import time, hashlib
   from imitation_learning_amd import _lib
   rs = np.random.RandomState(5)

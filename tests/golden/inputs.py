@@ -7,6 +7,8 @@ Shapes follow SURVEY.md §8(d): D4RL-shaped transitions with an absorbing bit.
 """
 from __future__ import annotations
 
+import functools
+
 import numpy as np
 
 f32 = np.float32
@@ -162,6 +164,26 @@ def gmmil_case(seed, B1, B2, D, weighted=True):
   w = rs.uniform(0.5, 1.5, B1).astype(f32) if weighted else np.ones(B1, f32)
   we = rs.uniform(0.5, 1.5, B2).astype(f32) if weighted else np.ones(B2, f32)
   return X, E, w, we
+
+
+# (n1, n2, D, S) where only the direct-difference GMMIL kernels serve: D > 128 with rows that are not whole 16-byte lanes and ragged tiles; the largest D of the scalar-row
+# kernel (11 column tiles of 64); D < 4; D = 1 (state only: D == S)
+GMMIL_DIRECT_SHAPES = ((130, 257, 132, 124), (40, 700, 152, 144), (70, 33, 3, 2), (40, 50, 1, 1))
+
+
+@functools.lru_cache(maxsize=None)
+def gmmil_float64_case(n1, n2, D, S):
+  """One of GMMIL_DIRECT_SHAPES with its float64 results, computed once per process and read-only: the inputs, the median bandwidths rounded to float32 (what the kernels
+  are given), the distance matrix, both similarities."""
+  X, E, w, we = gmmil_case(41, n1, n2, D, weighted=True)
+  d64 = lambda a, b: ((a.astype(np.float64)[:, None, :] - b.astype(np.float64)[None, :, :]) ** 2).mean(2)
+  dxe, dxx, dee = d64(X, E), d64(X, X), d64(E, E)
+  g1, g2 = float(f32(1.0 / (np.median(dxe) + 1e-8))), float(f32(1.0 / (np.median(dee) + 1e-8)))
+  wn, wen = w.astype(np.float64) / w.astype(np.float64).sum(), we.astype(np.float64) / we.astype(np.float64).sum()
+  sim64 = sum(wn * (np.exp(-gm * dxe) @ wen) for gm in (g1, g2)); self64 = sum(wn * (np.exp(-gm * dxx) @ wn) for gm in (g1, g2))
+  out = dict(X=X, E=E, w=w, we=we, g1=g1, g2=g2, dxe=dxe, dxx=dxx, sim64=sim64, self64=self64)
+  for k in ('dxe', 'dxx', 'sim64', 'self64'): out[k].setflags(write=False)   # (the inputs become tensors, which torch wants writable; nothing writes to them)
+  return out
 
 
 def pwil_case(seed, N, D, steps):

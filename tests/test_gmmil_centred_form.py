@@ -52,3 +52,18 @@ def test_centred_gram_form_keeps_the_direct_forms_accuracy_and_the_plain_gram_fo
   assert e_centred <= 3 * e_direct + 1e-3 * bound
   if offset >= 50:
     assert e_plain > bound, e_plain / bound   # what the offset costs the uncentred product
+
+
+@pytest.mark.parametrize('dims', gi.GMMIL_DIRECT_SHAPES)
+def test_float32_direct_form_is_inside_the_bounds_its_kernels_are_tested_at(dims):
+  """tests/test_gpu_parity.py::test_gmmil_direct_form_matches_float64_outside_the_mfma_range compares k_gmmil_sx / k_gmmil_direct with float64 at 1e-5 max|similarity| and
+  the distance matrix at rtol 1e-5 + 2e-6 of its largest entry. Here the same comparison for the numpy float32 direct evaluation of the same inputs: the number format
+  meets those bounds with room to spare (a tenth), at D = 152 as at D = 1, so a kernel that misses them has a fault of its own."""
+  c = gi.gmmil_float64_case(*dims)
+  X, E = c['X'], c['E']
+  dxe, dxx = _direct(X, E, f32), _direct(X, X, f32)
+  r32, s32 = _rewards(dxe, dxx, c['w'], c['we'], c['g1'], c['g2'], f32)
+  bound = 1e-5 * np.abs(c['sim64']).max()
+  assert np.abs(s32 - c['sim64']).max() <= 0.1 * bound and np.abs(r32 - (c['sim64'] - c['self64'])).max() <= 0.1 * bound and np.abs((s32 - r32) - c['self64']).max() <= 0.1 * bound
+  for d32, d64 in ((dxe, c['dxe']), (dxx, c['dxx'])):
+    assert (np.abs(d32 - d64) <= 0.1 * (1e-5 * np.abs(d64) + 2e-6 * np.abs(d64).max())).all()

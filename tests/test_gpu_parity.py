@@ -430,6 +430,30 @@ def test_gmmil_centred_gram_form_is_as_close_to_float64_as_the_direct_form(dims,
   assert np.abs(N(r) - (sim64 - self64)).max() <= bound, np.abs(N(r) - (sim64 - self64)).max() / bound
 
 
+@pytest.mark.parametrize('dims', gi.GMMIL_DIRECT_SHAPES)
+def test_gmmil_direct_form_matches_float64_outside_the_mfma_range(dims):
+  """The direct-difference kernels where they serve real calls, against float64 at the bound of the other GMMIL tests (1e-5 max|similarity|): the reward for D > 128 -
+  k_gmmil_direct at D = 132 (rows that are not whole 16-byte lanes, ragged tiles), k_gmmil_sx at its largest D (152, 11 column tiles) - and the distance matrix behind the
+  bandwidth medians at every shape, D = 3 and D = 1 (state only) among them: k_gmmil_direct's element-wise operand loads with fewer features than one 16-byte lane (their
+  rewards are k_gmmil_mfma's unless IL_GMMIL_MFMA=0). Three calls each (self-resetting arrival counters). The numpy float32 direct evaluation is inside the same bounds
+  (tests/test_gmmil_centred_form.py), so the bound is the format's, not these kernels'."""
+  n1, n2, D, S = dims
+  c = gi.gmmil_float64_case(*dims)
+  X, E, sim64, self64 = c['X'], c['E'], c['sim64'], c['self64']
+  disc = il.GMMILDiscriminator(S, max(D - S, 1), Cfg(state_only=D == S))
+  disc.gamma_1, disc.gamma_2 = c['g1'], c['g2']
+  act = lambda M: T(M[:, S:]) if D > S else T(np.zeros((M.shape[0], 1), np.float32))
+  args = (T(X[:, :S]), act(X), T(E[:, :S]), act(E))
+  for _ in range(3):
+    r, sim, self_sim = il_training.gmmil_predict_reward(disc, *args, T(c['w']), T(c['we']), return_parts=True)
+  bound = 1e-5 * np.abs(sim64).max()
+  errs = [np.abs(N(sim) - sim64).max() / bound, np.abs(N(self_sim) - self64).max() / bound, np.abs(N(r) - (sim64 - self64)).max() / bound]
+  print(f'gmmil direct form {dims}: |sim|, |self|, |reward| errors / bound = {errs[0]:.3e}, {errs[1]:.3e}, {errs[2]:.3e}')
+  assert max(errs) <= 1, errs
+  close(N(il_training.gmmil_sqdist(disc, *args)), c['dxe'], 'sqdist')
+  close(N(il_training.gmmil_sqdist(disc, args[0], args[1], args[0], args[1])), c['dxx'], 'self sqdist')
+
+
 GMMIL_FORMS_WORKER = r'''
 import hashlib, sys
 sys.path[:0] = [sys.argv[1], sys.argv[1] + '/tests', sys.argv[1] + '/tests/golden']
@@ -453,16 +477,17 @@ print('DIGEST', h.hexdigest())
 
 
 def test_gmmil_launch_forms_are_bit_identical(tmp_path):
-  """k_gmmil_sx (round 5: the row operand in scalar registers, 32 x 256 pairs per workgroup), k_gmmil_resident (all features of both tiles resident in LDS, fence-free arrival),
-  k_gmmil_direct (chunked ring) and k_gmmil_pack + k_gmmil_tile keep every
-  pair's accumulation order over the features, the 64-column partial sums and the tile-ordered final sums: the same bits for rewards, both similarities and the distance
-  matrix, at the timed size, for ragged shapes, for rows that are not whole 16-byte lanes and for D > 128. (The switches are read once per process: one process per form.)"""
+  """The two direct-difference forms - k_gmmil_sx (the row operand in scalar registers, 32 x 256 pairs per workgroup) and k_gmmil_direct (64 x 64 pairs, feature chunks
+  through a register ring) - keep every pair's accumulation order over the features, the 64-column partial sums and the tile-ordered final sums: the same bits for rewards,
+  both similarities and the distance matrix. The default chain under IL_GMMIL_MFMA=0 (k_gmmil_sx where eligible: the timed size, the small shape, ragged with D % 8 == 0
+  and its largest D; k_gmmil_direct for the ragged shape whose rows are not whole 16-byte lanes and for D = 132) against k_gmmil_direct everywhere (IL_GMMIL_SX=0).
+  (The switches are read once per process: one process per form.)"""
   import subprocess, sys
   script = tmp_path / 'forms.py'
   script.write_text(GMMIL_FORMS_WORKER)
   root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
   digests = {}
-  for name, env in (('scalar rows', {}), ('resident', dict(IL_GMMIL_SX='0')), ('direct', dict(IL_GMMIL_SX='0', IL_GMMIL_RESIDENT='0')), ('pack+tile', dict(IL_GMMIL_DIRECT='0'))):
+  for name, env in (('scalar rows where eligible', {}), ('direct everywhere', dict(IL_GMMIL_SX='0'))):
     r = subprocess.run([sys.executable, str(script), root], env=dict(os.environ, IL_GMMIL_MFMA='0', **env), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     digests[name] = [l for l in r.stdout.splitlines() if l.startswith('DIGEST')][-1].split()[1]

@@ -407,7 +407,8 @@ GPU_BODIES = (
     'test_device_beta_draws_are_beta_distributed',
     'test_bc_update_matches_oracle_and_reference', 'test_actor_act_matches_oracle', 'test_adam_and_polyak_kernels',
     'test_gail_update_matches_oracle_and_reference', 'test_gail_loss_variants_match_reference', 'test_gail_ragged_batch_and_state_only',
-    'test_gmmil_matches_oracle_and_reference', 'test_gmmil_full_size_properties', 'test_gmmil_centred_gram_form_is_as_close_to_float64_as_the_direct_form', 'test_pwil_matches_oracle_and_reference', 'test_pwil_every_launch_path_matches_oracle',
+    'test_gmmil_matches_oracle_and_reference', 'test_gmmil_full_size_properties', 'test_gmmil_centred_gram_form_is_as_close_to_float64_as_the_direct_form',
+    'test_gmmil_direct_form_matches_float64_outside_the_mfma_range', 'test_pwil_matches_oracle_and_reference', 'test_pwil_every_launch_path_matches_oracle',
     'test_reward_relabeller_bit_exact', 'test_mix_expert_agent_transitions_bit_exact',
     'test_red_matches_reference', 'test_dril_matches_reference', 'test_every_shipped_red_dril_shape_runs_at_ant_dims', 'test_dril_onchip_masks_are_bernoulli_and_change_per_call',
     'test_general_shape_tile_engine_matches_oracle_at_block_batches',
