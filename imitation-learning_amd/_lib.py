@@ -98,6 +98,10 @@ class Epoch(C.Structure):   # il_epoch: a device-resident epoch of expert batche
   _fields_ = [('cursor', C.c_void_p), ('n_batches', C.c_int64), ('noise_base', C.c_uint32)]
 
 
+class ActLearner(C.Structure):   # il_act_learner: one learner of il_act_step_population (a device array of these)
+  _fields_ = [('actor', C.c_void_p), ('mailbox', C.c_void_p), ('carry', C.c_void_p), ('ring', C.c_void_p), ('ring_state', C.c_void_p), ('noise_seed', C.c_uint64)]
+
+
 class SampleArgs(C.Structure):
   _fields_ = [('state', C.c_void_p),
               ('ring_state_a', C.c_void_p), ('ring_a', C.c_void_p), ('capacity_a', C.c_int64), ('row_floats_a', C.c_int32), ('idx_a', C.c_void_p), ('rows_a', C.c_void_p),
@@ -186,6 +190,7 @@ _SIGNATURES = {
     'il_batch_mix_relabel_dyn': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P]),
     'il_act_mailbox_floats': (C.c_int32, [C.c_int32, C.c_int32]),
     'il_act_step': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, C.c_int64, _P]),
+    'il_act_step_population': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     'il_act_publish': (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P]),
     'il_disc_workspace_floats': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     'il_gail_disc_step': (C.c_int, [C.POINTER(Disc), C.POINTER(Batch), C.POINTER(Batch), _P, C.POINTER(GailExtra), C.c_uint32, _P]),

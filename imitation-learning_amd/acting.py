@@ -18,6 +18,10 @@ Schedules:
             the append and the publish ride in the update's stream / hipGraph (UpdatePlan.pre_hooks / post_hooks). The behaviour
             policy lags the learner by one to two updates (what a host-side actor mirror would do).
 
+Population (`PopulationActingWorker`): L learners of one fused actor shape (a seed sweep in one process) step in lockstep through `il_act_step_population` - ONE launch
+of L workgroups and one wait for L echoes per act / append / step, instead of L launches and L turn-arounds. Every learner keeps its own mailbox, carry, ring, cursor,
+Philox seed and offset; a learner with nothing to do in a launch idles (it gets its echo, nothing else of it is touched).
+
 PWIL (`ActingWorker(..., reward_model=PWILDiscriminator)`): the reward of a transition is the greedy coupling of its (state, action) against the expert atoms
 (models.py:216-249), which the per-function loop computes with a launch and a `.item()` per step. Here every launch that appends is preceded, on the same stream, by ONE
 coupling launch (`il_pwil_act_reward`) that reads the pending transition where the append reads it, leaves the reward in the carry and - at an episode end - sets the
@@ -35,6 +39,7 @@ from . import _lib
 
 PENDING, WRAP_ABSORBING, GREEDY, NO_ACTION, CARRY_FROM_MAILBOX, REWARD_ON_DEVICE = 1, 2, 4, 8, 16, 32  # IL_ACT_* (include/il_hip.h)
 _HEADER = 8
+_NOISE_OFFSET = 6   # ACT_MAIL_NOISE_OFFSET (csrc/act_mail.hpp): il_act_step_population reads the learner's Philox offset here, as raw uint32 bits
 _SEQ_MOD = 1 << 17  # the commit word (sequence * 64 + flags) travels as fp32: < 2^23
 
 
@@ -97,7 +102,8 @@ def general_one_launch(actor) -> bool:
 class ActingWorker:
   """One environment worker feeding one `ReplayMemory` from one `SoftActor` (train.py:151-168)."""
 
-  def __init__(self, actor, memory, mirror: bool = False, reward_model=None):
+  def __init__(self, actor, memory, mirror: bool = False, reward_model=None, noise_seed=None):
+    """`noise_seed`: the Philox seed of this worker's samples (default: torch.initial_seed()) - several workers in one process, one per learner of a sweep, take distinct ones."""
     assert _lib.on_device(actor.flat) and _lib.on_device(memory.ring), 'ActingWorker needs the actor and the ring on the GPU (there is no CPU path)'
     assert actor.state_size == memory.state_size and actor.action_size == memory.action_size
     self.general = bool(getattr(actor, 'general', False))
@@ -118,7 +124,7 @@ class ActingWorker:
     dev = memory.ring.device
     self.carry = torch.zeros(self.S + self.A + 4, dtype=torch.float32, device=dev)
     self._seq = 0   # one sequence for both mailboxes: the device de-duplicates appends by commit word
-    self._seed = C.c_uint64(torch.initial_seed() & (2**64 - 1))
+    self._seed = C.c_uint64((torch.initial_seed() if noise_seed is None else int(noise_seed)) & (2**64 - 1))
     self._fixed = {}
     self._pending_seq = None
     self._workspace = None
@@ -259,3 +265,176 @@ class ActingWorker:
     plan.pre_hooks.append(self.enqueue_append)
     plan.post_hooks.append(self.enqueue_publish)
     return self
+
+
+class _MailboxBlock:
+  """Host view of L il_act_step mailboxes as ONE pinned [L, floats] block: a post is a few vectorised numpy writes, payload first, the L commit words last."""
+
+  def __init__(self, L: int, S: int, A: int):
+    n = int(_lib.lib().il_act_mailbox_floats(S, A))
+    self.tensor = torch.zeros(L, n, dtype=torch.float32, pin_memory=True)
+    self.host = self.tensor.numpy()
+    self.bits = self.host.view(np.uint32)
+    Sp, Ap = (S + 3) & ~3, (A + 3) & ~3
+    self.L, self.S, self.A, self.floats = L, S, A, n
+    self.o_next, self.o_obs, self.o_act = _HEADER, _HEADER + Sp, _HEADER + 2 * Sp
+    self.o_echo = self.o_act + Ap
+    assert self.o_echo < n
+    self.host[:, self.o_echo] = -1.0
+    self.echo = self.host[:, self.o_echo]
+    self.words = None   # commit words of the last post
+
+  def commit(self, seq: int, flags: np.ndarray) -> np.ndarray:
+    self.words = (seq * 64 + flags).astype(np.float32)
+    self.host[:, 0] = self.words
+    return self.words
+
+  def wait(self, what: str, timeout_s: float = 10.0):
+    echo, words, spins, t0 = self.echo, self.words, 0, 0.0
+    while not np.array_equal(echo, words):
+      spins += 1
+      if spins == 1:
+        t0 = time.perf_counter()
+      elif spins & 0xFFF == 0 and time.perf_counter() - t0 > timeout_s:
+        torch.cuda.synchronize()  # surfaces an asynchronous launch failure, if that is what happened
+        missing = [l for l in range(self.L) if echo[l] != words[l]]
+        raise RuntimeError(f'{what}: no echo from the device after {timeout_s:.0f} s for learner(s) {missing} (commit words {words[missing].tolist()}, mailboxes hold {echo[missing].tolist()})')
+
+
+def _rows(xs, rows, width: int) -> np.ndarray:
+  return np.stack([_row(xs[l])[:width] for l in rows])
+
+
+class PopulationActingWorker:
+  """L environment workers of one shape - L `SoftActor`s feeding L `ReplayMemory`s - whose device work per lockstep environment step is ONE launch
+  (`il_act_step_population`: workgroup l = learner l's `il_act_step`). `act` / `append` / `step` are `ActingWorker`'s exact and fused schedules over lists (entry l belongs to
+  learner l); a `None` entry makes that learner idle in the launch. Every learner's `actor._act_calls`, `memory.idx / full / num_trajectories`, ring and cursor end up
+  where its own `ActingWorker(actor, memory, noise_seed=noise_seeds[l])` would have left them. Fused actor shapes only (depth 2, ReLU, hidden 64..256 in multiples of 64);
+  no mirror / overlap schedule and no PWIL reward model."""
+
+  def __init__(self, actors, memories, noise_seeds, reward_models=None):
+    actors, memories, noise_seeds = list(actors), list(memories), [int(s) for s in noise_seeds]
+    if reward_models is not None and any(r is not None for r in (reward_models if isinstance(reward_models, (list, tuple)) else [reward_models])):
+      raise NotImplementedError('PopulationActingWorker: no PWIL reward model (IL_ACT_REWARD_ON_DEVICE needs a coupling launch per learner in front of the append: one ActingWorker per learner)')
+    L = len(actors)
+    assert L >= 1 and len(memories) == L and len(noise_seeds) == L, 'PopulationActingWorker: one memory and one noise seed per actor'
+    a0, m0 = actors[0], memories[0]
+    if any(getattr(a, 'general', False) for a in actors):
+      raise NotImplementedError('PopulationActingWorker: actor shapes outside depth 2 / ReLU / hidden 64..256 in multiples of 64 / action_size <= 8 have no population launch (one ActingWorker per learner)')
+    for a, m in zip(actors, memories):
+      assert _lib.on_device(a.flat) and _lib.on_device(m.ring), 'PopulationActingWorker needs the actors and the rings on the GPU (there is no CPU path)'
+      assert (a.state_size, a.action_size, a.hidden) == (a0.state_size, a0.action_size, a0.hidden) and (m.state_size, m.action_size) == (a0.state_size, a0.action_size), 'PopulationActingWorker: one shape for all learners'
+      assert m.ring.device == m0.ring.device and a.flat.device == a0.flat.device
+    self.actors, self.memories, self.L = actors, memories, L
+    self.S, self.A, self.H = m0.state_size, m0.action_size, a0.hidden
+    self.device = m0.ring.device
+    self._seeds = noise_seeds
+    self.carry = torch.zeros(L, self.S + self.A + 4, dtype=torch.float32, device=self.device)
+    self.eval_carry = torch.zeros(L, self.S + self.A + 4, dtype=torch.float32, device=self.device)   # evaluation acts between two fused steps: never the carry of a transition in flight
+    self._act_box, self._append_box, self._eval_box = _MailboxBlock(L, self.S, self.A), _MailboxBlock(L, self.S, self.A), _MailboxBlock(L, self.S, self.A)
+    self._seq = 0   # one sequence for the act and the append mailboxes: the device de-duplicates appends by commit word
+    self._eval_seq = 0   # the evaluation mailboxes never post PENDING: a sequence of their own, so no number of evaluation launches between two appends can bring a learner's consumed word round again
+    self._descs = {id(box): self._descriptors(box, carry) for box, carry in ((self._act_box, self.carry), (self._append_box, self.carry), (self._eval_box, self.eval_carry))}
+    self._absorbing = np.array([bool(m.absorbing) for m in memories])
+    self._all = list(range(L))
+
+  def _descriptors(self, box: _MailboxBlock, carry: torch.Tensor) -> torch.Tensor:
+    """The il_act_learner array of one role, uploaded once (every pointer is stable for the life of the worker)."""
+    from .training import _device_array
+    base, stride = box.tensor.data_ptr(), box.floats * 4
+    return _device_array([_lib.ActLearner(a.flat.data_ptr(), base + l * stride, carry[l].data_ptr(), m.ring.data_ptr(), m._ring_state.data_ptr(), s & (2**64 - 1))
+                          for l, (a, m, s) in enumerate(zip(self.actors, self.memories, self._seeds))], self.device)
+
+  def _launch(self, box: _MailboxBlock):
+    rc = _lib.lib().il_act_step_population(_lib.ptr(self._descs[id(box)]), self.L, self.S, self.A, self.H, torch.cuda.current_stream().cuda_stream)
+    if rc: _lib.check(rc)
+
+  def _next_seq(self) -> int:
+    self._seq = self._seq % (_SEQ_MOD - 1) + 1
+    return self._seq
+
+  def _next_eval_seq(self) -> int:
+    self._eval_seq = self._eval_seq % (_SEQ_MOD - 1) + 1
+    return self._eval_seq
+
+  def _post_act(self, box: _MailboxBlock, obs, flags: np.ndarray):
+    """Observation and Philox offset of every learner that acts (flags without NO_ACTION); counts the act in its actor, as SoftActor._act does."""
+    rows = [l for l in self._all if not flags[l] & NO_ACTION]
+    if rows:
+      box.host[rows, box.o_obs:box.o_obs + self.S] = _rows(obs, rows, self.S)
+      calls = []
+      for l in rows:
+        a = self.actors[l]
+        a._act_calls += 1   # the Philox offset is shared with SoftActor._act, so the two entry points never reuse noise
+        calls.append(a._act_calls & 0xFFFFFFFF)
+      box.bits[rows, _NOISE_OFFSET] = calls
+
+  def _post_transition(self, box: _MailboxBlock, rows, step, next_obs, reward, terminal, timeout):
+    if rows:
+      box.host[rows, 2:6] = np.array([(float(reward[l]), float(bool(terminal[l])), float(bool(timeout[l])), float(step[l] if np.ndim(step) else step)) for l in rows], dtype=np.float32)
+      box.host[rows, box.o_next:box.o_next + self.S] = _rows(next_obs, rows, self.S)
+
+  def _mirror_appends(self, rows, terminal, timeout, wrap):
+    for l in rows:
+      m = self.memories[l]
+      m._advance(bool(terminal[l]), bool(timeout[l]))
+      if wrap[l]: m._advance(False, False)
+
+  def _collect(self, box: _MailboxBlock) -> torch.Tensor:
+    box.wait('il_act_step_population')
+    return torch.from_numpy(box.host[:, box.o_act:box.o_act + self.A].copy())
+
+  def _transition_flags(self, next_obs, terminal, timeout):
+    rows = [l for l in self._all if next_obs[l] is not None]
+    wrap = np.zeros(self.L, dtype=bool)
+    for l in rows:
+      wrap[l] = self._absorbing[l] and bool(terminal[l]) and not bool(timeout[l])
+    flags = np.zeros(self.L, dtype=np.int64)
+    flags[rows] = PENDING
+    flags[wrap] |= WRAP_ABSORBING
+    return rows, wrap, flags
+
+  # --- exact schedule
+  def act(self, obs, greedy: bool = False, _box=None) -> torch.Tensor:
+    """`actor_l(obs[l]).sample()` (or the greedy action) for every learner as one [L, A] CPU tensor, remembering (obs, action) on the device for `append`. `obs[l] is None`:
+    learner l idles (its row of the result is whatever its mailbox last held)."""
+    box = _box or self._act_box
+    flags = np.array([NO_ACTION if o is None else (GREEDY if greedy else 0) for o in obs], dtype=np.int64)
+    assert len(flags) == self.L
+    self._post_act(box, obs, flags)
+    box.commit(self._next_eval_seq() if box is self._eval_box else self._next_seq(), flags)
+    self._launch(box)
+    return self._collect(box)
+
+  def append(self, step, next_obs, reward, terminal, timeout):
+    """`memory_l.append(...)` of the (state, action) of learner l's last `act`, plus its absorbing wrap at a true termination. Asynchronous: nothing is waited for.
+    `step`: one int for all learners or a list; `next_obs[l] is None`: learner l idles."""
+    box = self._append_box
+    if box.words is not None: box.wait('il_act_step_population(append)')   # normally already echoed: the act in between ran after it on the same stream
+    rows, wrap, flags = self._transition_flags(next_obs, terminal, timeout)
+    flags |= NO_ACTION
+    self._post_transition(box, rows, step, next_obs, reward, terminal, timeout)
+    box.commit(self._next_seq(), flags)
+    self._launch(box)
+    self._mirror_appends(rows, terminal, timeout, wrap)
+
+  # --- fused schedule
+  def step(self, step, next_obs, reward, terminal, timeout, obs=None, greedy: bool = False) -> torch.Tensor:
+    """append(transition of learner l's last action) + act(obs[l]) for every learner in ONE launch. `obs[l]` defaults to `next_obs[l]`; pass the reset observation where
+    the episode ended. `next_obs[l] is None`: learner l idles (no append, no action)."""
+    box = self._act_box
+    rows, wrap, flags = self._transition_flags(next_obs, terminal, timeout)
+    idle = [l for l in self._all if next_obs[l] is None]
+    flags[idle] = NO_ACTION
+    if greedy: flags[rows] |= GREEDY
+    self._post_transition(box, rows, step, next_obs, reward, terminal, timeout)
+    self._post_act(box, [None if next_obs[l] is None else (next_obs[l] if obs is None or obs[l] is None else obs[l]) for l in self._all], flags)
+    box.commit(self._next_seq(), flags)
+    self._launch(box)
+    self._mirror_appends(rows, terminal, timeout, wrap)
+    return self._collect(box)
+
+  # --- evaluation: the same kernel through a second descriptor set (own mailboxes, scratch carries, never PENDING)
+  def act_eval(self, obs) -> torch.Tensor:
+    """Greedy actions for the learners with an observation ([L, A]; the others idle), leaving the training carries and mailboxes alone."""
+    return self.act(obs, greedy=True, _box=self._eval_box)

@@ -130,6 +130,39 @@ def compose(overrides: List[str], config_dir: str = None) -> Config:
   return Config(cfg)
 
 
+def _split_sweep(value: str) -> List[str]:
+  """The comma list of one override (`1,2,3`); commas inside brackets, braces or quotes belong to a value (`[1,2]`)."""
+  parts, depth, quote, cur = [], 0, '', ''
+  for ch in value:
+    if quote:
+      quote = '' if ch == quote else quote
+    elif ch in '\'"':
+      quote = ch
+    elif ch in '([{':
+      depth += 1
+    elif ch in ')]}':
+      depth -= 1
+    if ch == ',' and depth == 0 and not quote:
+      parts.append(cur); cur = ''
+    else:
+      cur += ch
+  return parts + [cur]
+
+
+def compose_multirun(argv: List[str], config_dir: str = None):
+  """Hydra's basic sweeper (`python train.py -m seed=1,2,3 env=hopper,ant`): every override with a comma list is swept, the jobs are the Cartesian product of the lists in
+  the order of the command line with the LAST swept key varying fastest, numbered from 0. Returns (configs, overrides): the composed config of every job and the override
+  strings it was composed from (`-m` / `--multirun` dropped). `compose` itself keeps refusing `-m`."""
+  import itertools
+  overrides = [o for o in argv if o not in ('-m', '--multirun')]
+  choices = []
+  for o in overrides:
+    k, eq, v = o.partition('=')
+    choices.append([k + eq + part.strip() for part in _split_sweep(v)] if eq else [o])
+  jobs = [list(job) for job in itertools.product(*choices)]
+  return [compose(job, config_dir) for job in jobs], jobs
+
+
 def validate(cfg: Config):
   """The assertions of reference train.py:28-48."""
   assert cfg.algorithm in ALGORITHMS

@@ -1,10 +1,11 @@
 // The acting worker's device protocol (include/il_hip.h il_act_step: the contract; this header: the one place on the device side that knows the layout). Shared by
-// k_act_step (sac.hip), k_act_step_general / k_act_commit_general (general.hip) and k_pwil_couple (pwil.hip).
+// k_act_step / k_act_step_population (sac.hip), k_act_step_general / k_act_commit_general (general.hip) and k_pwil_couple (pwil.hip).
 #pragma once
 #include "il_common.hpp"
 
 // ---- mailbox (pinned host memory): IL_MAIL_HEADER words, then next_state | observation | action | echo, the vectors padded to 4 floats ----
-enum { ACT_MAIL_COMMIT = 0, ACT_MAIL_REWARD = 2, ACT_MAIL_TERMINAL = 3, ACT_MAIL_TIMEOUT = 4, ACT_MAIL_STEP = 5 };   // ([TERMINAL + 1] is TIMEOUT, like the two ring columns)
+enum { ACT_MAIL_COMMIT = 0, ACT_MAIL_REWARD = 2, ACT_MAIL_TERMINAL = 3, ACT_MAIL_TIMEOUT = 4, ACT_MAIL_STEP = 5,   // ([TERMINAL + 1] is TIMEOUT, like the two ring columns)
+       ACT_MAIL_NOISE_OFFSET = 6 };   // il_act_step_population: this learner's Philox offset as raw uint32 bits, written before the commit word (the one-learner entry points take it as an argument)
 template <class F>
 struct ActMail {
   F* mail; int o_next, o_obs, o_act, o_echo;

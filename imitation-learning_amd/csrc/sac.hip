@@ -3142,16 +3142,18 @@ extern "C" int il_actor_log_prob(const float* actor, int32_t S, int32_t A, int32
 // (memory.py:40-44), optionally wrap it for absorbing states (memory.py:65-68), sample the action for the next observation
 // (models.py:90-94) and hand it to the host through a pinned, device-mapped mailbox. The ring cursor lives on the device.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void k_act_step(const float* __restrict__ actor, int S, int A, int H, float* mail, float* __restrict__ carry, float* __restrict__ ring,
-                                                  long long* __restrict__ ring_state, int row, uint64_t seed, uint32_t offset, const int* __restrict__ version, long long mirror_stride) {
-  if (version) actor += (size_t)version[0] * mirror_stride;   // published parameter snapshot (il_act_publish): never the arena an update is rewriting
-  extern __shared__ __attribute__((aligned(16))) float smem[];
+// The step itself, shared by k_act_step and k_act_step_population (one workgroup = one learner's step; the same arithmetic in both, so the same bits).
+// kMailOffset: the Philox offset is the raw uint32 in header word ACT_MAIL_NOISE_OFFSET of this learner's mailbox (read behind the commit word) instead of `offset`.
+template <bool kMailOffset>
+__device__ __forceinline__ void act_step_body(float* smem, const float* __restrict__ actor, int S, int A, int H, float* mail, float* __restrict__ carry, float* __restrict__ ring,
+                                              long long* __restrict__ ring_state, int row, uint64_t seed, uint32_t offset) {
   const int tid = threadIdx.x;
   const ActPost p = act_post(mail, carry, ring_state, S, A);
   if (p.uncoupled) return;   // block-uniform: no row, no action, no echo
   act_append(p, carry, ring, row, S, A);
   if (!(p.flags & IL_ACT_NO_ACTION)) {  // block-uniform
     const int greedy = p.flags & IL_ACT_GREEDY;
+    if (kMailOffset) offset = __float_as_uint(mail[ACT_MAIL_NOISE_OFFSET]);
     const ActTile t = actor_tile(smem, actor, S, A, H, p.m.obs(), p.m.ld, 0, 1);   // barriers inside: every carry[] read above precedes the writes below
     if (tid < A) {
       const float mean = t.Os[tid], lsr = t.Os[A + tid];
@@ -3162,6 +3164,22 @@ __global__ __launch_bounds__(1024) void k_act_step(const float* __restrict__ act
     if (tid >= 64 && tid < 64 + S) carry[tid - 64] = p.m.obs()[tid - 64];
   }
   act_commit(p, carry, ring_state, S, A);
+}
+
+__global__ __launch_bounds__(1024) void k_act_step(const float* __restrict__ actor, int S, int A, int H, float* mail, float* __restrict__ carry, float* __restrict__ ring,
+                                                  long long* __restrict__ ring_state, int row, uint64_t seed, uint32_t offset, const int* __restrict__ version, long long mirror_stride) {
+  if (version) actor += (size_t)version[0] * mirror_stride;   // published parameter snapshot (il_act_publish): never the arena an update is rewriting
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  act_step_body<false>(smem, actor, S, A, H, mail, carry, ring, ring_state, row, seed, offset);
+}
+
+// One environment step of L learners (a seed sweep in one process) as ONE launch: workgroup l runs the step above for learners[l] - its own actor, mailbox, carry, ring,
+// cursor and Philox seed. The workgroups share nothing and never wait for each other (no co-residency requirement); a learner whose post has neither a pending
+// transition nor an action to take (an idle one: IL_ACT_NO_ACTION alone) gets its echo and nothing else of it is written.
+__global__ __launch_bounds__(1024) void k_act_step_population(const il_act_learner* __restrict__ learners, int S, int A, int H, int row) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const il_act_learner d = learners[blockIdx.x];
+  act_step_body<true>(smem, d.actor, S, A, H, d.mailbox, d.carry, d.ring, (long long*)d.ring_state, row, d.noise_seed, 0u);
 }
 
 extern "C" int il_actor_act(const float* actor, int32_t S, int32_t A, int32_t H, const float* states, int32_t ld_states, int32_t n, const float* eps,
@@ -3215,6 +3233,19 @@ extern "C" int il_act_step(const float* actor, int32_t S, int32_t A, int32_t H, 
                                                                                                     mirror_version, mirror_stride);
   }
   IL_CHECK_LAUNCH("il_act_step");
+  return IL_OK;
+}
+
+extern "C" int il_act_step_population(const il_act_learner* learners, int32_t n_learners, int32_t S, int32_t A, int32_t H, il_stream_t stream_) {
+  IL_CHECK_ARG(learners && n_learners >= 1, "il_act_step_population: null descriptors or no learner (n_learners=%d)", n_learners);
+  IL_CHECK_ARG(H % 64 == 0 && H >= 64 && H <= 256 && A >= 1 && 2 * A <= 16 && S >= 1, "il_act_step_population: unsupported dims (hidden=%d, action_dim=%d)", H, A);
+  const int row = il_ring_row_floats(S, A);
+  IL_CHECK_ARG(row <= tile_threads(H) && 64 + S <= tile_threads(H), "il_act_step_population: ring row of %d floats / state_dim %d exceed the %d-thread workgroup", row, S, tile_threads(H));
+  {
+    IL_TRACE("k_act_step_population", stream_);
+    k_act_step_population<<<n_learners, tile_threads(H), tile_lds_bytes(round_up16(S + A), H), (hipStream_t)stream_>>>(learners, S, A, H, row);
+  }
+  IL_CHECK_LAUNCH("il_act_step_population");
   return IL_OK;
 }
 

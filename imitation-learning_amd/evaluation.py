@@ -3,6 +3,8 @@
 The policy mean comes from `il_actor_act` (one launch per environment step, SoftActor.get_greedy_action); the environment and the
 episode bookkeeping stay on the host, as in the reference. Episodes are recorded into preallocated host buffers (the horizon is
 known from env.max_episode_steps) instead of python lists of 1-row tensors.
+
+`evaluate_population` evaluates the L learners of a `PopulationActingWorker` in lockstep: one `il_act_step_population` launch per evaluation step for all of them.
 """
 import torch
 
@@ -50,4 +52,27 @@ def evaluate_agent(actor, env, num_episodes: int, return_trajectories: bool = Fa
   returns = [log.total for log in logs]
   if return_trajectories:
     return returns, [log.as_trajectory() for log in logs]
+  return returns
+
+
+def evaluate_population(worker, eval_envs, num_episodes: int):
+  """`[evaluate_agent(actor_l, eval_envs[l], num_episodes) for l]` with ONE launch per lockstep evaluation step (`PopulationActingWorker.act_eval`: greedy, own mailboxes
+  and scratch carries, so a transition in flight between two fused steps keeps its carry). A learner that has finished its episodes idles until the last one has; each
+  actor's `_act_calls` advances by the number of steps of its own episodes, as `get_greedy_action` would have advanced it."""
+  L = worker.L
+  assert len(eval_envs) == L
+  returns = [[] for _ in range(L)]
+  if num_episodes <= 0: return returns
+  with torch.inference_mode():
+    obs, totals = [env.reset() for env in eval_envs], [0.0] * L
+    while any(o is not None for o in obs):
+      acts = worker.act_eval(obs)
+      for l in range(L):
+        if obs[l] is None: continue
+        nxt, r, finished = eval_envs[l].step(acts[l:l + 1])
+        totals[l] += float(r)
+        if finished:
+          returns[l].append(totals[l]); totals[l] = 0.0
+          nxt = eval_envs[l].reset() if len(returns[l]) < num_episodes else None
+        obs[l] = nxt
   return returns

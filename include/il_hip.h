@@ -374,6 +374,8 @@ int il_bc_step_general(float* actor, float* actor_grad, const il_adam* opt, int3
  * mailbox: il_act_mailbox_floats(S,A) floats of pinned host memory, Sp = roundup4(S), Ap = roundup4(A):
  *   host -> device  [0] commit word = sequence * 64 + IL_ACT_* flags (as a float, < 2^23), written LAST: it publishes the post
  *                   [2] reward  [3] terminal  [4] timeout  [5] step
+ *                   [6] il_act_step_population only: the Philox offset of this post's sample, raw uint32 bits, written before the commit word
+ *                       (il_act_step / il_act_step_general take the offset as an argument and ignore the word)
  *                   [8, 8+S)       next_state of the pending transition
  *                   [8+Sp, 8+Sp+S) observation to act on (== next_state unless the episode ended and the env was reset)
  *   device -> host  [8+2Sp, +A)    action;   [8+2Sp+Ap] echo of the commit word, stored last with system-scope release
@@ -401,6 +403,15 @@ int32_t il_act_mailbox_floats(int32_t state_dim, int32_t action_dim);
 int il_act_step(const float* actor, int32_t state_dim, int32_t action_dim, int32_t hidden, float* mailbox, float* carry, float* ring,
                 int64_t* ring_state, uint64_t noise_seed, uint32_t noise_offset, const int32_t* mirror_version, int64_t mirror_stride,
                 il_stream_t stream);
+/* il_act_step for n_learners learners of one shape in ONE launch (a seed sweep in one process): workgroup l runs il_act_step's contract for learners[l] (a DEVICE array).
+ * Every learner has its own mailbox (pinned host memory), carry, ring, cursor and Philox seed; its Philox offset travels in word [6] of its mailbox, because the
+ * learners' offsets drift apart (evaluation episodes of different lengths share the counter). A learner whose post carries IL_ACT_NO_ACTION and no IL_ACT_PENDING is
+ * idle in this launch: it gets its echo and nothing else of it is written. Shape limits: il_act_step's. No mirror form; IL_ACT_REWARD_ON_DEVICE posts are
+ * the caller's to refuse (no coupling launch precedes this one). */
+typedef struct il_act_learner {
+  const float* actor; float* mailbox; float* carry; float* ring; int64_t* ring_state; uint64_t noise_seed;
+} il_act_learner;
+int il_act_step_population(const il_act_learner* learners /* device */, int32_t n_learners, int32_t state_dim, int32_t action_dim, int32_t hidden, il_stream_t stream);
 /* Publish the actor arena (n floats) into snapshot slot (version+1)%3 of `mirror` and advance the version. version_and_counter: device
  * int32[2] = {version, internal completion counter}, zero-initialised. Enqueue after every update (capturable into the update's graph). */
 int il_act_publish(const float* actor, int64_t n, float* mirror, int64_t mirror_stride, int32_t* version_and_counter, il_stream_t stream);
@@ -812,7 +823,7 @@ int il_red_epoch_steps(const il_red* d, const il_batch* ring, const float* mask_
                        uint32_t flags, const il_epoch* epoch, int32_t steps, il_stream_t stream);
 
 /* sizeof() of the descriptor structs in this build (0 il_batch, 1 il_adam, 2 il_sac, 3 il_disc, 4 il_pwil, 5 il_sample_args, 6 il_red,
- * 7 il_dril, 8 il_disc_shaped, 9 il_disc_deep, 10 il_peer_bucket, 11 il_disc_shaped_deep, 12 il_epoch; -1 otherwise): lets a binding verify its own struct definitions. */
+ * 7 il_dril, 8 il_disc_shaped, 9 il_disc_deep, 10 il_peer_bucket, 11 il_disc_shaped_deep, 12 il_epoch, 13 il_act_learner; -1 otherwise): lets a binding verify its own struct definitions. */
 int32_t il_struct_size(int32_t which);
 
 #ifdef __cplusplus

@@ -8,6 +8,10 @@ points (GAIL variants with per-update host inputs, batch sizes that are not a mu
 Acting goes through `il.ActingWorker` for every algorithm (`+acting.schedule=exact|fused|overlap`, default exact; `per_function` keeps the reference's call sequence). PWIL's
 reward is computed on the device in front of each append and its expert relabel (mix_expert_data != none) is one library call; `+pretraining.schedule=per_function` keeps
 the row-by-row loop.
+
+Sweeps:  python train.py -m seed=1,2,3 algorithm=GAIL env=halfcheetah  (Hydra's multirun: comma lists, Cartesian product, outputs/<algorithm>_<env>_sweeper/<time>/<job>/).
+Jobs that differ only in their seed train as ONE population in lockstep (`train_sweep`: `il.BatchedPopulationPlan` for the update, `il.PopulationActingWorker` or one
+`il.ActingWorker` per learner for acting: `+sweep.schedule=population|per_learner`, the same bits either way); every other sweep runs its jobs one after another, and says so.
 """
 import os
 import sys
@@ -21,7 +25,7 @@ import imitation_learning_amd as il  # noqa: E402
 from imitation_learning_amd import _lib  # noqa: E402
 from imitation_learning_amd import config as il_config  # noqa: E402
 from imitation_learning_amd.environments import make_env  # noqa: E402
-from imitation_learning_amd.evaluation import evaluate_agent  # noqa: E402
+from imitation_learning_amd.evaluation import evaluate_agent, evaluate_population  # noqa: E402
 from imitation_learning_amd.models import default_device  # noqa: E402
 from imitation_learning_amd.utils import cycle, lineplot  # noqa: E402
 
@@ -387,7 +391,272 @@ def train(cfg, file_prefix: str = '') -> float:
   return float(np.mean(score)) if score else float('nan')
 
 
+# ---- seed sweeps (reference README.md:96-99: `python train.py -m seed=1,2,...`): the jobs of one sweep that differ only in their seed, as one population in one process
+SWEEP_SCHEDULES = ('population', 'per_learner')
+SWEEP_DEFAULT_SCHEDULE = 'per_learner'
+
+
+def sweep_schedule(cfg) -> str:
+  """`+sweep.schedule=population`: one il_act_step_population launch per lockstep environment step, the il_*_population launches per update, evaluate_population.
+  `per_learner`: the same driver, learners, seeds and learner ids through one ActingWorker(noise_seed=seed) per learner, plan.run() per learner and evaluate_agent - the
+  A/B partner, and the same bits."""
+  schedule = (cfg.get('sweep', {}) or {}).get('schedule', SWEEP_DEFAULT_SCHEDULE)
+  assert schedule in SWEEP_SCHEDULES, f'+sweep.schedule={schedule}: expected one of {SWEEP_SCHEDULES}'
+  return schedule
+
+
+def _fused_shape(model_cfg) -> bool:
+  return int(model_cfg.depth) == 2 and str(model_cfg.activation) == 'relu' and int(model_cfg.hidden_size) % 64 == 0 and 64 <= int(model_cfg.hidden_size) <= 256
+
+
+def sweep_fallback_reason(cfg):
+  """None when a seed sweep of this configuration can train as one population (what il.BatchedPopulationPlan and il.PopulationActingWorker take); otherwise the reason
+  its jobs run one after another through train()."""
+  if cfg.algorithm not in ('SAC', 'GAIL'):
+    return f'algorithm={cfg.algorithm} has no population launches (SAC and GAIL have)'
+  if not (_fused_shape(cfg.reinforcement.actor) and _fused_shape(cfg.reinforcement.critic)):
+    return 'an actor / critic shape outside depth 2, ReLU, hidden 64..256 in multiples of 64 has no population launches'
+  if int(cfg.reinforcement.actor.hidden_size) != int(cfg.reinforcement.critic.hidden_size):
+    return 'actor and critic of different hidden sizes have no population launches'
+  if cfg.training.batch_size % 16 != 0:
+    return f'training.batch_size={cfg.training.batch_size} is not a multiple of 16'
+  if cfg.imitation.mix_expert_data != 'none':
+    return f'imitation.mix_expert_data={cfg.imitation.mix_expert_data} edits the batches between the launches'
+  if cfg.imitation.bc_aux_loss:
+    return 'imitation.bc_aux_loss adds an actor step per update that the population launches do not have'
+  if int(cfg.distributed.world_size) != 1:
+    return 'distributed.world_size > 1: a population is a single-GPU mode'
+  acting = (cfg.get('acting', {}) or {}).get('schedule', 'exact')
+  if acting not in ('exact', 'fused'):
+    return f'+acting.schedule={acting}: the population acting launch has the exact and the fused schedule'
+  if cfg.algorithm == 'GAIL':
+    d = cfg.imitation.discriminator
+    if (int(d.depth), str(d.activation)) != (1, 'relu'):
+      return 'a depth-2 / tanh discriminator runs its per-function entry points inside the plan'
+    if d.reward_shaping or d.subtract_log_policy:
+      return 'reward shaping / subtract_log_policy run their per-function entry points inside the plan'
+    if cfg.imitation.loss_function == 'PUGAIL' and float(cfg.imitation.nonnegative_margin) != float('inf'):
+      return 'a finite PUGAIL margin needs a value pass ahead of the gradients'
+    if cfg.imitation.loss_function == 'Mixup':   # whatever mixup_alpha: il_gail_step_population refuses every Mixup descriptor
+      return 'imitation.loss_function=Mixup has no population discriminator step (BCE and PUGAIL with an infinite margin have)'
+  return None
+
+
+def _without_seed(cfg) -> dict:
+  import copy
+  d = copy.deepcopy(dict(cfg))
+  d.pop('seed', None)
+  return d
+
+
+def sweep_groups(cfgs):
+  """The jobs of a sweep as runs: [(job numbers, reason)] in job order. reason None: those jobs differ only in `seed` and train as one population (train_sweep);
+  otherwise a single job for train(), with the reason it is not part of a population."""
+  keys, members = [], []
+  for j, cfg in enumerate(cfgs):
+    k = _without_seed(cfg)
+    for i, other in enumerate(keys):
+      if other == k:
+        members[i].append(j); break
+    else:
+      keys.append(k); members.append([j])
+  runs = []
+  for jobs in members:
+    reason = sweep_fallback_reason(cfgs[jobs[0]])
+    if reason is None and len(jobs) == 1:
+      reason = 'no other job of the sweep differs from it in the seed alone'
+    if reason is None and len({cfgs[j].seed for j in jobs}) != len(jobs):
+      reason = 'two jobs with the same seed'
+    runs += [(jobs, None)] if reason is None else [([j], reason) for j in jobs]
+  return sorted(runs, key=lambda r: r[0][0])
+
+
+def sweep_dir(cfg, stamp: str) -> str:
+  """The reference's hydra.sweep.dir: outputs/${algorithm}_${env}_sweeper/<time>; job n writes into its subdirectory n."""
+  return os.path.join('outputs', f'{cfg.algorithm}_{cfg.env}_sweeper', stamp)
+
+
+class _Learner:
+  """Everything one job of a seed sweep owns."""
+
+
+def train_sweep(cfgs, prefixes):
+  """The loop of train() in lockstep over L learners that differ only in their seed: per lockstep step ONE population act launch, L host environment steps and ONE
+  append launch (`+acting.schedule=fused`: one launch for both); on update steps ONE population update (il.BatchedPopulationPlan); on evaluation steps
+  evaluate_population. Every learner has its own seeds, index stream, environments, rings, networks, optimisers and `learner_id`; job l writes what a single run writes
+  under prefixes[l]. Returns the mean normalised score per job."""
+  L = len(cfgs)
+  assert L >= 1 and len(prefixes) == L
+  for cfg in cfgs: il_config.validate(cfg)
+  cfg0 = cfgs[0]
+  assert all(_without_seed(c) == _without_seed(cfg0) for c in cfgs), 'train_sweep: the jobs of one population differ only in their seed'
+  reason = sweep_fallback_reason(cfg0)
+  if reason is not None: raise NotImplementedError(f'train_sweep: {reason}')
+  how, schedule = sweep_schedule(cfg0), (cfg0.get('acting', {}) or {}).get('schedule', 'exact')
+  dev = default_device()
+  assert _lib.on_device(torch.empty(0, device=dev)), 'train.py needs a GPU: the update path has no CPU fallback'
+  B, env_kw = cfg0.training.batch_size, dict(cfg0.get('synthetic_env', {}) or {})
+  start_time = time.time()   # check_time_usage: training_time is what train() reports - everything after the environments, the expert data and the networks are built
+
+  learners = []
+  for i, cfg in enumerate(cfgs):
+    ln = _Learner()
+    ln.cfg, ln.prefix, seed, built = cfg, prefixes[i], cfg.seed, time.time()
+    il.seed(seed); np.random.seed(seed); torch.manual_seed(seed)   # in front of this learner's construction: its data, initialisation and pretraining are its seed's
+    ln.stream = il.IndexStream(seed)   # the learner's own replay index stream (agent batch, then expert batch, per update)
+    ln.env, ln.eval_env = make_env(cfg.env, cfg.imitation.absorbing, load_data=True, **env_kw), make_env(cfg.env, cfg.imitation.absorbing, **env_kw)
+    ln.env.seed(seed); ln.eval_env.seed(seed)
+    lo, hi = ln.env.env.ref_min_score, ln.env.env.ref_max_score
+    ln.normalise = lambda returns, lo=lo, hi=hi: (np.asarray(returns) - lo) / (hi - lo)
+    ln.expert_memory = ln.env.get_dataset(trajectories=cfg.imitation.trajectories, subsample=cfg.imitation.subsample, device=dev)
+    S, A = ln.env.observation_space.shape[0], ln.env.action_space.shape[0]
+    ln.actor, ln.critic, ln.log_alpha = il.SoftActor(S, A, cfg.reinforcement.actor), il.TwinCritic(S, A, cfg.reinforcement.critic), torch.zeros(1, device=dev)
+    ln.target_critic, entropy_target = il.create_target_network(ln.critic), cfg.reinforcement.target_temperature * A
+    ln.actor_optimiser = il.AdamW(ln.actor, lr=cfg.training.learning_rate, weight_decay=cfg.training.weight_decay)
+    ln.critic_optimiser = il.AdamW(ln.critic, lr=cfg.training.learning_rate, weight_decay=cfg.training.weight_decay)
+    ln.temperature_optimiser = il.Adam(ln.log_alpha, lr=cfg.training.learning_rate)
+    ln.memory = il.ReplayMemory(cfg.memory.size, S, A, cfg.imitation.absorbing)
+    ln.memory.index_rng = ln.expert_memory.index_rng = ln.stream
+    ln.discriminator = ln.discriminator_optimiser = None
+    if cfg.algorithm == 'GAIL':
+      ln.discriminator = il.GAILDiscriminator(S, A, cfg.imitation, cfg.reinforcement.discount)
+      ln.discriminator_optimiser = il.AdamW(ln.discriminator, lr=cfg.imitation.learning_rate, weight_decay=cfg.imitation.weight_decay)
+    ln.metrics = dict(train_steps=[], train_returns=[], test_steps=[], test_returns=[], test_returns_normalized=[], update_steps=[], predicted_rewards=[], alphas=[], entropies=[], Q_values=[])
+    ln.score = []
+    start_time += time.time() - built
+    if cfg.bc_pretraining.iterations > 0:
+      pretrain_bc(cfg, ln.actor, ln.expert_memory, S, A)   # one PretrainPlan per learner
+    ln.plan = il.UpdatePlan(cfg.algorithm, ln.actor, ln.critic, ln.log_alpha, ln.target_critic, ln.memory, ln.actor_optimiser, ln.critic_optimiser, ln.temperature_optimiser, B,
+                            cfg.reinforcement.discount, entropy_target, cfg.reinforcement.polyak_factor, expert_memory=ln.expert_memory, discriminator=ln.discriminator,
+                            discriminator_optimiser=ln.discriminator_optimiser, imitation_cfg=cfg.imitation if cfg.algorithm == 'GAIL' else None, overlap=False, learner_id=i)
+    ln.plan.main_feeds_ring = True
+    ln.plan.watch_timeouts()
+    if ln.discriminator is not None: ln.discriminator.eval()   # train.py:147
+    learners.append(ln)
+  plans = [ln.plan for ln in learners]
+
+  if how == 'population':
+    pop = il.BatchedPopulationPlan(plans)
+    worker = il.PopulationActingWorker([ln.actor for ln in learners], [ln.memory for ln in learners], [ln.cfg.seed for ln in learners])
+    update = pop.run
+  else:
+    pop, worker = None, None
+    workers = [il.ActingWorker(ln.actor, ln.memory, noise_seed=ln.cfg.seed) for ln in learners]
+    def update():
+      for p in plans: p.run()
+
+  every = range(L)
+  t, train_return = [0] * L, [0.0] * L
+  state = [ln.env.reset() for ln in learners]
+  action = None
+  if schedule == 'fused':
+    action = worker.act(state) if worker is not None else torch.cat([workers[l].act(state[l]) for l in every])
+  captured, last_good = False, 0
+  for step in range(1, cfg0.steps + 1):
+    if schedule == 'exact':
+      action = worker.act(state) if worker is not None else torch.cat([workers[l].act(state[l]) for l in every])
+    next_state, reward, terminal, timed_out, following = [None] * L, [0.0] * L, [False] * L, [False] * L, [None] * L
+    for l, ln in enumerate(learners):
+      next_state[l], reward[l], terminal[l] = ln.env.step(action[l:l + 1])
+      t[l] += 1
+      timed_out[l] = t[l] == ln.env.max_episode_steps
+      following[l] = ln.env.reset() if terminal[l] else next_state[l]   # the observation the next action is for
+    true_terminal = [terminal[l] and not timed_out[l] for l in every]
+    if schedule == 'exact':
+      if worker is not None: worker.append(step, next_state, reward, true_terminal, timed_out)
+      else:
+        for l in every: workers[l].append(step, next_state[l], reward[l], true_terminal[l], timed_out[l])
+    else:
+      if worker is not None: action = worker.step(step, next_state, reward, true_terminal, timed_out, obs=following)
+      else: action = torch.cat([workers[l].step(step, next_state[l], reward[l], true_terminal[l], timed_out[l], obs=following[l]) for l in every])
+    for l, ln in enumerate(learners):
+      train_return[l] += reward[l]
+      if terminal[l]:
+        ln.metrics['train_steps'].append(step); ln.metrics['train_returns'].append([train_return[l]])
+        t[l], train_return[l] = 0, 0.0
+      state[l] = following[l]
+
+    if step >= cfg0.training.start and step % cfg0.training.interval == 0:
+      if pop is not None and captured:
+        pop.replay()
+      else:
+        update()
+        if pop is not None and not captured and os.environ.get('IL_TRAIN_LAUNCH', 'direct') == 'graph':   # the first update eagerly (loads the code objects), then one replay per update
+          pop.capture(warmup=0)
+          captured = True
+      for p in plans: check_timeouts_seen(p, step, last_good)   # host reads of pinned words: every step, independent of logging.interval
+      last_good = step
+      if cfg0.logging.interval > 0 and step % cfg0.logging.interval == 0:  # the only D2H reads of the update path (train.py:205-210)
+        for ln in learners:
+          p, m = ln.plan, ln.metrics
+          p.join()
+          check_handoff(p, step)
+          m['update_steps'].append(step); m['predicted_rewards'].append(p.transitions['rewards'].cpu().numpy())
+          m['alphas'].append(ln.log_alpha.exp().cpu().numpy()); m['entropies'].append((-p.logp).cpu().numpy()); m['Q_values'].append(p.q.cpu().numpy())
+
+    if step % cfg0.evaluation.interval == 0 and not cfg0.check_time_usage:
+      if worker is not None:
+        returns = evaluate_population(worker, [ln.eval_env for ln in learners], cfg0.evaluation.episodes)
+      else:
+        returns = [evaluate_agent(ln.actor, ln.eval_env, cfg0.evaluation.episodes) for ln in learners]
+      for ln, episode_returns in zip(learners, returns):
+        m, cfg, normalised = ln.metrics, ln.cfg, ln.normalise(episode_returns)
+        ln.score.append(float(normalised.mean()))
+        for key, value in (('test_steps', step), ('test_returns', episode_returns), ('test_returns_normalized', list(normalised))): m[key].append(value)
+        lineplot(m['test_steps'], m['test_returns'], filename=f'{ln.prefix}test_returns', title=f'{cfg.algorithm}: {cfg.env} Test Returns')
+        if len(m['train_returns']) > 0:
+          lineplot(m['train_steps'], m['train_returns'], filename=f'{ln.prefix}train_returns', title=f'Training {cfg.algorithm}: {cfg.env} Train Returns')
+        if cfg.logging.interval > 0 and len(m['update_steps']) > 0:   # train.py:224-228
+          if cfg.algorithm != 'SAC': lineplot(m['update_steps'], m['predicted_rewards'], filename=f'{ln.prefix}predicted_rewards', yaxis='Predicted Reward', title=f'{cfg.algorithm}: {cfg.env} Predicted Rewards')
+          lineplot(m['update_steps'], m['alphas'], filename=f'{ln.prefix}sac_alpha', yaxis='Alpha', title=f'{cfg.algorithm}: {cfg.env} Alpha')
+          lineplot(m['update_steps'], m['entropies'], filename=f'{ln.prefix}sac_entropy', yaxis='Entropy', title=f'{cfg.algorithm}: {cfg.env} Entropy')
+          lineplot(m['update_steps'], m['Q_values'], filename=f'{ln.prefix}Q_values', yaxis='Q-value', title=f'{cfg.algorithm}: {cfg.env} Q-values')
+
+  for p in plans:   # never save a learner whose last updates ran on expired device-side waits
+    p.join()
+    check_timeouts_seen(p, cfg0.steps, last_good)
+    check_handoff(p, cfg0.steps)
+  torch.cuda.synchronize()
+  scores = []
+  for ln in learners:
+    cfg, m = ln.cfg, ln.metrics
+    if cfg.check_time_usage: m['training_time'] = time.time() - start_time
+    if cfg.save_trajectories:   # train.py:231-234
+      _, trajectories = evaluate_agent(ln.actor, ln.eval_env, cfg.evaluation.episodes, return_trajectories=True, render=cfg.render)
+      torch.save(trajectories, f'{ln.prefix}trajectories.pth')
+    torch.save(dict(actor=ln.actor.state_dict(), critic=ln.critic.state_dict(), log_alpha=ln.log_alpha), f'{ln.prefix}agent.pth')
+    if cfg.algorithm == 'GAIL': torch.save(ln.discriminator.state_dict(), f'{ln.prefix}discriminator.pth')   # train.py:238
+    torch.save(m, f'{ln.prefix}metrics.pth')
+    scores.append(float(np.mean(ln.score)) if ln.score else float('nan'))
+  return scores
+
+
+def multirun(argv, stamp=None):
+  """`python train.py -m ...`: compose the jobs, group them, run every group. Returns (sweep directory, scores in job order)."""
+  cfgs, overrides = il_config.compose_multirun(argv)
+  root = os.path.abspath(sweep_dir(cfgs[0], stamp or time.strftime('%m-%d_%H-%M-%S')))
+  prefixes = []
+  for j in range(len(cfgs)):
+    os.makedirs(os.path.join(root, str(j)), exist_ok=True)
+    prefixes.append(os.path.join(root, str(j), ''))
+  scores = [None] * len(cfgs)
+  for jobs, reason in sweep_groups(cfgs):
+    if reason is None:
+      print(f'[train] sweep: jobs {jobs[0]}..{jobs[-1]} ({" | ".join(" ".join(overrides[j]) for j in jobs)}) train as one population of {len(jobs)} learners '
+            f'(+sweep.schedule={sweep_schedule(cfgs[jobs[0]])})', file=sys.stderr)
+      for j, sc in zip(jobs, train_sweep([cfgs[j] for j in jobs], [prefixes[j] for j in jobs])): scores[j] = sc
+    else:
+      j = jobs[0]
+      print(f'[train] sweep: job {j} ({" ".join(overrides[j])}) runs on its own, one job after another: {reason}', file=sys.stderr)
+      scores[j] = train(cfgs[j], file_prefix=prefixes[j])
+  for j, cfg in enumerate(cfgs):
+    print(f'#{j} {" ".join(overrides[j])}: {cfg.algorithm} {cfg.env}: mean normalised score {scores[j]:.4f} (outputs in {os.path.join(root, str(j))})')
+  return root, scores
+
+
 def main(argv):
+  if any(o in ('-m', '--multirun') for o in argv):
+    return multirun(argv)[1]
   cfg = il_config.compose(argv)
   out = os.path.join('outputs', f'{cfg.algorithm}_{cfg.env}', time.strftime('%m-%d_%H-%M-%S'))
   if int(os.environ.get('RANK', '0')) == 0:   # data-parallel runs: rank 0 owns the output directory (the other ranks write nothing)
