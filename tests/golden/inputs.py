@@ -19,6 +19,29 @@ DIMS = {  # state size incl. absorbing bit, action size (environments.py:27, gym
 }
 
 
+# Widths away from the four above, where the kernels branch: the state / action sizes of `imitation.absorbing=false` (environments.py:27 without the absorbing bit), the
+# narrowest ones, the edges of the 16- and 32-wide input tiles for S and for S + A, and the limits of the entry points - S + A = 127 / 128 (RED, the general
+# discriminators; S = 127 for DRIL and the shaping potentials), ring rows of 255 -> 256 and exactly 256 floats (the acting launch at hidden 64), S + A = 507 / 508
+# (the fused SAC update), and two widths in between. (2S + A + 5) mod 4 takes every value, so packed rows with each amount of padding occur.
+EDGE_DIMS = ((11, 3), (17, 6), (111, 8),
+             (1, 1), (3, 1), (1, 8),
+             (15, 1), (16, 8), (33, 2), (63, 1), (64, 8),
+             (119, 8), (120, 8), (127, 1),
+             (121, 8), (122, 7),
+             (500, 8), (499, 8),
+             (255, 8), (129, 1))
+
+
+def edge_dims(max_state=None, max_input=None):
+  """The EDGE_DIMS within a kernel family's limits on S and on S + A."""
+  return tuple((S, A) for S, A in EDGE_DIMS if (max_state is None or S <= max_state) and (max_input is None or S + A <= max_input))
+
+
+def state_action_dims(env):
+  """(state size, action size) of `env`: a name in DIMS, or the pair itself."""
+  return DIMS[env] if isinstance(env, str) else (int(env[0]), int(env[1]))
+
+
 def mlp_params(rs, in_dim, hidden, depth, out_dim, out_scale=1.0):
   """Flat parameter vector in torch order, fan-in scaled weights, small non-zero biases."""
   dims = [in_dim] + [hidden] * depth + [out_dim]
@@ -50,7 +73,7 @@ def transitions(rs, n, S, A, *, state_shift=0.0, absorbing_frac=0.02, terminal_f
 
 def sac_case(seed, env='halfcheetah', hidden=256, batch=256, steps=3, depth=2, activation='relu', critic=None):
   """critic: (hidden, depth, activation) of the twin critics when they differ from the actor's (reinforcement.critic of the reference's configuration)."""
-  S, A = DIMS[env]
+  S, A = state_action_dims(env)
   ch, cd, ca = critic or (hidden, depth, activation)
   rs = np.random.RandomState(seed)
   actor = mlp_params(rs, S, hidden, depth, 2 * A, out_scale=0.3)
@@ -75,7 +98,7 @@ GENERAL_SAC_CASES = {
 
 
 def gail_case(seed, env='halfcheetah', hidden=64, batch=256, steps=3, spectral_norm=True):
-  S, A = DIMS[env]
+  S, A = state_action_dims(env)
   D = S + A
   rs = np.random.RandomState(seed)
   W1 = (rs.standard_normal((hidden, D)) * np.sqrt(2.0 / D)).astype(f32)
@@ -94,7 +117,7 @@ def gail_case(seed, env='halfcheetah', hidden=64, batch=256, steps=3, spectral_n
 def gail_deep_case(seed, env, hidden, batch, steps, depth=2, activation='tanh', spectral_norm=True):
   """GAIL discriminator of any `_create_fcnn` shape: weights / biases / u / v per layer (hidden layers then the H -> 1 output), policy + expert batches,
   the U(0,1) draws of the gradient penalty and of Mixup, and log pi offsets for subtract_log_policy."""
-  S, A = DIMS[env]
+  S, A = state_action_dims(env)
   D = S + A
   rs = np.random.RandomState(seed)
   dims = [D] + [hidden] * depth + [1]
@@ -121,7 +144,7 @@ GAIL_DEEP_CASES = (   # name, gail_deep_case arguments, loss_function, (lr, weig
 def gail_shaped_deep_case(seed, env, hidden, batch, steps, depth=2, activation='tanh', spectral_norm=True, state_only=False):
   """Reward-shaping discriminator with a shaping potential of any `_create_fcnn` shape: g = Linear(Dg, 1), h = [Linear - act] x depth - Linear(H, 1) on the state,
   spectral-norm buffers per Linear, batches with ~30 % terminals, the U(0,1) draws of the gradient penalty, Beta draws for Mixup and log pi offsets."""
-  S, A = DIMS[env]
+  S, A = state_action_dims(env)
   Dg = S if state_only else S + A
   rs = np.random.RandomState(seed)
   dims = [S] + [hidden] * depth + [1]
@@ -213,7 +236,7 @@ def adril_batches(seed, B, S, A):
 def red_case(seed, env, hidden, batch, steps, depth=1, activation='relu', p_in=0.0, p=0.0):
   """RED predictor / frozen target (`_create_fcnn`: D -> H (-> H) -> D, ReLU / Tanh), weighted expert batches, a sigma batch and a query batch; with
   dropout also the predictor's keep-masks per update (input, hidden 1[, hidden 2]) and for the train-mode set_sigma forward."""
-  S, A = DIMS[env]
+  S, A = state_action_dims(env)
   D = S + A
   rs = np.random.RandomState(seed)
   predictor, target = mlp_params(rs, D, hidden, depth, D), mlp_params(rs, D, hidden, depth, D)
@@ -239,7 +262,7 @@ RED_CASES = (   # name, red_case arguments, lr, weight decay; the last three mir
 def dril_case(seed, env, hidden, batch, steps, p_in=0.1, p=0.1, depth=1, activation='tanh'):
   """DRIL policy ensemble (`_create_fcnn`: Dropout-Linear(S,H)-Dropout-act(-Linear(H,H)-Dropout-act)-Linear(H,2A)), expert batches with their dropout
   keep-masks, and the masks of the 5-member Monte-Carlo ensemble for an expert set and a query set (rows in repeat_interleave order)."""
-  S, A = DIMS[env]
+  S, A = state_action_dims(env)
   rs = np.random.RandomState(seed)
   params = mlp_params(rs, S, hidden, depth, 2 * A, out_scale=0.3)
   keep = lambda shape, pr: (rs.uniform(size=shape) >= pr).astype(f32)
@@ -295,7 +318,7 @@ def raw_d4rl_dataset(seed, obs_dim=5, act_dim=2):
 def gail_shaped_case(seed, env, hidden, batch, steps, spectral_norm):
   """Reward-shaping discriminator: g = Linear(S+A, 1), h = Linear(S, H)-ReLU-Linear(H, 1), spectral-norm buffers, batches with ~30 % terminals so that
   the (1 - terminal) factor is exercised, gradient-penalty draws."""
-  S, A = DIMS[env]
+  S, A = state_action_dims(env)
   rs = np.random.RandomState(seed)
   D = S + A
   unit = lambda x: (x / np.linalg.norm(x)).astype(f32)

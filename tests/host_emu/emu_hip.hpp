@@ -9,7 +9,8 @@
 // have. A launch is a job in its stream's queue: jobs of one stream run in order, the jobs at the heads of different streams side by side, workgroups dispatched in
 // blockIdx order (x fastest). Several workgroups can be RESIDENT at once: a lane that polls a device-side counter (every polling loop of the kernels sleeps between two
 // polls: s_sleep) suspends its workgroup, and the others - later workgroups of the same launch, workgroups of the launch on the other stream - run until the counter
-// moves; that is what co-residency gives the device-side hand-offs on the GPU. Launches on the null stream run to completion at once. Atomics are plain
+// moves; that is what co-residency gives the device-side hand-offs on the GPU. Launches on the null stream run to completion at once (beside whatever the other streams
+// have queued, which may still be under way afterwards; a synchronisation or a wait of the null stream finishes it). Atomics are plain
 // read-modify-writes, fences and s_waitcnt nothing: program order on one thread is stronger than any of them.
 // IL_EMU_SCHEDULE=reverse|random:<seed> perturbs every choice the model leaves open (lane order, wave order between two barriers, the dispatch order of a launch's
 // workgroups, which stream's launch takes the next turn): a result that changes with it is a missing barrier, a race between workgroups or a hand-off that only works in
@@ -113,7 +114,7 @@ inline ucontext_t sched_ctx;
 // A launch is a job in its stream's queue; jobs of one stream run in order, jobs of different streams side by side. A workgroup (Block) owns its fibers, stacks, LDS and
 // exchange buffers, so that several can be resident at once: a lane that polls a device-side counter (every polling loop of the kernels sleeps: s_sleep) suspends its
 // WORKGROUP and lets the others - of the same launch, or of the launch at the head of another stream - run; that is what co-residency gives the device hand-offs on
-// the GPU. Launches on the null stream run to completion at once (everything else drained first), which is all the per-function tests need.
+// the GPU. Launches on the null stream run to completion at once, which is all the per-function tests need.
 struct Block {
   dim3 idx, gdim, bdim;
   int n = 0, cap = 0;
@@ -309,12 +310,16 @@ inline bool step(Job* j) {
   }
   return progress;
 }
-// runs every queued launch of every stream to completion
-inline void drain() {
+// runs every queued launch of every stream to completion. null_stream_only: until the null stream's queue is empty - what a launch on the null stream waits for. The
+// launches of the other streams take their turns meanwhile and stay where they are when it returns: a workgroup of theirs that polls for a signal of a LATER null-stream
+// launch (the discriminator branch of a directly launched update waiting for the index draw that follows an acting worker's append on the caller's stream) is still
+// resident, with its spin count, when that launch comes - on the device the caller's stream is asynchronous and the launch is already queued behind the first.
+inline void drain(bool null_stream_only = false) {
   if (draining) return;
   draining = true;
   read_schedule();
   for (;;) {
+    if (null_stream_only && streams[0].q.empty()) break;
     bool any = false;
     std::vector<uintptr_t> order;
     for (auto& kv : streams) if (!kv.second.q.empty()) order.push_back(kv.first);
@@ -344,6 +349,7 @@ inline void stream_wait(uintptr_t waiter, uintptr_t on) {   // hipStreamWaitEven
   if (streams[on].enqueued == streams[on].finished) return;
   Job* j = new Job(); j->is_wait = true; j->wait_stream = on; j->wait_seq = streams[on].enqueued; j->stream = waiter; j->seq = ++streams[waiter].enqueued;
   streams[waiter].q.push_back(j);
+  if (!waiter) drain();   // the null stream stands for the caller's stream AND for the host code between two launches (torch operations on CPU tensors): what it waits for is finished when this returns
 }
 
 // ---- stream capture (hipGraph): while a graph is being captured, launches and stream waits on the streams that belong to the capture are RECORDED - kernel arguments by
@@ -390,7 +396,7 @@ inline void launch(K kernel, dim3 grid, dim3 block, size_t lds_bytes, hipStream_
   StreamQ& s = streams[j->stream];
   j->seq = ++s.enqueued;
   s.q.push_back(j);
-  if (!stream) drain();   // the null stream: synchronous with everything
+  if (!stream) drain(true);   // the null stream: the launch has run when this returns; the other streams' launches ran beside it as far as they got
 }
 }  // namespace emu
 

@@ -311,6 +311,25 @@ def test_adam_and_polyak_kernels():
   np.testing.assert_allclose(N(tt), tgt, rtol=2e-7, atol=1e-9)
 
 
+def test_adam_at_a_late_step():
+  """AdamW resumed from a checkpoint (`load_state_dict`: step 99,999, non-zero moments), three steps: the first recomputes beta^t with pow() (the running products do
+  not belong to the loaded step), the next two continue them (adam_tick's two branches); bias corrections of 1 - 0.9^1e5 = 1 and 1 - 0.999^1e5 = 1 - 3.5e-44 instead
+  of the 0.1 and 0.001 of a first step. Against `onets.adam_step` at the bounds of test_adam_and_polyak_kernels."""
+  rs = np.random.RandomState(1)
+  n, t0 = 100_003, 99_999
+  p, gr = rs.standard_normal(n).astype(np.float32), (rs.standard_normal(n) * rs.uniform(1e-6, 1, n)).astype(np.float32)
+  m, v = (rs.standard_normal(n) * 0.1).astype(np.float32), (rs.uniform(1e-12, 1, n) ** 2).astype(np.float32)
+  pt = T(p.copy())
+  opt = il.AdamW(pt, lr=3e-4, weight_decay=0.1)
+  opt.load_state_dict(dict(step=t0, exp_avg=T(m.copy()), exp_avg_sq=T(v.copy())))
+  for k in range(1, 4):
+    opt.step(T(gr * k))
+    onets.adam_step(p, gr * k, m, v, t0 + k, 3e-4, 0.1)
+    np.testing.assert_allclose(N(pt), p, rtol=2e-7, atol=1e-9); np.testing.assert_allclose(N(opt.exp_avg_sq), v, rtol=2e-7, atol=0)
+    np.testing.assert_allclose(N(opt.exp_avg), m, rtol=2e-7, atol=1e-9)
+  assert int(opt.step_count[0]) == t0 + 3 and opt.state_dict()['step'] == t0 + 3
+
+
 # ------------------------------------------------------------------------------------------------ GAIL
 GAIL_CASES = [
     ('gail_default', dict(seed=31), dict(lr=3e-5, weight_decay=10, grad_penalty=1.0, entropy_bonus=0.0)),
@@ -543,8 +562,8 @@ def test_pwil_every_launch_path_matches_oracle(name, Nn, Th):
   assert int((d.expert_weights >= 0).sum()) == len(o.weights)
 
 
-def _make_plan(algorithm, seed, device_draw=True, loss='BCE', entropy_bonus=0.0, B=256, margin=float('inf'), reward_function='AIRL', mixup_alpha=1):
-  S, A = gi.DIMS['halfcheetah']
+def _make_plan(algorithm, seed, device_draw=True, loss='BCE', entropy_bonus=0.0, B=256, margin=float('inf'), reward_function='AIRL', mixup_alpha=1, dims=None):
+  S, A = dims or gi.DIMS['halfcheetah']
   torch.manual_seed(seed)
   cfg = Cfg(hidden_size=256, depth=2, activation='relu')
   actor, critic = il.SoftActor(S, A, cfg, device=DEV), il.TwinCritic(S, A, cfg, device=DEV)
@@ -563,11 +582,11 @@ def _make_plan(algorithm, seed, device_draw=True, loss='BCE', entropy_bonus=0.0,
 
 
 @pytest.mark.parametrize('reward_function', ['AIRL', 'GAIL', 'FAIRL'])
-def test_inline_relabel_heads_equal_the_reward_kernel(reward_function):
+def test_inline_relabel_heads_equal_the_reward_kernel(reward_function, dims=None):
   """models.py:177-180 inside the chained SAC launch (disc_reward.hpp: the rows a critic tile already holds are relabelled by the discriminator the other branch has just
   stepped) against `predict_reward` (k_gail_reward) on the same rows and the same, updated discriminator: the three reward heads, bit for bit."""
   il.seed(37); il_training._NOISE.clear()
-  plan, nets = _make_plan('GAIL', 19, reward_function=reward_function, B=64)
+  plan, nets = _make_plan('GAIL', 19, reward_function=reward_function, B=64, dims=dims)   # dims: tests/test_dim_edges_gpu.py runs this body at other (state, action) widths
   for _ in range(2):
     plan.run()
   torch.cuda.synchronize()

@@ -403,6 +403,11 @@ def test_batched_population_replays_through_the_oracle():
 def test_acting_launch_replays_through_the_oracle(schedule):
   """il_act_step (append + absorbing wrap + actor(state).sample() in one launch, train.py:151-168) against ReplayOracle + oracle.nets, with the Philox
   draws of every act recorded: ring contents bit-exact (the stored action = the returned action), actions at rtol 1e-5 of the oracle's."""
+  acting_launch_against_the_oracle(schedule, S, A, H)
+
+
+def acting_launch_against_the_oracle(schedule, S, A, H):
+  """The body of the test above at any fused actor shape (tests/test_dim_edges_gpu.py runs it at the widths next to il_act_step's limit)."""
   cap, steps = 41, 70
   cfg = Cfg(hidden_size=H, depth=2, activation='relu')
   torch.manual_seed(17)

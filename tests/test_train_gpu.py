@@ -47,6 +47,11 @@ COMMON = ['steps=260', 'training.start=120', 'evaluation.interval=130', 'evaluat
     ['algorithm=SAC', 'env=hopper', 'reinforcement.actor.depth=3', 'reinforcement.actor.activation=tanh', 'reinforcement.actor.hidden_size=48', 'reinforcement.critic.depth=1',
      'reinforcement.critic.activation=sigmoid', 'reinforcement.critic.hidden_size=80'],
     ['algorithm=GAIL', 'env=halfcheetah', 'reinforcement.actor.hidden_size=320', 'reinforcement.critic.hidden_size=320', 'bc_pretraining.iterations=20'],
+    # imitation.absorbing=false (conf/train_config.yaml, environments.py:27): no absorbing bit, so S = 11 / 17 / 111 - odd widths, packed-row fields off the 16-byte grid
+    ['algorithm=SAC', 'env=hopper', 'imitation.absorbing=false'],
+    ['algorithm=GAIL', 'env=halfcheetah', 'imitation.absorbing=false'],
+    ['algorithm=PWIL', 'env=walker2d', 'imitation.absorbing=false'],
+    ['algorithm=GMMIL', 'env=ant', 'imitation.absorbing=false'],
 ])
 def test_train_runs(tmp_path, args):
   sys.path.insert(0, ROOT)
