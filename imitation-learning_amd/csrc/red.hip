@@ -10,6 +10,8 @@
 //                tiles to pay: 32x32x24 at the default sizes);
 //   k_red_apply  slab sum -> grad (+ AdamW unless IL_FLAG_GRADS_ONLY).
 //   k_red_eval   forward (train or eval mode): reward = exp(-sigma_1 * mean_c (pred - target)^2) and / or the raw embeddings (for set_sigma).
+//   k_red_eval_population   the eval-mode reward of a population of learners (seed sweeps): the learner is a grid dimension, so the 8 workgroups a batch of 256 gives
+//                one learner become 8 L (il_red_reward_population).
 // Dropout keep-masks: supplied by the caller (parity tests feed the masks the reference drew) or drawn on chip from the Philox stream.
 #include "il_common.hpp"
 
@@ -255,11 +257,41 @@ __global__ __launch_bounds__(256) void k_red_eval(il_red d, il_batch b, RedMasks
   }
 }
 
-static int check_red(const il_red* d, const il_batch* b) {
-  IL_CHECK_ARG(d && b, "il_red: null descriptor");
+// Population axis of k_red_eval (il_red_reward_population): gridDim.y selects the learner. The shape (dims, hidden, activation, state_only: what sizes the LDS tile) is the
+// host descriptor's, passed by value; what a learner owns comes from its device descriptor: the two parameter arenas and the bandwidth sigma_1 (set_sigma gives every seed
+// its own). Eval mode whatever p_in / p say (train.py:147), no embeddings written. The tile is red_forward_tile as k_red_eval<DEPTH> runs it with training = 0: same bits.
+template <int DEPTH>
+__global__ __launch_bounds__(256) void k_red_eval_population(il_red d, const il_red* __restrict__ dL, const il_batch* __restrict__ bL, float* const* __restrict__ outL) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int lrn = blockIdx.y;
+  il_batch b = bL[lrn];
+  globalize(b);
+  d.predictor = as_global(dL[lrn].predictor); d.target = as_global(dL[lrn].target); d.sigma_1 = dL[lrn].sigma_1;
+  d.out_pred = d.out_target = nullptr;
+  float* out_reward = as_global(outL[lrn]);
+  const int D = d.state_dim + (d.state_only ? 0 : d.action_dim), H = d.hidden;
+  const RedLds l = red_carve(smem, D, H, DEPTH);
+  const int row0 = blockIdx.x * RT;
+  const RedMasks mk = {nullptr, {nullptr, nullptr}, 0u, 0};
+  red_forward_tile<DEPTH>(l, d, b, mk, row0, D, H);
+  if (threadIdx.x < RT && row0 + threadIdx.x < b.n) {
+    const int r = threadIdx.x;
+    float s = 0.f;
+    for (int c = 0; c < D; ++c) { const float e = l.E[r * l.ldx + c]; s = fmaf(e, e, s); }
+    out_reward[row0 + r] = expf(-d.sigma_1 * (s / (float)D));   // models.py:280
+  }
+}
+
+static int check_red_shape(const il_red* d) {
   const int D = d->state_dim + (d->state_only ? 0 : d->action_dim);
   IL_CHECK_ARG(D >= 1 && D <= 128 && d->hidden >= 2 && d->hidden <= 256 && d->hidden % 2 == 0, "il_red: unsupported dims (input=%d, hidden=%d)", D, d->hidden);
   IL_CHECK_ARG(d->depth >= 0 && d->depth <= 2 && (d->activation == 0 || d->activation == 1), "il_red: depth must be 1 or 2 (0 = 1) and activation 0 (relu) or 1 (tanh)");
+  return IL_OK;
+}
+
+static int check_red(const il_red* d, const il_batch* b) {
+  IL_CHECK_ARG(d && b, "il_red: null descriptor");
+  if (int rc = check_red_shape(d)) return rc;
   IL_CHECK_ARG(d->p_in >= 0.f && d->p_in < 1.f && d->p >= 0.f && d->p < 1.f, "il_red: dropout probabilities must be in [0,1)");
   IL_CHECK_ARG(d->predictor && d->target, "il_red: null parameter arena");
   IL_CHECK_ARG(b->n > 0 && b->states && (d->state_only || b->actions), "il_red: bad batch");
@@ -321,5 +353,24 @@ extern "C" int il_red_forward(const il_red* d, const il_batch* batch, int32_t tr
   const RedMasks mk = {mask_in, {mask_h1, mask_h2}, noise_offset, training ? 1 : 0};
   { IL_TRACE("k_red_eval", (hipStream_t)stream_); eval<<<ceil_div(batch->n, RT), 256, lds, (hipStream_t)stream_>>>(dd, *batch, mk, out_reward); }
   IL_CHECK_LAUNCH("il_red_forward");
+  return IL_OK;
+}
+
+// population axis: predict_reward (eval mode) of n_learners RED discriminators of one shape in one launch
+extern "C" int il_red_reward_population(const il_red* descs_dev, const il_batch* batches_dev, float* const* rewards_out_dev, int32_t n_learners, const il_red* shape_host,
+                                        il_stream_t stream_) {
+  IL_CHECK_ARG(shape_host, "il_red_reward_population: null shape descriptor");
+  IL_CHECK_ARG(descs_dev && batches_dev && rewards_out_dev, "il_red_reward_population: null device array (descriptors %p, batches %p, reward pointers %p)", (const void*)descs_dev,
+               (const void*)batches_dev, (const void*)rewards_out_dev);
+  IL_CHECK_ARG(n_learners >= 1 && n_learners <= 65535, "il_red_reward_population: n_learners=%d must be in 1..65535 (the learner is a grid dimension)", n_learners);
+  if (int rc = check_red_shape(shape_host)) return rc;
+  IL_CHECK_ARG(shape_host->batch > 0, "il_red_reward_population: batch=%d must be > 0", shape_host->batch);
+  const il_red* d = shape_host;
+  const int D = d->state_dim + (d->state_only ? 0 : d->action_dim), depth = red_depth(*d);
+  const size_t lds = red_lds_floats(D, d->hidden, depth) * sizeof(float);
+  const auto eval = depth == 2 ? k_red_eval_population<2> : k_red_eval_population<1>;
+  if (int rc = red_ensure_lds((const void*)eval, lds)) return rc;   // (the > 64 KiB opt-in attaches to a kernel: k_red_eval's does not cover this one)
+  { IL_TRACE("k_red_eval_population", (hipStream_t)stream_); eval<<<dim3(ceil_div(d->batch, RT), n_learners), 256, lds, (hipStream_t)stream_>>>(*d, descs_dev, batches_dev, rewards_out_dev); }
+  IL_CHECK_LAUNCH("il_red_reward_population");
   return IL_OK;
 }

@@ -1482,7 +1482,9 @@ class BatchedPopulationPlan:
   """N independent learners with identical shapes advanced by the SAME kernel launches (`il_*_population`): the learner id is a grid
   dimension, so one update of the whole population costs 11 launches instead of 11 N.  This is the route from the latency-bound
   single-learner regime towards the HBM roofline.  Every learner keeps its own replay ring, MT19937 index stream,
-  networks, optimiser state, scratch and Philox counter (build the `UpdatePlan`s with distinct `learner_id`s)."""
+  networks, optimiser state, scratch and Philox counter (build the `UpdatePlan`s with distinct `learner_id`s).  SAC, GAIL (`il_gail_step_population`: discriminator step +
+  relabel) and RED (`il_red_reward_population`: every learner's eval-mode reward under its own predictor, target and sigma_1) learners; GAIL's and RED's reward launches run
+  on a second stream beside the reward-independent forward kernels (IL_POP_OVERLAP=0: in stream order)."""
 
   def __init__(self, plans, groups: Optional[int] = None):
     self.plans = list(plans)
@@ -1501,7 +1503,11 @@ class BatchedPopulationPlan:
     for p in self.plans:
       p._set_device_sync(False)   # one stream, one set of launches for all learners: plain stream order
     p0 = self.plans[0]
-    assert all(p.algorithm == p0.algorithm and p.B == p0.B for p in self.plans) and p0.algorithm in ('SAC', 'GAIL'), 'the population launches exist for SAC and GAIL learners'
+    assert all(p.algorithm == p0.algorithm and p.B == p0.B for p in self.plans) and p0.algorithm in ('SAC', 'GAIL', 'RED'), 'the population launches exist for SAC, GAIL and RED learners'
+    if p0.algorithm == 'RED':
+      shape = lambda r: (r.state_dim, r.action_dim, r.hidden, r.depth, r.activation, r.state_only, r.batch)   # what sizes il_red_reward_population's tile and grid
+      assert all(shape(p.red) == shape(p0.red) for p in self.plans), 'BatchedPopulationPlan(RED): the discriminators of one population share dims, hidden, depth, activation, state_only and batch'
+      assert not any(p.mix_expert or p.bc_aux for p in self.plans), 'BatchedPopulationPlan(RED): mixed batches / the BC auxiliary step have no population launches'
     if any(getattr(p, 'general', False) for p in self.plans):
       raise NotImplementedError('BatchedPopulationPlan: actor / critic shapes outside depth 2 / ReLU / hidden <= 256 / action_size <= 8 have no population launches (PopulationPlan runs them as independent graph branches)')
     self.algorithm, self.B, self.L, dev = p0.algorithm, p0.B, len(self.plans), p0.rows.device
@@ -1520,9 +1526,12 @@ class BatchedPopulationPlan:
       self.disc_descs = _device_array([p.disc for p in self.plans], dev)
       self.expert_batches = _device_array([p.eb for p in self.plans], dev)
       self.reward_ptrs = torch.tensor([p.rewards.data_ptr() for p in self.plans], dtype=torch.int64, device=dev)
+    if self.algorithm == 'RED':   # every learner's own predictor / target arenas and sigma_1 (set_sigma): read on the device from its descriptor
+      self.red_descs = _device_array([p.red for p in self.plans], dev)
+      self.reward_ptrs = torch.tensor([p.rewards.data_ptr() for p in self.plans], dtype=torch.int64, device=dev)
     self.graph = None
     self._prepared = False
-    self.side = torch.cuda.Stream() if self.algorithm == 'GAIL' and os.environ.get('IL_POP_OVERLAP', '1') != '0' else None
+    self.side = torch.cuda.Stream() if self.algorithm in ('GAIL', 'RED') and os.environ.get('IL_POP_OVERLAP', '1') != '0' else None
 
   def run(self):
     if self.subs is not None:
@@ -1537,20 +1546,27 @@ class BatchedPopulationPlan:
     L, st, p0 = _lib.lib(), _lib.stream_ptr(), self.plans[0]
     prepared = _lib.IL_FLAG_SAC_PREPARED if self._prepared else 0
     _lib.check(L.il_replay_sample_population(_lib.ptr(self.sample_args), self.L, self.B, self.max_row, st))
-    if self.algorithm == 'GAIL' and self.side is not None:
+    if self.algorithm == 'RED':
+      assert not any(p.discriminator.training for p in self.plans), 'BatchedPopulationPlan(RED): discriminator.eval() first (train.py:147)'
+    if self.algorithm in ('GAIL', 'RED') and self.side is not None:
       # The discriminator kernels (48 small workgroups per learner, latency-bound: ~60 us of a ~450 us replay at 32 learners) run on a second stream beside the
       # reward-independent forward kernels of every learner and join before the critic loss. One fork / join per replay (its ~10 us of queue signalling is paid once
       # for the whole population, unlike in the single-learner update where it is why the branches hand over on the device instead).
       main = torch.cuda.current_stream()
       self.side.wait_stream(main)
       with torch.cuda.stream(self.side):
-        _lib.check(L.il_gail_step_population(_lib.ptr(self.disc_descs), _lib.ptr(self.batches), _lib.ptr(self.expert_batches), _lib.ptr(self.reward_ptrs), self.L, C.byref(p0.disc), _lib.stream_ptr()))
+        if self.algorithm == 'GAIL':
+          _lib.check(L.il_gail_step_population(_lib.ptr(self.disc_descs), _lib.ptr(self.batches), _lib.ptr(self.expert_batches), _lib.ptr(self.reward_ptrs), self.L, C.byref(p0.disc), _lib.stream_ptr()))
+        else:   # RED: the eval-mode reward of every learner (8 workgroups per learner at batch 256), the same fork and join
+          _lib.check(L.il_red_reward_population(_lib.ptr(self.red_descs), _lib.ptr(self.batches), _lib.ptr(self.reward_ptrs), self.L, C.byref(p0.red), _lib.stream_ptr()))
       _lib.check(L.il_sac_update_population(_lib.ptr(self.sac_descs), _lib.ptr(self.batches), self.L, C.byref(p0.sac), prepared | _lib.IL_FLAG_SAC_FORWARD_ONLY, st))
       main.wait_stream(self.side)
       _lib.check(L.il_sac_update_population(_lib.ptr(self.sac_descs), _lib.ptr(self.batches), self.L, C.byref(p0.sac), _lib.IL_FLAG_SAC_SKIP_FORWARD, st))
     else:
       if self.algorithm == 'GAIL':
         _lib.check(L.il_gail_step_population(_lib.ptr(self.disc_descs), _lib.ptr(self.batches), _lib.ptr(self.expert_batches), _lib.ptr(self.reward_ptrs), self.L, C.byref(p0.disc), st))
+      if self.algorithm == 'RED':
+        _lib.check(L.il_red_reward_population(_lib.ptr(self.red_descs), _lib.ptr(self.batches), _lib.ptr(self.reward_ptrs), self.L, C.byref(p0.red), st))
       _lib.check(L.il_sac_update_population(_lib.ptr(self.sac_descs), _lib.ptr(self.batches), self.L, C.byref(p0.sac), prepared, st))
     self._prepared = True
 

@@ -670,6 +670,13 @@ int il_red_step(const il_red* d, const il_batch* expert, const float* mask_in, c
  * out_pred, out_target [n, D] (what set_sigma feeds to the pairwise distance + median; set_sigma runs in TRAIN mode, train.py:128: training = 1 + masks). */
 int il_red_forward(const il_red* d, const il_batch* batch, int32_t training, const float* mask_in, const float* mask_h1, const float* mask_h2, uint32_t noise_offset,
                    float* out_reward, float* out_pred, float* out_target, il_stream_t stream);
+/* Population axis: predict_reward (eval mode, whatever p_in / p say) of n_learners RED discriminators of one shape in ONE launch, grid (ceil(batch / 32), n_learners);
+ * rewards_out_dev[l] -> float[batch], every value bit-identical to il_red_forward(&desc_l, &batch_l, training = 0). Conventions of il_gail_step_population: device arrays
+ * indexed by the learner id and one host descriptor for the shape (state_dim, action_dim, state_only, hidden, depth, activation, batch). What a learner owns is read from
+ * ITS device descriptor: predictor, target and sigma_1 (set_sigma gives every seed its own bandwidth). No embeddings are written. IL_ERR_ARG for a null array,
+ * n_learners outside 1..65535 or a shape outside il_red_forward's limits; IL_ERR_UNSUPPORTED when a tile needs more than 160 KiB of LDS; nothing is launched then. */
+int il_red_reward_population(const il_red* descs_dev, const il_batch* batches_dev, float* const* rewards_out_dev, int32_t n_learners, const il_red* shape_host,
+                             il_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * DRIL (reference models.py:84-120: SoftActor built from conf/algorithm/DRIL.yaml's discriminator config = Dropout(p_in) -> Linear(S,H)

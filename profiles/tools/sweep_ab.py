@@ -6,7 +6,8 @@
   rate      aggregate env-steps/s = L * steps / training_time; training_time is what check_time_usage=true reports (everything behind the construction of environments,
             expert data and networks: plan set-up, the loop, every launch drained before the clock stops; evaluation is off under check_time_usage)
 (c) counts as faster than (b) only if its median beats (b)'s by more than (b)'s spread (max - min) of this job; the default of +sweep.schedule follows from that at both L.
-  python profiles/tools/sweep_ab.py [--steps 4000] [--repeats 5] [--learners 4 16] [--algorithms GAIL SAC] [--out profiles/sweep_ab.txt]"""
+  python profiles/tools/sweep_ab.py [--steps 4000] [--repeats 5] [--learners 4 16] [--algorithms GAIL SAC] [--out profiles/sweep_ab.txt]
+(--algorithms RED: the same three forms with the predictor's pretraining cut to 100 iterations per learner)"""
 import argparse
 import os
 import sys
@@ -35,8 +36,9 @@ def say(text):
 
 
 def overrides(algorithm, steps, start):
+  extra = ['imitation.pretraining.iterations=100'] if algorithm == 'RED' else []   # (the predictor's pretraining sits in front of the clock: kept short, the job measures the loop)
   return [f'algorithm={algorithm}', 'env=halfcheetah', f'steps={steps}', f'training.start={start}', 'training.batch_size=256', 'check_time_usage=true', 'logging.interval=1000',
-          '+synthetic_env.dataset_trajectories=6']
+          '+synthetic_env.dataset_trajectories=6'] + extra
 
 
 def run_form(form, algorithm, L, steps, start, out_dir):

@@ -412,15 +412,16 @@ def _fused_shape(model_cfg) -> bool:
 def sweep_fallback_reason(cfg):
   """None when a seed sweep of this configuration can train as one population (what il.BatchedPopulationPlan and il.PopulationActingWorker take); otherwise the reason
   its jobs run one after another through train()."""
-  if cfg.algorithm not in ('SAC', 'GAIL'):
-    return f'algorithm={cfg.algorithm} has no population launches (SAC and GAIL have)'
+  if cfg.algorithm not in ('SAC', 'GAIL', 'RED'):
+    return f'algorithm={cfg.algorithm} has no population launches (SAC, GAIL and RED have)'
   if not (_fused_shape(cfg.reinforcement.actor) and _fused_shape(cfg.reinforcement.critic)):
     return 'an actor / critic shape outside depth 2, ReLU, hidden 64..256 in multiples of 64 has no population launches'
   if int(cfg.reinforcement.actor.hidden_size) != int(cfg.reinforcement.critic.hidden_size):
     return 'actor and critic of different hidden sizes have no population launches'
   if cfg.training.batch_size % 16 != 0:
     return f'training.batch_size={cfg.training.batch_size} is not a multiple of 16'
-  if cfg.imitation.mix_expert_data != 'none':
+  # RED with prefill_memory: the expert rows are moved into the agent ring once, in front of the loop (train.py:134); nothing is edited between the launches
+  if cfg.imitation.mix_expert_data != 'none' and not (cfg.algorithm == 'RED' and cfg.imitation.mix_expert_data == 'prefill_memory'):
     return f'imitation.mix_expert_data={cfg.imitation.mix_expert_data} edits the batches between the launches'
   if cfg.imitation.bc_aux_loss:
     return 'imitation.bc_aux_loss adds an actor step per update that the population launches do not have'
@@ -521,11 +522,27 @@ def train_sweep(cfgs, prefixes):
     if cfg.algorithm == 'GAIL':
       ln.discriminator = il.GAILDiscriminator(S, A, cfg.imitation, cfg.reinforcement.discount)
       ln.discriminator_optimiser = il.AdamW(ln.discriminator, lr=cfg.imitation.learning_rate, weight_decay=cfg.imitation.weight_decay)
+    elif cfg.algorithm == 'RED':
+      ln.discriminator = il.REDDiscriminator(S, A, cfg.imitation)
+      ln.discriminator_optimiser = il.AdamW(ln.discriminator, lr=cfg.imitation.learning_rate, weight_decay=cfg.imitation.weight_decay)
     ln.metrics = dict(train_steps=[], train_returns=[], test_steps=[], test_returns=[], test_returns_normalized=[], update_steps=[], predicted_rewards=[], alphas=[], entropies=[], Q_values=[])
     ln.score = []
     start_time += time.time() - built
+    began = time.time()
     if cfg.bc_pretraining.iterations > 0:
       pretrain_bc(cfg, ln.actor, ln.expert_memory, S, A)   # one PretrainPlan per learner
+    if cfg.algorithm == 'RED':   # train.py:114-134 in train()'s order, under this learner's seeds: predictor pretraining, its own bandwidth, the prefill
+      if pretraining_schedule(cfg) == 'plan' and cfg.imitation.pretraining.iterations > 0:
+        il.PretrainPlan('RED', ln.discriminator, ln.discriminator_optimiser, ln.expert_memory, B, torch.Generator().manual_seed(cfg.seed)).run(cfg.imitation.pretraining.iterations)
+      else:
+        for batch in expert_batches(cfg, ln.expert_memory, S, A, cfg.imitation.pretraining.iterations):
+          il.target_estimation_update(ln.discriminator, batch, ln.discriminator_optimiser)
+      ln.discriminator.set_sigma(ln.expert_memory['states'][:B], ln.expert_memory['actions'][:B])
+      if cfg.check_time_usage:   # what train() reports: this learner's pretraining on its own, and a training_time that starts behind it
+        ln.metrics['pre_training_time'] = time.time() - began
+        start_time += ln.metrics['pre_training_time']
+      if cfg.imitation.mix_expert_data == 'prefill_memory': ln.memory.transfer_transitions(ln.expert_memory)
+      ln.discriminator.eval()   # train.py:147, in front of the plan: from here on the predictor's dropout is off
     ln.plan = il.UpdatePlan(cfg.algorithm, ln.actor, ln.critic, ln.log_alpha, ln.target_critic, ln.memory, ln.actor_optimiser, ln.critic_optimiser, ln.temperature_optimiser, B,
                             cfg.reinforcement.discount, entropy_target, cfg.reinforcement.polyak_factor, expert_memory=ln.expert_memory, discriminator=ln.discriminator,
                             discriminator_optimiser=ln.discriminator_optimiser, imitation_cfg=cfg.imitation if cfg.algorithm == 'GAIL' else None, overlap=False, learner_id=i)
@@ -625,7 +642,7 @@ def train_sweep(cfgs, prefixes):
       _, trajectories = evaluate_agent(ln.actor, ln.eval_env, cfg.evaluation.episodes, return_trajectories=True, render=cfg.render)
       torch.save(trajectories, f'{ln.prefix}trajectories.pth')
     torch.save(dict(actor=ln.actor.state_dict(), critic=ln.critic.state_dict(), log_alpha=ln.log_alpha), f'{ln.prefix}agent.pth')
-    if cfg.algorithm == 'GAIL': torch.save(ln.discriminator.state_dict(), f'{ln.prefix}discriminator.pth')   # train.py:238
+    if cfg.algorithm in ('GAIL', 'RED'): torch.save(ln.discriminator.state_dict(), f'{ln.prefix}discriminator.pth')   # train.py:238
     torch.save(m, f'{ln.prefix}metrics.pth')
     scores.append(float(np.mean(ln.score)) if ln.score else float('nan'))
   return scores
