@@ -85,6 +85,23 @@ class _Mailbox:
         self._t0 = time.perf_counter()
 
 
+def _drain(box, launched: bool, what: str):
+  """Before a worker lets go of its append mailbox: wait for the echo of the last post if a launch for it has been issued. The mailbox is pinned host memory that a queued
+  launch reads through a raw pointer; once the tensor is freed torch's host allocator hands the block to the next pinned allocation of that size at once (it knows of no
+  stream that uses it: tests/test_acting_mailbox_lifetime_cpu.py shows the reuse on the GPU), and that allocation's fill then rewrites the payload under the launch - a
+  worker dropped right behind an asynchronous `append` lost part of its last next_state that way. The act mailbox needs no such wait: `act` and `step` return with its
+  echo. Only `append` (the exact schedule) marks a launch: the overlap schedule's posts are consumed by `enqueue_append` launches that a plan may have captured or recorded
+  (no echo comes until it replays them), and train.py keeps such a worker alive until the plan has been joined."""
+  if box is None or not launched: return
+  word = getattr(box, 'word', None)
+  try:
+    if word is None:                                                       # a _MailboxBlock: every learner's echo
+      if getattr(box, 'words', None) is not None: box.wait(what)
+    elif word and box.host[box.o_echo] != word: box.wait(word, what)
+  except RuntimeError:   # no echo within the bound (a failed launch): nothing left to protect, and __del__ must not raise
+    pass
+
+
 def _row(x) -> np.ndarray:
   if torch.is_tensor(x):
     x = x.detach().to('cpu', torch.float32).numpy()
@@ -219,7 +236,11 @@ class ActingWorker:
     if box.word: box.wait(box.word, 'il_act_step(append)')  # normally already echoed: the act in between ran after it on the same stream
     box.post(self._next_seq(), PENDING | NO_ACTION | self._reward_flag | (WRAP_ABSORBING if wrap else 0), float(reward), float(terminal), float(timeout), float(step), next_obs=_row(next_obs))
     self._launch(box, acts=False, appends=True)
+    self._append_launched = True
     self._mirror_append(bool(terminal), bool(timeout), wrap)
+
+  def __del__(self):
+    _drain(getattr(self, '_append_box', None), getattr(self, '_append_launched', False), 'il_act_step(append)')
 
   # --- fused schedule
   def step(self, step, next_obs, reward, terminal: bool, timeout: bool, obs=None, greedy: bool = False) -> torch.Tensor:
@@ -416,7 +437,11 @@ class PopulationActingWorker:
     self._post_transition(box, rows, step, next_obs, reward, terminal, timeout)
     box.commit(self._next_seq(), flags)
     self._launch(box)
+    self._append_launched = True
     self._mirror_appends(rows, terminal, timeout, wrap)
+
+  def __del__(self):
+    _drain(getattr(self, '_append_box', None), getattr(self, '_append_launched', False), 'il_act_step_population(append)')
 
   # --- fused schedule
   def step(self, step, next_obs, reward, terminal, timeout, obs=None, greedy: bool = False) -> torch.Tensor:

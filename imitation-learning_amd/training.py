@@ -52,12 +52,13 @@ def _f32(t: Optional[Tensor], device) -> Optional[Tensor]:
 
 
 def sac_descriptor(actor: SoftActor, critic: TwinCritic, log_alpha: Tensor, target_critic: TwinCritic, batch_size: int, actor_optimiser: AdamW, critic_optimiser: AdamW,
-                   temperature_optimiser: Adam, discount: float, entropy_target: float, polyak_factor: float, tag=None, seed_offset: int = 0) -> _lib.Sac:
+                   temperature_optimiser: Adam, discount: float, entropy_target: float, polyak_factor: float, tag=None, seed_offset: int = 0, general: Optional[bool] = None) -> _lib.Sac:
+  """general: lay the workspace out for csrc/general.hip; None = decided by the networks' shape alone (what every captured plan asks for)."""
   S, A, H, dev = actor.state_size, actor.action_size, actor.hidden, actor.flat.device
   assert _lib.on_device(log_alpha) and log_alpha.dtype == torch.float32
   if isinstance(actor, DropoutSoftActor):
     raise NotImplementedError('sac_update: a dropout policy ensemble (DRIL discriminator) is not a reinforcement-learning actor of the HIP path')
-  if _general_shape(actor, critic):   # csrc/general.hip: its own (larger) scratch layout; reinforcement.actor and reinforcement.critic may differ in every dimension
+  if _general_shape(actor, critic) if general is None else general:   # csrc/general.hip: its own (larger) scratch layout; reinforcement.actor and reinforcement.critic may differ in every dimension
     floats = int(_lib.lib().il_sac_workspace_floats_general(S, A, H, actor.depth, critic.hidden, critic.depth, batch_size))
   else:
     assert critic.hidden == H
@@ -87,17 +88,24 @@ def _general_shape(actor, critic=None) -> bool:
   return bool(getattr(actor, 'general', False) or (critic is not None and getattr(critic, 'general', False)))
 
 
+def _general_call(actor, critic, batch_size: int) -> bool:
+  """The per-function entry points: general shapes, and the fused shape at a batch that is not whole 16-row tiles (il_sac_update / il_bc_step refuse it) - the same
+  parameter layout (torch order, twin critics at a stride rounded up to 4 floats), run by csrc/general.hip, which takes any batch >= 1."""
+  return _general_shape(actor, critic) or batch_size % 16 != 0
+
+
 def sac_update(actor: SoftActor, critic: TwinCritic, log_alpha: Tensor, target_critic: TwinCritic, transitions: Dict[str, Tensor], actor_optimiser: AdamW,
                critic_optimiser: AdamW, temperature_optimiser: Adam, discount: float, entropy_target: float, polyak_factor: float, *,
                eps_next: Optional[Tensor] = None, eps_cur: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
   """One SAC update (reference training.py:14-54). Returns (log_probs[B], min(Q1,Q2)[B]) like the reference."""
   dev = actor.flat.device
   B = transitions['states'].size(0)
-  d = sac_descriptor(actor, critic, log_alpha, target_critic, B, actor_optimiser, critic_optimiser, temperature_optimiser, discount, entropy_target, polyak_factor)
+  general = _general_call(actor, critic, B)
+  d = sac_descriptor(actor, critic, log_alpha, target_critic, B, actor_optimiser, critic_optimiser, temperature_optimiser, discount, entropy_target, polyak_factor, general=general)
   b = batch_desc(transitions)
   logp, q = torch.empty(B, device=dev), torch.empty(B, device=dev)
   e1, e2 = _f32(eps_next, dev), _f32(eps_cur, dev)
-  if _general_shape(actor, critic):
+  if general:
     from .models import ACTIVATION_IDS
     _lib.check(_lib.lib().il_sac_update_general(C.byref(d), C.byref(b), actor.depth, ACTIVATION_IDS[actor.activation], critic.hidden, critic.depth, ACTIVATION_IDS[critic.activation],
                                                 _lib.ptr(e1), _lib.ptr(e2), _lib.ptr(logp), _lib.ptr(q), 0, _lib.stream_ptr()))
@@ -117,7 +125,7 @@ def behavioural_cloning_update(actor: SoftActor, expert_transition: Dict[str, Te
     t.setdefault(k, t['weights'] if k != 'next_states' else t['states'])
   b = batch_desc(t)
   S, A, H, B = actor.state_size, actor.action_size, actor.hidden, b.n
-  if _general_shape(actor):
+  if _general_call(actor, None, B):
     from .models import ACTIVATION_IDS
     ws, loss, od = actor._general_workspace(B), torch.empty(1, device=dev), actor_optimiser.desc()
     _lib.check(_lib.lib().il_bc_step_general(_lib.ptr(actor.flat), _lib.ptr(actor_optimiser.grad), C.byref(od), S, A, H, actor.depth, ACTIVATION_IDS[actor.activation], C.byref(b), _lib.ptr(ws),
@@ -1338,7 +1346,7 @@ class PretrainPlan:
     if orders is not None:
       self.orders = orders.to('cpu', torch.int32).reshape(-1, B).contiguous()
       if self.orders.size(0) < 1: raise ValueError('PretrainPlan: empty orders')
-    self.general = kind == 'BC' and _general_shape(model)
+    self.general = kind == 'BC' and _general_call(model, None, B)   # (the fused il_bc_epoch_steps runs whole 16-row tiles only, so its B // 16 loss partials below are one per tile)
     # ---- the ring as an il_batch read through the order table (the form UpdatePlan._ring_batches builds for il_sac_update_gather)
     self.table = torch.zeros(2 * self.chunk, B, dtype=torch.int32, device=dev)
     self.staging = torch.zeros(self.chunk, B, dtype=torch.int32).pin_memory()

@@ -32,6 +32,26 @@ EDGE_DIMS = ((11, 3), (17, 6), (111, 8),
              (255, 8), (129, 1))
 
 
+# Batch sizes away from the multiples of 16 the rest of the suite runs, where the kernels' row tiles get ragged tails. Every B mod 4 occurs (the 4-row vector groups
+# `row0 + 4 * g` over the padded Bp: 1 and 2 and 3 rows in the last group) and both sides of 16, 32, 64 and 128:
+# 1, 2, 3 - one tile with 15, 14, 13 padded rows, one row group; a batch of ONE row (means over B = 1, a 1 x 1 Gram matrix);
+# 15, 17 - one row short of a 16-row tile (IL_TILE_R) and one row into the second tile;
+# 31, 33 - the same around 32: the 32-row block jobs of dw_block.hpp and two-tile workgroups;
+# 63, 65 - around 64: one row per lane of a wave, and the 64-row tiles of the GMMIL / PWIL kernels;
+# 127, 129, 130 - around 128 (DWS_ROWS: general.hip takes the 32 x 32 block jobs only when the padded batch is a multiple of 128; 127 pads to it, 129 / 130 leave it)
+# and 256-thread row kernels at half a workgroup; 130 = 2 mod 4 above 128.
+EDGE_BATCHES = (1, 2, 3, 15, 17, 31, 33, 63, 65, 127, 129, 130)
+
+# Hidden widths per kernel family, at the edges of what its entry point admits and around its 16- and 64-wide tiles (tests/test_size_edges_gpu.py):
+EDGE_HIDDEN_GAIL = (16, 48, 240, 512)                            # il_disc: multiples of 16 in 16 .. 512 (one k-block, three, 15, and the limit; its LDS check admits 512 at S + A = 14)
+EDGE_HIDDEN_SHAPED = (1, 3, 17, 31, 65, 255, 256)                # il_disc_shaped: 1 .. 256
+EDGE_HIDDEN_DEEP = (2, 3, 17, 31, 65, 127, 128)                  # il_disc_deep, il_disc_shaped_deep: 2 .. 128
+EDGE_HIDDEN_RED = (2, 6, 30, 66, 254, 256)                       # il_red, il_dril: even widths in 2 .. 256
+EDGE_HIDDEN_GENERAL = (1, 3, 17, 33, 63, 65, 100, 127, 257)      # csrc/general.hip, layer at a time: 1 .. 2048
+EDGE_HIDDEN_GENERAL_ACTOR = (3, 33, 100, 257)
+EDGE_HIDDEN_FUSED = (64, 128, 192, 256)                          # csrc/sac.hip: the lane-ordered copies at multiples of 64
+
+
 def edge_dims(max_state=None, max_input=None):
   """The EDGE_DIMS within a kernel family's limits on S and on S + A."""
   return tuple((S, A) for S, A in EDGE_DIMS if (max_state is None or S <= max_state) and (max_input is None or S + A <= max_input))
@@ -268,7 +288,7 @@ def dril_case(seed, env, hidden, batch, steps, p_in=0.1, p=0.1, depth=1, activat
   keep = lambda shape, pr: (rs.uniform(size=shape) >= pr).astype(f32)
   batches = [transitions(rs, batch, S, A, state_shift=0.5, weighted=True) for _ in range(steps)]
   for b in batches:
-    b['actions'] = np.clip(b['actions'], -0.97, 0.97).astype(f32); b['actions'][:2] = np.array([1.0, -1.0], f32)[:, None]  # exercise the clamp
+    b['actions'] = np.clip(b['actions'], -0.97, 0.97).astype(f32); b['actions'][:2] = np.array([1.0, -1.0], f32)[:min(batch, 2), None]  # exercise the clamp (in the rows a batch of one has)
   expert, query = transitions(rs, 80, S, A, state_shift=0.5), transitions(rs, 37, S, A)
   c = dict(S=S, A=A, H=hidden, B=batch, p_in=p_in, p=p, depth=depth, activation=activation, params=params, batches=batches, m0=[keep((batch, S), p_in) for _ in range(steps)],
            m1=[keep((batch, hidden), p) for _ in range(steps)], expert=expert, query=query, e_m0=keep((80 * 5, S), p_in), e_m1=keep((80 * 5, hidden), p),

@@ -811,10 +811,14 @@ def test_unsupported_shapes_and_options_fail_loudly():
     il.SoftActor(18, 6, Cfg(hidden_size=256, depth=2, activation='gelu'))
   with pytest.raises(NotImplementedError):
     il.TwinCritic(18, 6, Cfg(hidden_size=256, depth=2, activation='relu', dropout=0.1))
-  c = gi.sac_case(3, 'halfcheetah', 256, 24, 1)   # batch not a multiple of the 16-row tile
-  actor, critic, target, log_alpha, ao, co, to = make_sac(c)
-  with pytest.raises(RuntimeError, match='multiple of 16'):
-    il.sac_update(actor, critic, log_alpha, target, tbatch(c['batches'][0]), ao, co, to, 0.99, -6.0, 0.995)
+  c = gi.sac_case(3, 'halfcheetah', 256, 24, 1)   # batch not a multiple of the 16-row tile: the fused entry point refuses it (il.sac_update routes such a batch to
+  actor, critic, target, log_alpha, ao, co, to = make_sac(c)   # csrc/general.hip: tests/test_size_edges_gpu.py), and so does every plan that reaches it directly
+  d = il_training.sac_descriptor(actor, critic, log_alpha, target, 24, ao, co, to, 0.99, -6.0, 0.995, general=False)
+  b, out = il_training.batch_desc(tbatch(c['batches'][0])), torch.empty(2, 24, device=DEV)
+  before = N(actor.flat), N(critic.flat)
+  with pytest.raises(RuntimeError, match='il_sac: batch=24 must be a positive multiple of 16'):
+    _lib.check(_lib.lib().il_sac_update(C.byref(d), C.byref(b), None, None, _lib.ptr(out[0]), _lib.ptr(out[1]), 0, _lib.stream_ptr()))
+  assert np.array_equal(N(actor.flat), before[0]) and np.array_equal(N(critic.flat), before[1])
   g = gi.gail_case(31)
   d, _, icfg = make_disc(g)
   icfg.update(loss_function='Hinge', grad_penalty=1.0, entropy_bonus=0.0)

@@ -101,3 +101,28 @@ def test_seed_sweep_graph_replays_equal_direct_launches_on_the_emulated_kernels(
   tp = _bodies(monkeypatch)
   monkeypatch.chdir(tmp_path)
   tp.test_seed_sweep_graph_replays_equal_direct_launches(tmp_path, monkeypatch, short=SHORT)
+
+
+def test_seed_sweep_at_a_ragged_batch_trains_job_after_job_on_the_emulated_kernels(monkeypatch, tmp_path, capsys):
+  """`python train.py -m seed=3,4 algorithm=SAC training.batch_size=100`: the population launches take whole 16-row tiles only, so the sweep falls back to one train() per
+  job (tests/test_sweep_config_cpu.py checks the grouping) - and each job must train to the end: checkpoints, finite scores, updates logged at the batch asked for."""
+  import numpy as np
+  import torch
+  _bodies(monkeypatch)
+  sys.path.insert(0, os.path.dirname(HERE))
+  import train
+  monkeypatch.chdir(tmp_path)
+  root, scores = train.multirun(['-m', 'seed=3,4', 'algorithm=SAC', 'env=hopper', 'steps=50', 'training.start=40', 'evaluation.interval=25', 'evaluation.episodes=1', 'logging.interval=2',
+                                 '+synthetic_env.max_episode_steps=20', '+synthetic_env.dataset_trajectories=6', 'training.batch_size=100', 'reinforcement.actor.hidden_size=64',
+                                 'reinforcement.critic.hidden_size=64'], stamp='ragged')
+  err = capsys.readouterr().err
+  assert err.count('runs on its own, one job after another: training.batch_size=100 is not a multiple of 16') == 2
+  assert len(scores) == 2 and np.isfinite(scores).all()
+  actors = []
+  for j in (0, 1):
+    agent = torch.load(os.path.join(root, str(j), 'agent.pth'), weights_only=False)
+    metrics = torch.load(os.path.join(root, str(j), 'metrics.pth'), weights_only=False)
+    assert all(torch.isfinite(v).all() for v in agent['actor'].values()) and len(metrics['update_steps']) >= 2
+    assert all(np.isfinite(q).all() and q.shape == (100,) for q in metrics['Q_values'])
+    actors.append(agent['actor'])
+  assert any(not torch.equal(v, actors[1][k]) for k, v in actors[0].items())   # two seeds, two learners

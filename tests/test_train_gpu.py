@@ -79,6 +79,28 @@ def test_train_runs(tmp_path, args):
       assert 'g.0.parametrizations.weight.original' in disc and 'g.2.parametrizations.weight.0._v' in disc
 
 
+@pytest.mark.parametrize('args', [['algorithm=SAC', 'env=halfcheetah'], ['algorithm=GAIL', 'env=hopper']], ids=['SAC', 'GAIL'])
+def test_train_runs_at_a_batch_that_is_not_whole_tiles(tmp_path, args):
+  """`training.batch_size=100` with the default (fused-shape) networks: train.py takes its per-function path, whose SAC update runs csrc/general.hip at such a batch
+  (it used to stop at the first update with `il_sac: batch=100 must be a positive multiple of 16`)."""
+  sys.path.insert(0, ROOT)
+  import train
+  from imitation_learning_amd import config
+  os.chdir(tmp_path)
+  cfg = config.compose(args + COMMON[:-1] + ['training.batch_size=100'])
+  assert cfg.training.batch_size == 100
+  score = train.train(cfg)
+  assert np.isfinite(score)
+  agent = torch.load(tmp_path / 'agent.pth', weights_only=False)
+  assert 'actor' in agent and all(torch.isfinite(v).all() for v in agent['actor'].values())
+  metrics = torch.load(tmp_path / 'metrics.pth', weights_only=False)
+  assert 'critic_1.critic.0.weight' in agent['critic'] and len(metrics['update_steps']) >= 2
+  assert all(np.isfinite(q).all() and q.shape == (100,) for q in metrics['Q_values'])
+  if cfg.algorithm == 'GAIL':
+    disc = torch.load(tmp_path / 'discriminator.pth', weights_only=False)
+    assert 'g.0.parametrizations.weight.original' in disc and 'g.2.parametrizations.weight.0._v' in disc
+
+
 def test_unsupported_configurations_fail_loudly():
   """Every algorithm= of the reference runs; option combinations without a kernel raise instead of silently running something else."""
   sys.path.insert(0, ROOT)

@@ -3,7 +3,7 @@
 
 Drives the loop of reference train.py:26-243 (act -> store -> [update block] -> evaluate -> save) on the MI355X path:
 the update block (train.py:171-203) is `UpdatePlan` (one captured hipGraph replay per step, every algorithm) or the per-function HIP entry
-points (GAIL variants with per-update host inputs, batch sizes that are not a multiple of 16).  Hydra is replaced by `imitation_learning_amd.config.compose`
+points (GAIL variants with per-update host inputs, batch sizes that are not a multiple of 16 - where the default networks run csrc/general.hip).  Hydra is replaced by `imitation_learning_amd.config.compose`
 (same keys, same precedence).  Supported on the HIP path: SAC, GAIL (BCE loss), GMMIL, PWIL, AdRIL (and SQIL via update_freq=0), RED, DRIL, BC - every algorithm= of the reference.
 Acting goes through `il.ActingWorker` for every algorithm (`+acting.schedule=exact|fused|overlap`, default exact; `per_function` keeps the reference's call sequence). PWIL's
 reward is computed on the device in front of each append and its expert relabel (mix_expert_data != none) is one library call; `+pretraining.schedule=per_function` keeps
