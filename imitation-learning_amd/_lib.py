@@ -102,6 +102,10 @@ class ActLearner(C.Structure):   # il_act_learner: one learner of il_act_step_po
   _fields_ = [('actor', C.c_void_p), ('mailbox', C.c_void_p), ('carry', C.c_void_p), ('ring', C.c_void_p), ('ring_state', C.c_void_p), ('noise_seed', C.c_uint64)]
 
 
+class GmmilLearner(C.Structure):   # il_gmmil_learner: one learner of il_gmmil_reward_population (a device array of these)
+  _fields_ = [('policy', Batch), ('expert', Batch), ('gamma_1', C.c_float), ('gamma_2', C.c_float), ('workspace', C.c_void_p), ('out_rewards', C.c_void_p)]
+
+
 class SampleArgs(C.Structure):
   _fields_ = [('state', C.c_void_p),
               ('ring_state_a', C.c_void_p), ('ring_a', C.c_void_p), ('capacity_a', C.c_int64), ('row_floats_a', C.c_int32), ('idx_a', C.c_void_p), ('rows_a', C.c_void_p),
@@ -226,6 +230,7 @@ _SIGNATURES = {
     'il_gail_reward': (C.c_int, [C.POINTER(Disc), C.POINTER(Batch), _P, _P, _P, _P]),
     'il_gmmil_workspace_floats': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     'il_gmmil_reward': (C.c_int, [C.POINTER(Batch), C.POINTER(Batch), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P, _P, _P, C.c_int64, _P]),
+    'il_gmmil_reward_population': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _P]),
     'il_gmmil_sqdist': (C.c_int, [C.POINTER(Batch), C.POINTER(Batch), C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
     'il_pwil_reset': (C.c_int, [C.POINTER(Pwil), _P]),
     'il_pwil_scratch_floats': (C.c_int64, [C.c_int32, C.c_double]),

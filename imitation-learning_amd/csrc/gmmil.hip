@@ -548,13 +548,14 @@ __device__ __forceinline__ float gmf_weight_share(const il_batch& b, int tid, co
   for (int i = 1024 + tid; i < b.n; i += 256) s += gload(b.weights + (size_t)i * b.ld_weights);
   return s;
 }
+// The body of k_gmmil_mfma and k_gmmil_mfma_pop: `bid` is the workgroup's number among the (row block, column block) pairs of ONE reward - blockIdx.x of the single learner's
+// launch, the block number within its learner in the population's. Everything else the two kernels share to the instruction, so a learner's rewards are the same bits.
+// (The batches come by reference: by value, hipcc moved the single learner's kernel-argument loads behind its first time stamp.)
 template <int NKQ, bool LANES, int COLS>
-__global__ __launch_bounds__(256) void k_gmmil_mfma(il_batch pol, il_batch exp, int S, int D, float g1, float g2, float* __restrict__ ws_,
-                                                    float* __restrict__ out_r, float* __restrict__ out_sim, float* __restrict__ out_self) {
+__device__ __forceinline__ void gmmil_mfma_body(il_batch& pol, il_batch& exp, int S, int D, float g1, float g2, float* __restrict__ ws_, float* __restrict__ out_r,
+                                                float* __restrict__ out_sim, float* __restrict__ out_self, const int bid, float* smem) {
   using L = GmfLds<NKQ, COLS>;
   constexpr int DP = L::DP, LD = L::LD, NQ = DP / 4, YP = 256 / COLS, HQ = NQ / YP;   // a column's features are split over YP threads, HQ 16-byte lanes each
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  IL_ST_BEGIN(IL_ST_GMMIL);
   IL_TL(2, 0);
   float* Ys = smem + L::ys; float* cs = smem + L::cs; float* cpart = smem + L::cpart; float* nyh = smem + L::nyh; float* wys = smem + L::wys;
   float* nxs = smem + L::nxs; float* red = smem + L::red; float* ps = smem + L::ps;
@@ -565,9 +566,9 @@ __global__ __launch_bounds__(256) void k_gmmil_mfma(il_batch pol, il_batch exp, 
   // workgroup -> (row block, column block): consecutive workgroup ids go to the eight XCDs in turn, so the 32 workgroups an XCD hosts of every 256 are given an 8 x 4 patch
   // of the block grid - its L2 then fetches 8 row blocks + 4 column blocks instead of 2 row blocks + every column block (1 MB -> 0.5 MB per XCD at B = 1024)
   const int nI = w.b1p / GMF_ROWS, nJ = nE + nX;
-  int it = (int)blockIdx.x % nI, jy = (int)blockIdx.x / nI;
+  int it = bid % nI, jy = bid / nI;
   if (nI % 8 == 0 && nJ % 4 == 0 && ((nI / 8) * (nJ / 4)) % 8 == 0) {
-    const int xcd = (int)blockIdx.x & 7, slot = (int)blockIdx.x >> 3, patch = (slot >> 5) * 8 + xcd, in = slot & 31;
+    const int xcd = bid & 7, slot = bid >> 3, patch = (slot >> 5) * 8 + xcd, in = slot & 31;
     it = (patch % (nI / 8)) * 8 + (in & 7); jy = (patch / (nI / 8)) * 4 + (in >> 3);
   }
   const int mat = jy >= nE ? 1 : 0, jb = jy - (mat ? nE : 0);   // mat 0: policy vs expert, 1: policy vs policy
@@ -743,7 +744,30 @@ __global__ __launch_bounds__(256) void k_gmmil_mfma(il_batch pol, il_batch exp, 
     if (out_sim) out_sim[i] = sim;
     if (out_self) out_self[i] = self;
   }
+}
+template <int NKQ, bool LANES, int COLS>
+__global__ __launch_bounds__(256) void k_gmmil_mfma(il_batch pol, il_batch exp, int S, int D, float g1, float g2, float* __restrict__ ws_,
+                                                    float* __restrict__ out_r, float* __restrict__ out_sim, float* __restrict__ out_self) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  IL_ST_BEGIN(IL_ST_GMMIL);
+  gmmil_mfma_body<NKQ, LANES, COLS>(pol, exp, S, D, g1, g2, ws_, out_r, out_sim, out_self, (int)blockIdx.x, smem);
   IL_ST_END(IL_ST_GMMIL);
+}
+// ---------------------------------------------------------------------------------------------
+// k_gmmil_mfma_pop (il_gmmil_reward_population): the rewards of a population of learners (seed sweeps) in one launch. At the shipped batch of 128 one reward is 16 workgroups
+// on a 256-CU part; ten seeds are 160. The shape (n1, n2, S, D - hence NKQ, COLS and the W workgroups of one reward) is the host's, the same for every learner; what a learner
+// owns comes from ITS entry of the device array: both batches, the two bandwidths, its workspace (own partial sums, own self-resetting arrival counters: a learner's last
+// arriver counts that learner's tickets only) and its output. LANES is the caller's promise for all learners (it changes how operands are requested, never a value).
+// Grid (W, learners): the learner on blockIdx.y, the learner's block on blockIdx.x, which gmmil_mfma_body orders as k_gmmil_mfma does. (An XCD-local form - the grid
+// flattened and dealt so that XCD x hosts learners x, x + 8, ... whole, each learner's operands in ONE L2 - was built and timed against this one: no difference beyond the
+// spread at batch 128 with 10 and 16 learners, and 88 against 49 us at 4 learners of batch 1024, where four XCDs did all the work: profiles/gmmil_population_mapping.txt.)
+// ---------------------------------------------------------------------------------------------
+template <int NKQ, bool LANES, int COLS>
+__global__ __launch_bounds__(256) void k_gmmil_mfma_pop(const il_gmmil_learner* __restrict__ learners, int n1, int n2, int S, int D) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  il_gmmil_learner d = learners[blockIdx.y];
+  d.policy.n = n1; d.expert.n = n2;   // the shape is the host's: what sized the grid bounds every access
+  gmmil_mfma_body<NKQ, LANES, COLS>(d.policy, d.expert, S, D, d.gamma_1, d.gamma_2, as_global(d.workspace), as_global(d.out_rewards), nullptr, nullptr, (int)blockIdx.x, smem);
 }
 static int gmmil_mfma_on(int D) {   // IL_GMMIL_MFMA=0: the direct-difference launches (k_gmmil_sx, k_gmmil_direct)
   static const int on = [] { const char* e = getenv("IL_GMMIL_MFMA"); return e && e[0] == '0' ? 0 : 1; }();
@@ -818,6 +842,54 @@ extern "C" int il_gmmil_reward(const il_batch* pol, const il_batch* exp, int32_t
   }
   IL_CHECK_LAUNCH("il_gmmil_reward");
   return IL_OK;
+}
+
+template <int NKQ, bool LANES, int COLS>
+static int gmmil_pop_launch_(const il_gmmil_learner* learners, int n_learners, int n1, int n2, int S, int D, hipStream_t st) {
+  const GmmilWs w = gmmil_ws(n1, n2, D);
+  const size_t lds = (size_t)GmfLds<NKQ, COLS>::total * sizeof(float);
+  const int nE = (w.b2p + COLS - 1) / COLS, nX = (w.b1p + COLS - 1) / COLS, W = (w.b1p / GMF_ROWS) * (nE + nX);
+  const int64_t wgs = (int64_t)n_learners * W;
+  IL_CHECK_ARG(wgs <= 0x7fffffffll, "il_gmmil_reward_population: %lld workgroups (%d learners x %d) exceed a grid dimension's range", (long long)wgs, n_learners, W);
+  auto kern = k_gmmil_mfma_pop<NKQ, LANES, COLS>;   // (one identifier: the host emulator's launch macro splits its arguments at commas)
+  if (int rc = gmmil_ensure_lds(kern, lds)) return rc;
+  IL_TRACE("k_gmmil_tile_population", st);
+  kern<<<dim3(W, n_learners, 1), 256, lds, st>>>(learners, n1, n2, S, D);
+  IL_CHECK_LAUNCH("il_gmmil_reward_population");
+  return IL_OK;
+}
+template <int NKQ, bool LANES>
+static int gmmil_pop_launch_l(const il_gmmil_learner* learners, int n_learners, int n1, int n2, int S, int D, hipStream_t st) {
+  il_batch pol = {}, exp = {};
+  pol.n = n1; exp.n = n2;
+  switch (gmmil_mfma_cols(&pol, &exp, D)) {   // one learner's shape decides, as in il_gmmil_reward: the partial sums (hence the bits) follow the column block
+    case 32: return gmmil_pop_launch_<NKQ, LANES, 32>(learners, n_learners, n1, n2, S, D, st);
+    case 64: return gmmil_pop_launch_<NKQ, LANES, 64>(learners, n_learners, n1, n2, S, D, st);
+    default: return gmmil_pop_launch_<NKQ, LANES, 128>(learners, n_learners, n1, n2, S, D, st);
+  }
+}
+template <int NKQ>
+static int gmmil_pop_launch(const il_gmmil_learner* learners, int n_learners, int n1, int n2, int S, int D, int lanes, hipStream_t st) {
+  return lanes && D >= 4 ? gmmil_pop_launch_l<NKQ, true>(learners, n_learners, n1, n2, S, D, st) : gmmil_pop_launch_l<NKQ, false>(learners, n_learners, n1, n2, S, D, st);
+}
+// population axis: il_gmmil_reward of n_learners learners of one shape in one launch (include/il_hip.h)
+extern "C" int il_gmmil_reward_population(const il_gmmil_learner* learners_dev, int32_t n_learners, int32_t n1, int32_t n2, int32_t S, int32_t A, int32_t state_only,
+                                          int32_t whole_lanes, int64_t workspace_floats, il_stream_t stream_) {
+  IL_CHECK_ARG(learners_dev, "il_gmmil_reward_population: null learner array");
+  IL_CHECK_ARG(n_learners >= 1 && n_learners <= 65535, "il_gmmil_reward_population: n_learners=%d must be in 1..65535", n_learners);
+  IL_CHECK_ARG(n1 >= 1 && n2 >= 1, "il_gmmil_reward_population: batch sizes n1=%d, n2=%d must be >= 1", n1, n2);
+  IL_CHECK_ARG(S >= 1 && (state_only || A >= 0), "il_gmmil_reward_population: bad dims (state=%d, action=%d)", S, A);
+  const int D = S + (state_only ? 0 : A);
+  if (!gmmil_mfma_on(D))
+    return il_set_error(IL_ERR_UNSUPPORTED, "il_gmmil_reward_population: dim=%d: the population launch is the centred-Gram form (dim <= 128, not under IL_GMMIL_MFMA=0); "
+                        "other shapes keep il_gmmil_reward per learner", D);
+  const GmmilWs w = gmmil_ws(n1, n2, D);
+  if (workspace_floats < w.total)
+    return il_set_error(IL_ERR_WORKSPACE, "il_gmmil_reward_population: every learner's workspace too small (%lld < %lld floats)", (long long)workspace_floats, (long long)w.total);
+  hipStream_t st = (hipStream_t)stream_;
+  if (D <= 32) return gmmil_pop_launch<2>(learners_dev, n_learners, n1, n2, S, D, whole_lanes, st);
+  if (D <= 64) return gmmil_pop_launch<4>(learners_dev, n_learners, n1, n2, S, D, whole_lanes, st);
+  return gmmil_pop_launch<8>(learners_dev, n_learners, n1, n2, S, D, whole_lanes, st);
 }
 
 // distance matrix between a and b ([na][nb]). To keep the ABI allocation-free the caller passes the same kind of workspace as for il_gmmil_reward.

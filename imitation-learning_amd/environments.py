@@ -27,6 +27,12 @@ _SPECS = {  # obs dim (without absorbing bit), action dim, can terminate early, 
 }
 
 
+def env_dims(env_name: str, absorbing: bool) -> Tuple[int, int]:
+  """(state_size, action_size) as the training loop sees them - the absorbing indicator bit included - without building the environment."""
+  obs_dim, act_dim = _SPECS[env_name][:2]
+  return obs_dim + (1 if absorbing else 0), act_dim
+
+
 class _Space:
   def __init__(self, dim):
     self.shape = (dim,)

@@ -1480,6 +1480,16 @@ class PopulationPlan:
     self.graph.replay()
 
 
+def gmmil_whole_lanes(batches, state_size: int, action_size: int, state_only) -> int:
+  """The `whole_lanes` promise of il_gmmil_reward_population (include/il_hip.h): 1 when EVERY batch descriptor has whole 16-byte lanes along its rows - il_gmmil_reward's own
+  rule, applied on the host to the descriptors whose copies live on the device. Either answer gives the same rewards; 1 requests the operands a lane at a time."""
+  def ok(b):
+    st = (b.states or 0) % 16 == 0 and b.ld_states % 4 == 0 and state_size % 4 == 0
+    ac = bool(state_only) or ((b.actions or 0) % 16 == 0 and b.ld_actions % 4 == 0 and action_size % 4 == 0)
+    return st and ac
+  return int(all(ok(b) for b in batches))
+
+
 def _device_array(structs, device) -> Tensor:
   """ctypes descriptors -> one device byte tensor (the kernels index it with the learner id)."""
   raw = b''.join(bytes(x) for x in structs)
@@ -1491,8 +1501,11 @@ class BatchedPopulationPlan:
   dimension, so one update of the whole population costs 11 launches instead of 11 N.  This is the route from the latency-bound
   single-learner regime towards the HBM roofline.  Every learner keeps its own replay ring, MT19937 index stream,
   networks, optimiser state, scratch and Philox counter (build the `UpdatePlan`s with distinct `learner_id`s).  SAC, GAIL (`il_gail_step_population`: discriminator step +
-  relabel) and RED (`il_red_reward_population`: every learner's eval-mode reward under its own predictor, target and sigma_1) learners; GAIL's and RED's reward launches run
-  on a second stream beside the reward-independent forward kernels (IL_POP_OVERLAP=0: in stream order)."""
+  relabel), RED (`il_red_reward_population`: every learner's eval-mode reward under its own predictor, target and sigma_1) and GMMIL (`il_gmmil_reward_population`: every
+  learner's kernel-mean-embedding reward on its own batches, under its own frozen bandwidths, with its own workspace) learners; GAIL's, RED's and GMMIL's reward launches run
+  on a second stream beside the reward-independent forward kernels (IL_POP_OVERLAP=0: in stream order).  GMMIL: the FIRST run() is eager - every learner fixes its
+  bandwidths from its first batch on the host (models.py:193-195), one read per learner, once - and cannot be captured; from the second on an update is the same launches
+  as for the others."""
 
   def __init__(self, plans, groups: Optional[int] = None):
     self.plans = list(plans)
@@ -1511,11 +1524,15 @@ class BatchedPopulationPlan:
     for p in self.plans:
       p._set_device_sync(False)   # one stream, one set of launches for all learners: plain stream order
     p0 = self.plans[0]
-    assert all(p.algorithm == p0.algorithm and p.B == p0.B for p in self.plans) and p0.algorithm in ('SAC', 'GAIL', 'RED'), 'the population launches exist for SAC, GAIL and RED learners'
+    assert all(p.algorithm == p0.algorithm and p.B == p0.B for p in self.plans) and p0.algorithm in ('SAC', 'GAIL', 'RED', 'GMMIL'), 'the population launches exist for SAC, GAIL, RED and GMMIL learners of one batch size'
     if p0.algorithm == 'RED':
       shape = lambda r: (r.state_dim, r.action_dim, r.hidden, r.depth, r.activation, r.state_only, r.batch)   # what sizes il_red_reward_population's tile and grid
       assert all(shape(p.red) == shape(p0.red) for p in self.plans), 'BatchedPopulationPlan(RED): the discriminators of one population share dims, hidden, depth, activation, state_only and batch'
       assert not any(p.mix_expert or p.bc_aux for p in self.plans), 'BatchedPopulationPlan(RED): mixed batches / the BC auxiliary step have no population launches'
+    if p0.algorithm == 'GMMIL':
+      shape = lambda d: (d.state_size, d.action_size, bool(d.state_only))   # with B: what sizes il_gmmil_reward_population's grid, column block and workspaces
+      assert all(shape(p.discriminator) == shape(p0.discriminator) for p in self.plans), 'BatchedPopulationPlan(GMMIL): the learners of one population share state_size, action_size and state_only'
+      assert not any(p.mix_expert or p.bc_aux for p in self.plans), 'BatchedPopulationPlan(GMMIL): mixed batches / the BC auxiliary step have no population launches'
     if any(getattr(p, 'general', False) for p in self.plans):
       raise NotImplementedError('BatchedPopulationPlan: actor / critic shapes outside depth 2 / ReLU / hidden <= 256 / action_size <= 8 have no population launches (PopulationPlan runs them as independent graph branches)')
     self.algorithm, self.B, self.L, dev = p0.algorithm, p0.B, len(self.plans), p0.rows.device
@@ -1537,9 +1554,10 @@ class BatchedPopulationPlan:
     if self.algorithm == 'RED':   # every learner's own predictor / target arenas and sigma_1 (set_sigma): read on the device from its descriptor
       self.red_descs = _device_array([p.red for p in self.plans], dev)
       self.reward_ptrs = torch.tensor([p.rewards.data_ptr() for p in self.plans], dtype=torch.int64, device=dev)
+    self.gmmil_learners = None   # GMMIL: the il_gmmil_learner array, built once every learner's bandwidths are frozen (after the first run())
     self.graph = None
     self._prepared = False
-    self.side = torch.cuda.Stream() if self.algorithm in ('GAIL', 'RED') and os.environ.get('IL_POP_OVERLAP', '1') != '0' else None
+    self.side = torch.cuda.Stream() if self.algorithm in ('GAIL', 'RED', 'GMMIL') and os.environ.get('IL_POP_OVERLAP', '1') != '0' else None
 
   def run(self):
     if self.subs is not None:
@@ -1556,7 +1574,19 @@ class BatchedPopulationPlan:
     _lib.check(L.il_replay_sample_population(_lib.ptr(self.sample_args), self.L, self.B, self.max_row, st))
     if self.algorithm == 'RED':
       assert not any(p.discriminator.training for p in self.plans), 'BatchedPopulationPlan(RED): discriminator.eval() first (train.py:147)'
-    if self.algorithm in ('GAIL', 'RED') and self.side is not None:
+    if self.algorithm == 'GMMIL':
+      if any(p.discriminator.gamma_1 is None for p in self.plans):
+        # the first update: each learner's own median heuristic on its first batch (host-side, once), its reward by its own eager call; then the SAC launches in stream order
+        assert not torch.cuda.is_current_stream_capturing(), 'UpdatePlan(GMMIL): run() once before capture() (the first batch fixes the kernel bandwidths)'
+        for p in self.plans: p._enqueue_reward_model(st)
+        _lib.check(L.il_sac_update_population(_lib.ptr(self.sac_descs), _lib.ptr(self.batches), self.L, C.byref(p0.sac), prepared, st))
+        self._prepared = True
+        self._gmmil_freeze()   # here, not in the next run(): that one may be captured, and the array's upload is no graph node
+        return
+      if self.gmmil_learners is None: self._gmmil_freeze()
+      d0 = p0.discriminator
+      gmmil_args = (_lib.ptr(self.gmmil_learners), self.L, self.B, self.B, d0.state_size, d0.action_size, int(d0.state_only), self.gmmil_whole_lanes, self.gmmil_ws_floats)
+    if self.algorithm in ('GAIL', 'RED', 'GMMIL') and self.side is not None:
       # The discriminator kernels (48 small workgroups per learner, latency-bound: ~60 us of a ~450 us replay at 32 learners) run on a second stream beside the
       # reward-independent forward kernels of every learner and join before the critic loss. One fork / join per replay (its ~10 us of queue signalling is paid once
       # for the whole population, unlike in the single-learner update where it is why the branches hand over on the device instead).
@@ -1565,8 +1595,10 @@ class BatchedPopulationPlan:
       with torch.cuda.stream(self.side):
         if self.algorithm == 'GAIL':
           _lib.check(L.il_gail_step_population(_lib.ptr(self.disc_descs), _lib.ptr(self.batches), _lib.ptr(self.expert_batches), _lib.ptr(self.reward_ptrs), self.L, C.byref(p0.disc), _lib.stream_ptr()))
-        else:   # RED: the eval-mode reward of every learner (8 workgroups per learner at batch 256), the same fork and join
+        elif self.algorithm == 'RED':   # the eval-mode reward of every learner (8 workgroups per learner at batch 256), the same fork and join
           _lib.check(L.il_red_reward_population(_lib.ptr(self.red_descs), _lib.ptr(self.batches), _lib.ptr(self.reward_ptrs), self.L, C.byref(p0.red), _lib.stream_ptr()))
+        else:   # GMMIL: every learner's reward (16 workgroups per learner at batch 128), the same fork and join
+          _lib.check(L.il_gmmil_reward_population(*gmmil_args, _lib.stream_ptr()))
       _lib.check(L.il_sac_update_population(_lib.ptr(self.sac_descs), _lib.ptr(self.batches), self.L, C.byref(p0.sac), prepared | _lib.IL_FLAG_SAC_FORWARD_ONLY, st))
       main.wait_stream(self.side)
       _lib.check(L.il_sac_update_population(_lib.ptr(self.sac_descs), _lib.ptr(self.batches), self.L, C.byref(p0.sac), _lib.IL_FLAG_SAC_SKIP_FORWARD, st))
@@ -1575,12 +1607,31 @@ class BatchedPopulationPlan:
         _lib.check(L.il_gail_step_population(_lib.ptr(self.disc_descs), _lib.ptr(self.batches), _lib.ptr(self.expert_batches), _lib.ptr(self.reward_ptrs), self.L, C.byref(p0.disc), st))
       if self.algorithm == 'RED':
         _lib.check(L.il_red_reward_population(_lib.ptr(self.red_descs), _lib.ptr(self.batches), _lib.ptr(self.reward_ptrs), self.L, C.byref(p0.red), st))
+      if self.algorithm == 'GMMIL':
+        _lib.check(L.il_gmmil_reward_population(*gmmil_args, st))
       _lib.check(L.il_sac_update_population(_lib.ptr(self.sac_descs), _lib.ptr(self.batches), self.L, C.byref(p0.sac), prepared, st))
     self._prepared = True
+
+  def _gmmil_freeze(self):
+    """GMMIL, once, after the first update froze every learner's bandwidths: the device array il_gmmil_reward_population indexes with the learner id - each learner's two
+    batch descriptors, gamma_1 and gamma_2, its reward buffer, and its own zero-filled workspace (own partial sums and arrival counters), kept by this plan."""
+    p0, dev = self.plans[0], self.plans[0].rows.device
+    d0 = p0.discriminator
+    D = d0.state_size + (0 if d0.state_only else d0.action_size)
+    self.gmmil_ws_floats = int(_lib.lib().il_gmmil_workspace_floats(self.B, self.B, D))
+    stride = (self.gmmil_ws_floats + 63) // 64 * 64   # every learner's workspace starts on a 256-byte boundary (the partial sums leave as 8-byte exchanges)
+    self.gmmil_ws = torch.zeros((self.L, stride), dtype=torch.float32, device=dev)
+    self.gmmil_whole_lanes = gmmil_whole_lanes([b for p in self.plans for b in (p.pb, p.eb)], d0.state_size, d0.action_size, d0.state_only)
+    self.gmmil_learners = _device_array([_lib.GmmilLearner(p.pb, p.eb, float(p.discriminator.gamma_1), float(p.discriminator.gamma_2), self.gmmil_ws[l].data_ptr(), p.rewards.data_ptr())
+                                         for l, p in enumerate(self.plans)], dev)
 
   def capture(self, warmup: int = 0):
     for _ in range(warmup):
       self.run()
+    if self.algorithm == 'GMMIL':   # asked in front of the capture: an exception inside one would leave the stream capturing
+      assert not any(p.discriminator.gamma_1 is None for p in self.plans), 'UpdatePlan(GMMIL): run() once before capture() (the first batch fixes the kernel bandwidths)'
+      for pop in (self.subs or [self]):
+        if pop.gmmil_learners is None: pop._gmmil_freeze()   # (learners whose bandwidths were fixed before this plan was built)
     torch.cuda.synchronize()
     self.graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(self.graph):

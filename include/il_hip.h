@@ -593,6 +593,27 @@ int64_t il_gmmil_workspace_floats(int32_t n_policy, int32_t n_expert, int32_t di
 int il_gmmil_reward(const il_batch* policy, const il_batch* expert, int32_t state_dim, int32_t action_dim, int32_t state_only,
                     float gamma_1, float gamma_2, float* out_rewards, float* out_similarity, float* out_self_similarity,
                     float* workspace, int64_t workspace_floats, il_stream_t stream);
+/* Population axis (seed sweeps): il_gmmil_reward of n_learners learners of ONE shape in one launch. learners_dev is a DEVICE array indexed by the learner id; what a learner
+ * owns is read from its entry: both batches, its frozen bandwidths, its workspace and its output. */
+typedef struct il_gmmil_learner {
+  il_batch policy, expert;      /* the rows il_replay_sample_population wrote: read WITHOUT `gather`; `n` is ignored (n_policy / n_expert below hold for all learners) */
+  float gamma_1, gamma_2;
+  float* workspace;             /* this learner's own: >= il_gmmil_workspace_floats(n_policy, n_expert, dim) floats, zero-filled once (see above) */
+  float* out_rewards;           /* [n_policy] */
+} il_gmmil_learner;
+/* Every out_rewards[i] of learner l is BIT-IDENTICAL to il_gmmil_reward(&policy_l, &expert_l, ..., gamma_1_l, gamma_2_l, ...): the same kernel body, the same column block
+ * (chosen from one learner's shape, never from the population's size), the same block-ordered sums.
+ * - Workspaces: one per learner, never shared between learners or shapes. Each holds that learner's partial sums and self-resetting arrival counters; a learner's last
+ *   arriving workgroup sees that learner's tickets only. workspace_floats is the size of EACH.
+ * - whole_lanes: the caller's promise that for EVERY learner both batches have whole 16-byte lanes along their rows (states / actions pointers 16-byte aligned, ld_states /
+ *   ld_actions and state_dim / action_dim multiples of 4; actions exempt when state_only) - the library cannot inspect pointers that live on the device. Pass 0 when in doubt:
+ *   it changes how operands are requested, never a value.
+ * - One launch, nothing allocated. Workgroup -> (learner, block): learner on the grid's second axis, the learner's blocks in il_gmmil_reward's order.
+ * IL_ERR_ARG: null array, n_learners outside 1..65535, n_policy < 1 or n_expert < 1, a grid above 2^31 - 1 workgroups. IL_ERR_UNSUPPORTED: dim > 128, or IL_GMMIL_MFMA=0
+ * (those shapes keep il_gmmil_reward's direct forms per learner: the population has no launch for them). IL_ERR_WORKSPACE: workspace_floats below
+ * il_gmmil_workspace_floats(n_policy, n_expert, dim). Nothing is launched on any refusal. */
+int il_gmmil_reward_population(const il_gmmil_learner* learners_dev, int32_t n_learners, int32_t n_policy, int32_t n_expert, int32_t state_dim, int32_t action_dim,
+                               int32_t state_only, int32_t whole_lanes, int64_t workspace_floats, il_stream_t stream);
 /* models.py:25-28 _squared_distance matrix [na, nb] (used once for the median heuristic, models.py:193-195). */
 int il_gmmil_sqdist(const il_batch* a, const il_batch* b, int32_t state_dim, int32_t action_dim, int32_t state_only, float* out,
                     float* workspace, int64_t workspace_floats, il_stream_t stream);
@@ -830,7 +851,7 @@ int il_red_epoch_steps(const il_red* d, const il_batch* ring, const float* mask_
                        uint32_t flags, const il_epoch* epoch, int32_t steps, il_stream_t stream);
 
 /* sizeof() of the descriptor structs in this build (0 il_batch, 1 il_adam, 2 il_sac, 3 il_disc, 4 il_pwil, 5 il_sample_args, 6 il_red,
- * 7 il_dril, 8 il_disc_shaped, 9 il_disc_deep, 10 il_peer_bucket, 11 il_disc_shaped_deep, 12 il_epoch, 13 il_act_learner; -1 otherwise): lets a binding verify its own struct definitions. */
+ * 7 il_dril, 8 il_disc_shaped, 9 il_disc_deep, 10 il_peer_bucket, 11 il_disc_shaped_deep, 12 il_epoch, 13 il_act_learner, 14 il_gmmil_learner; -1 otherwise): lets a binding verify its own struct definitions. */
 int32_t il_struct_size(int32_t which);
 
 #ifdef __cplusplus

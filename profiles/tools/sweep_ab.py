@@ -7,7 +7,8 @@
             expert data and networks: plan set-up, the loop, every launch drained before the clock stops; evaluation is off under check_time_usage)
 (c) counts as faster than (b) only if its median beats (b)'s by more than (b)'s spread (max - min) of this job; the default of +sweep.schedule follows from that at both L.
   python profiles/tools/sweep_ab.py [--steps 4000] [--repeats 5] [--learners 4 16] [--algorithms GAIL SAC] [--out profiles/sweep_ab.txt]
-(--algorithms RED: the same three forms with the predictor's pretraining cut to 100 iterations per learner)"""
+(--algorithms RED: the same three forms with the predictor's pretraining cut to 100 iterations per learner; --algorithms GMMIL: at batch 128, the batch of every shipped GMMIL
+configuration, where one reward launch is 16 workgroups)"""
 import argparse
 import os
 import sys
@@ -37,7 +38,8 @@ def say(text):
 
 def overrides(algorithm, steps, start):
   extra = ['imitation.pretraining.iterations=100'] if algorithm == 'RED' else []   # (the predictor's pretraining sits in front of the clock: kept short, the job measures the loop)
-  return [f'algorithm={algorithm}', 'env=halfcheetah', f'steps={steps}', f'training.start={start}', 'training.batch_size=256', 'check_time_usage=true', 'logging.interval=1000',
+  batch = 128 if algorithm == 'GMMIL' else 256
+  return [f'algorithm={algorithm}', 'env=halfcheetah', f'steps={steps}', f'training.start={start}', f'training.batch_size={batch}', 'check_time_usage=true', 'logging.interval=1000',
           '+synthetic_env.dataset_trajectories=6'] + extra
 
 
@@ -86,7 +88,7 @@ def main(argv=None):
   if args.out:
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     out_path = os.path.abspath(args.out)
-  say(f'device {torch.cuda.get_device_name(0)}; halfcheetah (synthetic stand-in), batch 256, {args.steps} env steps per learner, one update per step from step {args.start}; '
+  say(f'device {torch.cuda.get_device_name(0)}; halfcheetah (synthetic stand-in), batch 256 (GMMIL: 128), {args.steps} env steps per learner, one update per step from step {args.start}; '
       f'{args.repeats} interleaved repeats; train.SWEEP_DEFAULT_SCHEDULE = {train.SWEEP_DEFAULT_SCHEDULE}')
   verdicts = []
   with tempfile.TemporaryDirectory() as tmp:

@@ -11,7 +11,7 @@ the row-by-row loop.
 
 Sweeps:  python train.py -m seed=1,2,3 algorithm=GAIL env=halfcheetah  (Hydra's multirun: comma lists, Cartesian product, outputs/<algorithm>_<env>_sweeper/<time>/<job>/).
 Jobs that differ only in their seed train as ONE population in lockstep (`train_sweep`: `il.BatchedPopulationPlan` for the update, `il.PopulationActingWorker` or one
-`il.ActingWorker` per learner for acting: `+sweep.schedule=population|per_learner`, the same bits either way); every other sweep runs its jobs one after another, and says so.
+`il.ActingWorker` per learner for acting: `+sweep.schedule=population|per_learner`, the same bits either way; GMMIL sweeps only when that key is given); every other sweep runs its jobs one after another, and says so.
 """
 import os
 import sys
@@ -24,7 +24,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import imitation_learning_amd as il  # noqa: E402
 from imitation_learning_amd import _lib  # noqa: E402
 from imitation_learning_amd import config as il_config  # noqa: E402
-from imitation_learning_amd.environments import make_env  # noqa: E402
+from imitation_learning_amd.environments import env_dims, make_env  # noqa: E402
 from imitation_learning_amd.evaluation import evaluate_agent, evaluate_population  # noqa: E402
 from imitation_learning_amd.models import default_device  # noqa: E402
 from imitation_learning_amd.utils import cycle, lineplot  # noqa: E402
@@ -412,16 +412,19 @@ def _fused_shape(model_cfg) -> bool:
 def sweep_fallback_reason(cfg):
   """None when a seed sweep of this configuration can train as one population (what il.BatchedPopulationPlan and il.PopulationActingWorker take); otherwise the reason
   its jobs run one after another through train()."""
-  if cfg.algorithm not in ('SAC', 'GAIL', 'RED'):
-    return f'algorithm={cfg.algorithm} has no population launches (SAC, GAIL and RED have)'
+  if cfg.algorithm not in ('SAC', 'GAIL', 'RED', 'GMMIL'):
+    return f'algorithm={cfg.algorithm} has no population launches (SAC, GAIL and RED have), and GMMIL under an explicit +sweep.schedule'
+  if cfg.algorithm == 'GMMIL' and (cfg.get('sweep', {}) or {}).get('schedule') is None:
+    # opt-in: a GMMIL sweep without the key runs as it always has; with it, its first update is eager (every learner's bandwidths) and the rest are population launches
+    return f'algorithm=GMMIL trains as one population (il_gmmil_reward_population) only when +sweep.schedule={"|".join(SWEEP_SCHEDULES)} is given'
   if not (_fused_shape(cfg.reinforcement.actor) and _fused_shape(cfg.reinforcement.critic)):
     return 'an actor / critic shape outside depth 2, ReLU, hidden 64..256 in multiples of 64 has no population launches'
   if int(cfg.reinforcement.actor.hidden_size) != int(cfg.reinforcement.critic.hidden_size):
     return 'actor and critic of different hidden sizes have no population launches'
   if cfg.training.batch_size % 16 != 0:
     return f'training.batch_size={cfg.training.batch_size} is not a multiple of 16'
-  # RED with prefill_memory: the expert rows are moved into the agent ring once, in front of the loop (train.py:134); nothing is edited between the launches
-  if cfg.imitation.mix_expert_data != 'none' and not (cfg.algorithm == 'RED' and cfg.imitation.mix_expert_data == 'prefill_memory'):
+  # RED and GMMIL with prefill_memory: the expert rows are moved into the agent ring once, in front of the loop (train.py:134, 192); nothing is edited between the launches
+  if cfg.imitation.mix_expert_data != 'none' and not (cfg.algorithm in ('RED', 'GMMIL') and cfg.imitation.mix_expert_data == 'prefill_memory'):
     return f'imitation.mix_expert_data={cfg.imitation.mix_expert_data} edits the batches between the launches'
   if cfg.imitation.bc_aux_loss:
     return 'imitation.bc_aux_loss adds an actor step per update that the population launches do not have'
@@ -430,6 +433,11 @@ def sweep_fallback_reason(cfg):
   acting = (cfg.get('acting', {}) or {}).get('schedule', 'exact')
   if acting not in ('exact', 'fused'):
     return f'+acting.schedule={acting}: the population acting launch has the exact and the fused schedule'
+  if cfg.algorithm == 'GMMIL':
+    S, A = env_dims(cfg.env, cfg.imitation.absorbing)
+    D = S + (0 if cfg.imitation.state_only else A)
+    if D > 128:
+      return f'GMMIL on {D} state + action dims: above 128 the reward runs its direct-difference launches per learner (il_gmmil_reward_population covers dims <= 128)'
   if cfg.algorithm == 'GAIL':
     d = cfg.imitation.discriminator
     if (int(d.depth), str(d.activation)) != (1, 'relu'):
@@ -485,7 +493,8 @@ def train_sweep(cfgs, prefixes):
   """The loop of train() in lockstep over L learners that differ only in their seed: per lockstep step ONE population act launch, L host environment steps and ONE
   append launch (`+acting.schedule=fused`: one launch for both); on update steps ONE population update (il.BatchedPopulationPlan); on evaluation steps
   evaluate_population. Every learner has its own seeds, index stream, environments, rings, networks, optimisers and `learner_id`; job l writes what a single run writes
-  under prefixes[l]. Returns the mean normalised score per job."""
+  under prefixes[l] (GAIL and RED: with a discriminator.pth; GMMIL, as in train(): without one - its bandwidths are fixed by each learner's first batch, in the first, eager,
+  update, and live in no file). Returns the mean normalised score per job."""
   L = len(cfgs)
   assert L >= 1 and len(prefixes) == L
   for cfg in cfgs: il_config.validate(cfg)
@@ -525,6 +534,8 @@ def train_sweep(cfgs, prefixes):
     elif cfg.algorithm == 'RED':
       ln.discriminator = il.REDDiscriminator(S, A, cfg.imitation)
       ln.discriminator_optimiser = il.AdamW(ln.discriminator, lr=cfg.imitation.learning_rate, weight_decay=cfg.imitation.weight_decay)
+    elif cfg.algorithm == 'GMMIL':   # no parameters and no optimiser: its state is the two bandwidths the learner's first batch fixes
+      ln.discriminator = il.GMMILDiscriminator(S, A, cfg.imitation)
     ln.metrics = dict(train_steps=[], train_returns=[], test_steps=[], test_returns=[], test_returns_normalized=[], update_steps=[], predicted_rewards=[], alphas=[], entropies=[], Q_values=[])
     ln.score = []
     start_time += time.time() - built
@@ -543,6 +554,7 @@ def train_sweep(cfgs, prefixes):
         start_time += ln.metrics['pre_training_time']
       if cfg.imitation.mix_expert_data == 'prefill_memory': ln.memory.transfer_transitions(ln.expert_memory)
       ln.discriminator.eval()   # train.py:147, in front of the plan: from here on the predictor's dropout is off
+    if cfg.algorithm == 'GMMIL' and cfg.imitation.mix_expert_data == 'prefill_memory': ln.memory.transfer_transitions(ln.expert_memory)   # train.py:192, once, in front of the loop
     ln.plan = il.UpdatePlan(cfg.algorithm, ln.actor, ln.critic, ln.log_alpha, ln.target_critic, ln.memory, ln.actor_optimiser, ln.critic_optimiser, ln.temperature_optimiser, B,
                             cfg.reinforcement.discount, entropy_target, cfg.reinforcement.polyak_factor, expert_memory=ln.expert_memory, discriminator=ln.discriminator,
                             discriminator_optimiser=ln.discriminator_optimiser, imitation_cfg=cfg.imitation if cfg.algorithm == 'GAIL' else None, overlap=False, learner_id=i)
