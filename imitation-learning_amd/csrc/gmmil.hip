@@ -667,12 +667,38 @@ __device__ __forceinline__ void gmmil_mfma_body(il_batch& pol, il_batch& exp, in
       for (int e = 0; e < 4; ++e) { acc0 = mfma16(xq[q][e], b0[e], acc0); acc1 = mfma16(xq[q][e], b1[e], acc1); }
     }
   };
+  // The Gram form's ssq carries an absolute error of the size of the centred NORMS' roundings, <= 2^-18 (|x - c|^2 + |y - c|^2) =: e with room to spare (D <= 128 terms
+  // each), where the direct difference form's error is relative to ssq itself. At gamma ~ 1 / median that is ~1e-6 in the exponent (the kernel's premise, above). A
+  // bandwidth far beyond it - gamma_2 = 1 / (0 + 1e-8) when more than half of the expert rows are equal, or one set from outside - multiplies it: at 1e4 / median the
+  // terms of DUPLICATE rows (ssq = +-tiny instead of 0) were off by 5e-3, the similarities by 5 x the 1e-5 bound (tests/test_value_edges_gpu.py). So a pair whose term
+  // could be off by more than 2^-12 under that bound, gamma e 2^(-gamma ssq) > 2^-12, takes its ssq from the operands in memory, as models.py:25-28 writes it. With
+  // gamma <= 45 / median no pair does, and all a tile pays is the wave-uniform test in front (a pair's e against nn_cold, from the larger bandwidth alone).
+  const float ga1 = -gex.c1, ga2 = -gex.c2, nn_cold = 0x1p+6f / fmaxf(fmaxf(ga1, ga2), 1e-30f);   // e * max(a1, a2) > 2^-12  <=>  nx + ny > 2^6 / max(ga1, ga2)
+  const float nx_max = fmaxf(fmaxf(nx4[0], nx4[1]), fmaxf(nx4[2], nx4[3]));
   auto finish = [&](int ct, const f32x4& acc) {   // lane: rows 4 g + r of the wave's 16, column 16 ct + l16 of the workgroup's 128
     const int c = ct * 16 + l16;
     float nyv = nyh[c];
 #pragma unroll
     for (int q = 1; q < YP; ++q) nyv += nyh[q * COLS + c];
     const float wyv = wys[c];
+    if (__builtin_expect(nx_max + nyv > nn_cold, 0)) {
+      const int col = min(jb * COLS + c, ny - 1);
+      for (int r = 0; r < 4; ++r) {
+        const float nn = nx4[r] + nyv, e = nn * 0x1p-18f;
+        float ssq = fmaxf(__builtin_fmaf(-2.f, acc[r], nn), 0.f);
+        if (wyv != 0.f && e * fmaxf(ga1 * __builtin_amdgcn_exp2f(ssq * gex.c1), ga2 * __builtin_amdgcn_exp2f(ssq * gex.c2)) > 0x1p-12f) {
+          const int row = min(it * GMF_ROWS + wave * 16 + 4 * g + r, n1 - 1);
+          ssq = 0.f;
+          for (int k = 0; k < D; ++k) {
+            const float xv = gload(k < S ? pol.states + ((size_t)row * pol.ld_states + k) : pol.actions + ((size_t)row * pol.ld_actions + (k - S)));
+            const float yv = gload(k < S ? yb.states + ((size_t)col * yb.ld_states + k) : yb.actions + ((size_t)col * yb.ld_actions + (k - S)));
+            ssq = __builtin_fmaf(xv - yv, xv - yv, ssq);
+          }
+        }
+        rs[r] = __builtin_fmaf(wyv, gmmil_pair_kernel(ssq, gex), rs[r]);
+      }
+      return;
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float ssq = fmaxf(__builtin_fmaf(-2.f, acc[r], nx4[r] + nyv), 0.f);

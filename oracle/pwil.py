@@ -2,6 +2,8 @@
 
 Literal restatement incl. row deletion (so "first index on ties" and the shrinking
 index space behave as in the reference); `reset()` restores atoms and weights.
+`alive` carries the ORIGINAL row index of every atom still present through the deletions
+(tests only: which atoms survive a tie, not just how many; no result depends on it).
 """
 from __future__ import annotations
 
@@ -29,6 +31,7 @@ class PwilOracle:
     self.atoms = (self.scale * (self.raw + self.offset)).astype(f32)
     n = self.raw.shape[0]
     self.weights = np.full(n, f32(1 / n), f32)
+    self.alive = np.arange(n)
 
   def compute_reward(self, atom_raw):
     atom = (self.scale * (np.asarray(atom_raw, f32).reshape(1, -1) + self.offset)).astype(f32)
@@ -42,6 +45,7 @@ class PwilOracle:
         cost += ew * float(dists[i])
         weight -= ew
         self.atoms, self.weights, dists = np.delete(self.atoms, i, 0), np.delete(self.weights, i, 0), np.delete(dists, i, 0)
+        self.alive = np.delete(self.alive, i)
       else:
         cost += weight * float(dists[i])
         self.weights[i] -= f32(weight)

@@ -218,10 +218,14 @@ GMMIL_DIRECT_SHAPES = ((130, 257, 132, 124), (40, 700, 152, 144), (70, 33, 3, 2)
 def gmmil_float64_case(n1, n2, D, S):
   """One of GMMIL_DIRECT_SHAPES with its float64 results, computed once per process and read-only: the inputs, the median bandwidths rounded to float32 (what the kernels
   are given), the distance matrix, both similarities."""
-  X, E, w, we = gmmil_case(41, n1, n2, D, weighted=True)
+  return gmmil_float64_results(*gmmil_case(41, n1, n2, D, weighted=True))
+
+
+def gmmil_float64_results(X, E, w, we, gamma_scales=(1.0, 1.0)):
+  """The float64 results of one GMMIL call on the float32 inputs given; gamma_scales multiply the two median bandwidths."""
   d64 = lambda a, b: ((a.astype(np.float64)[:, None, :] - b.astype(np.float64)[None, :, :]) ** 2).mean(2)
   dxe, dxx, dee = d64(X, E), d64(X, X), d64(E, E)
-  g1, g2 = float(f32(1.0 / (np.median(dxe) + 1e-8))), float(f32(1.0 / (np.median(dee) + 1e-8)))
+  g1, g2 = float(f32(gamma_scales[0] / (np.median(dxe) + 1e-8))), float(f32(gamma_scales[1] / (np.median(dee) + 1e-8)))
   wn, wen = w.astype(np.float64) / w.astype(np.float64).sum(), we.astype(np.float64) / we.astype(np.float64).sum()
   sim64 = sum(wn * (np.exp(-gm * dxe) @ wen) for gm in (g1, g2)); self64 = sum(wn * (np.exp(-gm * dxx) @ wn) for gm in (g1, g2))
   out = dict(X=X, E=E, w=w, we=we, g1=g1, g2=g2, dxe=dxe, dxx=dxx, sim64=sim64, self64=self64)
@@ -352,3 +356,91 @@ def gail_shaped_case(seed, env, hidden, batch, steps, spectral_norm):
   c['expert'] = [transitions(rs, batch, S, A, state_shift=0.5, weighted=True, terminal_frac=0.3) for _ in range(steps)]
   c['eps'] = [rs.uniform(size=batch).astype(f32) for _ in range(steps)]
   return c
+
+
+# ------------------------------------------------------------------------------------------------ value edges (tests/test_value_edges_gpu.py)
+# Everything above draws standard-normal data, fan-in scaled weights and small biases: a raw log-std stays in (-1, 1), a discriminator logit in (-3, 3), no two distances
+# are equal and no weight is 0. The helpers below edit a finished case (nothing is drawn again, so every existing case keeps its bits) to put VALUES where the kernels
+# branch on them.
+VALUE_EDGE_LOG_STD = (3.0, -25.0, 2.0, -20.0, 0.0, 1.9)   # above the clamp, below it, exactly on each (inclusive) bound, inside, and within the weights' spread of the upper bound
+VALUE_EDGE_LOG_STD_UPPER = (3.0, 2.0, 0.0, 1.9)           # `upper_only`: without the units whose sd is e^-20 (log pi of GIVEN actions then reaches 1e17 and hides every other term)
+VALUE_EDGE_MEAN = 12.0                                     # tanhf(x) == +-1 in float32 for |x| > 9.01
+VALUE_EDGE_MEAN_FAR = -50.0                                # softplus(-2 x) at 100: expf overflows from 88.7, so only the z > 20 branch of the kernels' softplus_f is finite there
+LOGIT_EDGE_SCALES = (1, 1, 30, 30, 100, 100, 300, 300, 1000, 1000, 3000)
+
+
+def actor_head_edges(c, upper_only=False, shift=0, key='actor'):
+  """Edits the tanh-Gaussian head of a `sac_case` / `dril_case` (c[key]: flat parameters whose last layer is Linear(H, 2A)) in place: the log-std bias of component i
+  becomes VALUE_EDGE_LOG_STD[(i + shift) % 6] (`upper_only`: VALUE_EDGE_LOG_STD_UPPER), the last-layer weight rows of the units at exactly 2.0 and -20.0 are zeroed (the
+  output then IS the bias, on the bound to the bit), the mean bias of component 0 is +12, of component 1 (A > 1) -12 and of component 2 (A > 2) -50. Returns the log-std
+  bias of every component."""
+  A, H = c['A'], c['H']
+  flat = c[key]
+  oW = flat.size - (2 * A * H + 2 * A)
+  W, b = flat[oW:oW + 2 * A * H].reshape(2 * A, H), flat[oW + 2 * A * H:]
+  cycle = VALUE_EDGE_LOG_STD_UPPER if upper_only else VALUE_EDGE_LOG_STD
+  values = tuple(cycle[(i + shift) % len(cycle)] for i in range(A))
+  for i, v in enumerate(values):
+    b[A + i] = v
+    if v in (2.0, -20.0): W[A + i] = 0
+  b[0] = VALUE_EDGE_MEAN
+  if A > 1: b[1] = -VALUE_EDGE_MEAN
+  if A > 2: b[2] = VALUE_EDGE_MEAN_FAR
+  return values
+
+
+def logit_edge_rows(batch, zero_weights=(12, 13)):
+  """Multiplies the state rows 0 .. 10 of a transition batch by LOGIT_EDGE_SCALES with alternating sign (the action rows by the sign alone: actions stay in [-1, 1]), so
+  that a discriminator's logits run from O(1) past +-100, and sets two weights to exactly 0. In place."""
+  n = batch['states'].shape[0]
+  for r, s in enumerate(LOGIT_EDGE_SCALES[:n]):
+    sign = f32(1 if r % 2 else -1)
+    batch['states'][r] *= f32(s) * sign; batch['actions'][r] *= sign
+    if 'next_states' in batch: batch['next_states'][r] *= f32(s) * sign
+  for r in zero_weights:
+    if r < n: batch['weights'][r] = 0
+  return batch
+
+
+def zero_weight_rows(batch):
+  """Weight 0 at the first row, at the last row and, when B >= 48, over the whole second 16-row tile. In place."""
+  n = batch['weights'].shape[0]
+  batch['weights'][0] = 0; batch['weights'][n - 1] = 0
+  if n >= 48: batch['weights'][16:32] = 0
+  return batch
+
+
+def pwil_tied_case(seed, N, D, steps):
+  """`pwil_case(seed, N // 3, D, steps)` with every atom three times, the rows permuted (the copies of one atom land in different 256-atom chunks and on different owner
+  threads); agent[1] IS an atom (distance 0, three times), agent[2] the midpoint of two atoms (a near tie: not an exact one after standardisation)."""
+  assert N % 3 == 0 and steps >= 3
+  base, agent = pwil_case(seed, N // 3, D, steps)
+  rs = np.random.RandomState(seed + 5000)
+  atoms = np.concatenate([base, base, base])[rs.permutation(N)]
+  agent[1] = atoms[7]
+  agent[2] = (f32(0.5) * (atoms[11] + atoms[N // 2])).astype(f32)
+  return atoms, agent
+
+
+def _adam_edge_grads(n=1027):
+  """Exact zeros, gradients whose square is a float32 denormal (1e-20 -> 1e-40) or underflows (1e-30 -> 1e-60), ordinary ones, and gradients whose square is near the
+  top of the range (1e15 -> 1e30) or overflows (3e19 -> inf), in both signs; 1027 elements: a vector body and a scalar tail of 3."""
+  values = np.array([0.0, 1e-30, -1e-30, 1e-20, -1e-20, 1e-3, -1e-3, 1.0, -1.0, 1e15, -1e15, 3e19, -3e19], f32)
+  return values[np.arange(n) % values.size].copy()
+
+
+ADAM_EDGE_GRADS = _adam_edge_grads()
+ADAM_EDGE_GRADS.setflags(write=False)
+
+
+@functools.lru_cache(maxsize=None)
+def gmmil_value_edge_case(n1, n2, D, S, gamma_scales=(1.0, 1.0)):
+  """`gmmil_case(41, ...)` with the second third of the policy rows a copy of the first (squared distance exactly 0 off the diagonal), the first third of the expert rows
+  equal to policy rows, and weights of exactly 0 on both sides (one of them on a duplicated row); float64 results as in gmmil_float64_case. gamma_scales = (1e4, 1e-4):
+  a first bandwidth at which every term between different rows underflows and a second at which every term is about 1."""
+  X, E, w, we = gmmil_case(41, n1, n2, D, weighted=True)
+  t1, t2 = n1 // 3, min(n2 // 3, n1)
+  X[t1:2 * t1] = X[:t1]
+  E[:t2] = X[:t2]
+  w[[0, t1, n1 - 1]] = 0; we[[1, n2 - 1]] = 0
+  return gmmil_float64_results(X, E, w, we, gamma_scales)

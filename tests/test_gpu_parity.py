@@ -456,8 +456,13 @@ def test_gmmil_direct_form_matches_float64_outside_the_mfma_range(dims):
   bandwidth medians at every shape, D = 3 and D = 1 (state only) among them: k_gmmil_direct's element-wise operand loads with fewer features than one 16-byte lane (their
   rewards are k_gmmil_mfma's unless IL_GMMIL_MFMA=0). Three calls each (self-resetting arrival counters). The numpy float32 direct evaluation is inside the same bounds
   (tests/test_gmmil_centred_form.py), so the bound is the format's, not these kernels'."""
+  gmmil_against_float64(dims, gi.gmmil_float64_case(*dims))
+
+
+def gmmil_against_float64(dims, c):
+  """The body of test_gmmil_direct_form_matches_float64_outside_the_mfma_range on a prepared case (tests/golden/inputs.py gmmil_float64_results). Returns the three errors
+  over the bound."""
   n1, n2, D, S = dims
-  c = gi.gmmil_float64_case(*dims)
   X, E, sim64, self64 = c['X'], c['E'], c['sim64'], c['self64']
   disc = il.GMMILDiscriminator(S, max(D - S, 1), Cfg(state_only=D == S))
   disc.gamma_1, disc.gamma_2 = c['g1'], c['g2']
@@ -471,6 +476,7 @@ def test_gmmil_direct_form_matches_float64_outside_the_mfma_range(dims):
   assert max(errs) <= 1, errs
   close(N(il_training.gmmil_sqdist(disc, *args)), c['dxe'], 'sqdist')
   close(N(il_training.gmmil_sqdist(disc, args[0], args[1], args[0], args[1])), c['dxx'], 'self sqdist')
+  return errs
 
 
 GMMIL_FORMS_WORKER = r'''
@@ -562,7 +568,7 @@ def test_pwil_every_launch_path_matches_oracle(name, Nn, Th):
   assert int((d.expert_weights >= 0).sum()) == len(o.weights)
 
 
-def _make_plan(algorithm, seed, device_draw=True, loss='BCE', entropy_bonus=0.0, B=256, margin=float('inf'), reward_function='AIRL', mixup_alpha=1, dims=None):
+def _make_plan(algorithm, seed, device_draw=True, loss='BCE', entropy_bonus=0.0, B=256, margin=float('inf'), reward_function='AIRL', mixup_alpha=1, dims=None, edit=None):
   S, A = dims or gi.DIMS['halfcheetah']
   torch.manual_seed(seed)
   cfg = Cfg(hidden_size=256, depth=2, activation='relu')
@@ -570,8 +576,10 @@ def _make_plan(algorithm, seed, device_draw=True, loss='BCE', entropy_bonus=0.0,
   target, log_alpha = il.create_target_network(critic), torch.zeros(1, device=DEV)
   ao, co, to = il.AdamW(actor, lr=3e-4, weight_decay=0), il.AdamW(critic, lr=3e-4, weight_decay=0), il.Adam(log_alpha, lr=3e-4)
   rs = np.random.RandomState(seed)
-  mem = il.ReplayMemory(20000, S, A, True, device=DEV); fill_memory(mem, gi.transitions(rs, 5000, S, A), 5000)
-  emem = il.ReplayMemory(2000, S, A, True, device=DEV); fill_memory(emem, gi.transitions(rs, 2000, S, A, state_shift=0.5), 2000)
+  tr, etr = gi.transitions(rs, 5000, S, A), gi.transitions(rs, 2000, S, A, state_shift=0.5)
+  if edit is not None: edit(tr, etr)   # (tests/test_value_edges_gpu.py: changes the finished rows in place before they enter the rings)
+  mem = il.ReplayMemory(20000, S, A, True, device=DEV); fill_memory(mem, tr, 5000)
+  emem = il.ReplayMemory(2000, S, A, True, device=DEV); fill_memory(emem, etr, 2000)
   icfg = Cfg(state_only=False, spectral_norm=True, loss_function=loss, grad_penalty=1.0, entropy_bonus=entropy_bonus, mixup_alpha=mixup_alpha, pos_class_prior=0.7, nonnegative_margin=margin,
              discriminator=Cfg(hidden_size=64, depth=1, activation='relu', reward_shaping=False, subtract_log_policy=False, reward_function=reward_function))
   disc = il.GAILDiscriminator(S, A, icfg, 0.97, device=DEV)
@@ -582,11 +590,11 @@ def _make_plan(algorithm, seed, device_draw=True, loss='BCE', entropy_bonus=0.0,
 
 
 @pytest.mark.parametrize('reward_function', ['AIRL', 'GAIL', 'FAIRL'])
-def test_inline_relabel_heads_equal_the_reward_kernel(reward_function, dims=None):
+def test_inline_relabel_heads_equal_the_reward_kernel(reward_function, dims=None, edit=None):
   """models.py:177-180 inside the chained SAC launch (disc_reward.hpp: the rows a critic tile already holds are relabelled by the discriminator the other branch has just
   stepped) against `predict_reward` (k_gail_reward) on the same rows and the same, updated discriminator: the three reward heads, bit for bit."""
   il.seed(37); il_training._NOISE.clear()
-  plan, nets = _make_plan('GAIL', 19, reward_function=reward_function, B=64, dims=dims)   # dims: tests/test_dim_edges_gpu.py runs this body at other (state, action) widths
+  plan, nets = _make_plan('GAIL', 19, reward_function=reward_function, B=64, dims=dims, edit=edit)   # dims: tests/test_dim_edges_gpu.py runs this body at other (state, action) widths
   for _ in range(2):
     plan.run()
   torch.cuda.synchronize()
@@ -596,6 +604,7 @@ def test_inline_relabel_heads_equal_the_reward_kernel(reward_function, dims=None
   torch.cuda.synchronize()
   assert np.isfinite(N(plan.rewards)).all() and (N(plan.rewards) > 0).any() == (reward_function != 'FAIRL' or (N(want) > 0).any())
   np.testing.assert_array_equal(N(plan.rewards), N(want))
+  return (plan, nets) if edit is not None else None   # (the value-edge module then checks, on the oracle's side, that the compared rows hold the logits it is about)
 
 
 def _beta_draws(seed, counter, alpha, n):

@@ -127,17 +127,20 @@ GAIL_CASES = [pytest.param(b, h, *GAIL_LOSSES[i % 4], id=f'{bh(b, h)}-{GAIL_LOSS
               for i, (b, h) in enumerate(_pairs(GAIL_BATCHES, gi.EDGE_HIDDEN_GAIL, shifts=(0, 1, 2)))]
 
 
-def _gail_body(dims, batch, hidden, loss, margin, seed):
+def _gail_body(dims, batch, hidden, loss, margin, seed, edit=None, reward_function='AIRL', reward_close=None, state_only_values=(False, True)):
   """The body of test_gail_ragged_batch_and_state_only (gradient, parameters and reward for both `state_only` values, the module's own initial parameters) with the loss
-  variants of test_gail_loss_variants_match_reference / test_gail_pugail_finite_margin_matches_reference and their bounds."""
+  variants of test_gail_loss_variants_match_reference / test_gail_pugail_finite_margin_matches_reference and their bounds.
+  For tests/test_value_edges_gpu.py: `edit(case)` changes the finished inputs in place; `reward_close(family, got, want, name, logits, **bounds)` takes the place of
+  `close` for the reward (the same bounds, applied per group of rows) and also sees the oracle's logits of the compared rows."""
   g = gi.gail_case(seed, env=dims, hidden=hidden, batch=batch, steps=1)
   eps_mix = gi.gail_extras(seed, g)['eps_mix'][0]
   G._free_last_column(dims, 2, g['policy'][0], g['expert'][0])
+  if edit is not None: edit(g)
   torch.manual_seed(seed)
   grad_atol = 4e-6 if loss == 'BCE' or margin != float('inf') else 1e-5
-  for state_only in (False, True):
+  for state_only in state_only_values:
     icfg = P.Cfg(state_only=state_only, spectral_norm=True, loss_function=loss, grad_penalty=0.5, mixup_alpha=0.7, entropy_bonus=0.01, pos_class_prior=0.7, nonnegative_margin=margin,
-                 discriminator=P.Cfg(hidden_size=hidden, depth=1, activation='relu', reward_shaping=False, subtract_log_policy=False, reward_function='AIRL'))
+                 discriminator=P.Cfg(hidden_size=hidden, depth=1, activation='relu', reward_shaping=False, subtract_log_policy=False, reward_function=reward_function))
     d = P.il.GAILDiscriminator(g['S'], g['A'], icfg, 0.97, device=P.DEV)
     D = g['S'] if state_only else g['D']
     ods = ogail.DiscState(D, hidden, True)
@@ -152,7 +155,9 @@ def _gail_body(dims, batch, hidden, loss, margin, seed):
                             loss_function=loss, pos_class_prior=0.7, nonnegative_margin=margin, eps_mix=eps_mix if loss == 'Mixup' else None)
     close('plain GAIL', P.N(opt.grad), ogr, f'disc grad (state_only={state_only})', atol_scale=grad_atol)
     close('plain GAIL', P.N(d.flat), ods.pack(), f'disc params (state_only={state_only})', atol_scale=4e-6)
-    close('plain GAIL', P.N(d.predict_reward(P.T(pb['states']), P.T(pb['actions']))), ogail.predict_reward(ods, cat(pb)), 'reward', rtol=1e-4, atol_scale=1e-5)
+    got, want = P.N(d.predict_reward(P.T(pb['states']), P.T(pb['actions']))), ogail.predict_reward(ods, cat(pb), reward_function)
+    if reward_close is None: close('plain GAIL', got, want, 'reward', rtol=1e-4, atol_scale=1e-5)
+    else: reward_close('plain GAIL', got, want, f'reward (state_only={state_only})', ogail.disc_logits(ods, cat(pb)), rtol=1e-4, atol_scale=1e-5)
     assert int(opt.step_count[0]) == 1   # (a PUGAIL value pass does not tick the optimiser)
 
 
@@ -180,15 +185,19 @@ SHAPED_CASES = [pytest.param(b, h, *LOSSES3[i % 4], id=f'{bh(b, h)}-{LOSSES3[i %
 def test_shaped_gail_at_edge_sizes(batch, hidden, loss, margin):
   """il_gail_shaped_step / il_gail_shaped_reward (the body of test_shaped_gail_at_edge_widths, its bounds): the gradient of one update and the GAIL-head reward with a
   potential of 1 .. 256 hidden units at batches of 1 .. 65 rows with fractional terminals."""
-  from oracle import gail_shaped as ogs
   i = SHAPED_BATCHES.index(batch)
-  dims = _dims_for(i, batch, hidden)
-  seed = SEEDS['shaped'] + batch + hidden
+  _shaped_body(_dims_for(i, batch, hidden), batch, hidden, loss, margin, SEEDS['shaped'] + batch + hidden)
+
+
+def _shaped_body(dims, batch, hidden, loss, margin, seed, edit=None, reward_function='GAIL', reward_close=None):
+  """The body of test_shaped_gail_at_edge_sizes; `edit`, `reward_function` and `reward_close` as in _gail_body."""
+  from oracle import gail_shaped as ogs
   c = gi.gail_shaped_case(seed, dims, hidden, batch, 1, True)
   em = gi.mixup_draws(seed + 1000, batch, 1)[0]
   G._free_last_column(dims, 5, c['policy'][0], c['expert'][0])
+  if edit is not None: edit(c)
   icfg = P.Cfg(state_only=False, spectral_norm=True, loss_function=loss, grad_penalty=1.0, mixup_alpha=0.7, entropy_bonus=0.0, pos_class_prior=0.7, nonnegative_margin=margin,
-               discriminator=P.Cfg(hidden_size=hidden, depth=1, activation='relu', reward_shaping=True, subtract_log_policy=False, reward_function='GAIL'))
+               discriminator=P.Cfg(hidden_size=hidden, depth=1, activation='relu', reward_shaping=True, subtract_log_policy=False, reward_function=reward_function))
   dd = P.il.GAILDiscriminator(c['S'], c['A'], icfg, 0.99, device=P.DEV)
   assert type(dd).__name__ == 'ShapedGAILDiscriminator'
   ods = ogs.ShapedState(c['S'], c['A'], hidden, 0.99, True)
@@ -204,7 +213,9 @@ def test_shaped_gail_at_edge_sizes(batch, hidden, loss, margin):
   close('shaped GAIL', P.N(opt.grad), og, 'shaped GAIL gradient', rtol=1e-5, atol_scale=1e-5)
   p = P.tbatch(c['policy'][0])
   dd.flat.copy_(P.T(ods.pack()))
-  close('shaped GAIL', P.N(dd.predict_reward(p['states'], p['actions'], p['next_states'], p['terminals'])), ogs.predict_reward(ods, c['policy'][0], 'GAIL'), 'shaped GAIL reward', rtol=2e-5, atol_scale=1e-5)
+  got, want = P.N(dd.predict_reward(p['states'], p['actions'], p['next_states'], p['terminals'])), ogs.predict_reward(ods, c['policy'][0], reward_function)
+  if reward_close is None: close('shaped GAIL', got, want, 'shaped GAIL reward', rtol=2e-5, atol_scale=1e-5)
+  else: reward_close('shaped GAIL', got, want, 'shaped GAIL reward', ogs.forward(ods, *ogs._split(ods, c['policy'][0])[:4])[0], rtol=2e-5, atol_scale=1e-5)
   assert int(opt.step_count[0]) == 1
 
 
@@ -221,13 +232,18 @@ SHAPED_DEEP_CASES = [c for c in DEEP_CASES if c.values[:2] != (65, 128)] + [pyte
 def test_gail_deep_at_edge_sizes(batch, hidden, depth, activation, loss):
   """gail_deep.hip against oracle/gail_deep.py (the body and bounds of test_gail_deep_at_edge_widths): the gradient and the spectral-norm buffers of one update with gradient
   penalty and entropy bonus, the AIRL reward on the oracle's updated parameters; hidden 2 .. 128, batches of 1 .. 65 rows."""
+  _deep_body(_dims_for(SHAPED_BATCHES.index(batch), batch, hidden), batch, hidden, depth, activation, loss, SEEDS['deep'] + batch)
+
+
+def _deep_body(dims, batch, hidden, depth, activation, loss, seed, edit=None, reward_function='AIRL', reward_close=None):
+  """The body of test_gail_deep_at_edge_sizes; `edit`, `reward_function` and `reward_close` as in _gail_body."""
   from oracle import gail_deep as ogd
   lr, wd, gp, ent = 1e-3, 0.1, 0.6, 0.02
-  dims = _dims_for(SHAPED_BATCHES.index(batch), batch, hidden)
-  c = gi.gail_deep_case(seed=SEEDS['deep'] + batch, env=dims, hidden=hidden, batch=batch, steps=1, depth=depth, activation=activation, spectral_norm=True)
+  c = gi.gail_deep_case(seed=seed, env=dims, hidden=hidden, batch=batch, steps=1, depth=depth, activation=activation, spectral_norm=True)
   G._free_last_column(dims, 6, c['policy'][0], c['expert'][0])
+  if edit is not None: edit(c)
   icfg = P.Cfg(state_only=False, spectral_norm=True, loss_function=loss, grad_penalty=gp, mixup_alpha=0.7, entropy_bonus=ent, pos_class_prior=0.7, nonnegative_margin=float('inf'),
-               discriminator=P.Cfg(hidden_size=hidden, depth=depth, activation=activation, reward_shaping=False, subtract_log_policy=False, reward_function='AIRL'))
+               discriminator=P.Cfg(hidden_size=hidden, depth=depth, activation=activation, reward_shaping=False, subtract_log_policy=False, reward_function=reward_function))
   d = P.il.models.DeepGAILDiscriminator(c['S'], c['A'], icfg, 0.97, device=P.DEV)
   ds = ogd.DeepDiscState(c['D'], hidden, depth, activation, True)
   for l in range(depth + 1):
@@ -242,7 +258,9 @@ def test_gail_deep_at_edge_sizes(batch, hidden, depth, activation, loss):
   close('gail_deep', P.N(opt.grad), ogr, 'deep gradient', rtol=2e-5, atol_scale=1e-5)
   close('gail_deep', P.N(d.sn), ds.pack_sn(), 'deep u / v', rtol=2e-5, atol_scale=1e-5)
   d.flat.copy_(P.T(ds.pack()))
-  close('gail_deep', P.N(d.predict_reward(P.T(pb['states']), P.T(pb['actions']))), ogd.predict_reward(ds, cat(pb), 'AIRL'), 'deep reward', rtol=5e-5, atol_scale=1e-5)
+  got, want = P.N(d.predict_reward(P.T(pb['states']), P.T(pb['actions']))), ogd.predict_reward(ds, cat(pb), reward_function)
+  if reward_close is None: close('gail_deep', got, want, 'deep reward', rtol=5e-5, atol_scale=1e-5)
+  else: reward_close('gail_deep', got, want, 'deep reward', ogd.disc_logits(ds, cat(pb)), rtol=5e-5, atol_scale=1e-5)
   assert int(opt.step_count[0]) == 1
 
 
@@ -257,12 +275,16 @@ def _shaped_deep_case(batch, hidden, depth, activation):
 def test_gail_shaped_deep_at_edge_sizes(batch, hidden, depth, activation, loss):
   """gail_shaped_deep.hip against oracle/gail_shaped_deep.py (the body and bounds of test_gail_shaped_deep_at_edge_widths): gradient, u / v, the AIRL reward; a potential of
   2 .. 128 hidden units, batches of 1 .. 65 rows with fractional terminals."""
+  _shaped_deep_body(_shaped_deep_case(batch, hidden, depth, activation), hidden, depth, activation, loss)
+
+
+def _shaped_deep_body(c, hidden, depth, activation, loss, reward_function='AIRL', reward_close=None):
+  """The body of test_gail_shaped_deep_at_edge_sizes on a prepared case; `reward_function` and `reward_close` as in _gail_body."""
   from oracle import gail_shaped_deep as osd
   from test_oracle_golden import _shaped_deep_state
   lr, wd, gp, ent = 1e-3, 0.1, 0.7, 0.01
-  c = _shaped_deep_case(batch, hidden, depth, activation)
   icfg = P.Cfg(state_only=False, spectral_norm=True, loss_function=loss, grad_penalty=gp, mixup_alpha=0.7, entropy_bonus=ent, pos_class_prior=0.7, nonnegative_margin=float('inf'),
-               discriminator=P.Cfg(hidden_size=hidden, depth=depth, activation=activation, reward_shaping=True, subtract_log_policy=False, reward_function='AIRL'))
+               discriminator=P.Cfg(hidden_size=hidden, depth=depth, activation=activation, reward_shaping=True, subtract_log_policy=False, reward_function=reward_function))
   d = P.il.models.ShapedDeepGAILDiscriminator(c['S'], c['A'], icfg, 0.97, device=P.DEV)
   ods = _shaped_deep_state(c)
   d.flat.copy_(P.T(ods.pack())); d.sn.copy_(P.T(ods.pack_sn()))
@@ -276,7 +298,9 @@ def test_gail_shaped_deep_at_edge_sizes(batch, hidden, depth, activation, loss):
   d.flat.copy_(P.T(ods.pack()))
   p = P.tbatch(pb)
   r = d.predict_reward(**P.il.make_gail_input(p['states'], p['actions'], p['next_states'], p['terminals'], None, True, False))
-  close('gail_shaped_deep', P.N(r), osd.predict_reward(ods, pb, 'AIRL'), 'shaped deep reward', rtol=5e-5, atol_scale=1e-5)
+  want = osd.predict_reward(ods, pb, reward_function)
+  if reward_close is None: close('gail_shaped_deep', P.N(r), want, 'shaped deep reward', rtol=5e-5, atol_scale=1e-5)
+  else: reward_close('gail_shaped_deep', P.N(r), want, 'shaped deep reward', osd.forward(ods, *osd._split(ods, pb)[:4])[0], rtol=5e-5, atol_scale=1e-5)
   assert int(opt.step_count[0]) == 1
 
 
@@ -329,10 +353,11 @@ RED_BATCHES = (1, 2, 3, 17, 33, 65)
 RED_CASES = [pytest.param(b, h, id=bh(b, h)) for b, h in _pairs(RED_BATCHES, gi.EDGE_HIDDEN_RED, shifts=(0, 2))]
 
 
-def _red_body(dims, batch, hidden):
+def _red_body(dims, batch, hidden, edit=None):
   from oracle import red as ored
   c = gi.red_case(SEEDS['red'] + batch + hidden, dims, hidden, batch, 2)
   G._free_last_column(dims, 3, *c['batches'], c['query'])
+  if edit is not None: edit(c)   # (tests/test_value_edges_gpu.py: changes the finished inputs in place)
   icfg = P.Cfg(state_only=False, reward_bandwidth_scale=None, discriminator=P.Cfg(hidden_size=hidden, depth=1, activation='relu', input_dropout=0, dropout=0))
   d = P.il.REDDiscriminator(c['S'], c['A'], icfg, device=P.DEV)
   d.flat.copy_(P.T(c['predictor'])); d.target_flat.copy_(P.T(c['target']))
@@ -358,10 +383,11 @@ def test_red_at_edge_sizes(batch, hidden):
   _red_body((NARROW, WIDER)[RED_BATCHES.index(batch) % 2], batch, hidden)
 
 
-def _dril_body(dims, batch, hidden):
+def _dril_body(dims, batch, hidden, edit=None, after_step=None):
   from oracle import dril as odril
   c = gi.dril_case(SEEDS['dril'] + batch + hidden, dims, hidden, batch, 2)
   G._free_last_column(dims, 4, *c['batches'], c['query'])
+  if edit is not None: edit(c)   # (tests/test_value_edges_gpu.py: changes the finished inputs in place)
   a = P.il.SoftActor(c['S'], c['A'], P.Cfg(hidden_size=hidden, depth=1, activation='tanh', input_dropout=0.1, dropout=0.1), device=P.DEV)
   a.flat.copy_(P.T(c['params']))
   opt = P.il.AdamW(a, lr=1e-3, weight_decay=0.0)
@@ -370,6 +396,7 @@ def _dril_body(dims, batch, hidden):
     P.il.behavioural_cloning_update(a, P.tbatch(b), opt, masks=(P.T(m0), P.T(m1)))
     odril.bc_update(ds, b, m0, m1, lr=1e-3, weight_decay=0.0)
     close_params('DRIL', P.N(a.flat), ds.params, f'size edge {bh(batch, hidden)} DRIL params {k}', 1e-3, steps=k)
+    if after_step is not None: after_step(k, P.N(opt.exp_avg), ds.m)   # (tests/test_value_edges_gpu.py: further comparisons, per slab of the parameter vector)
   q = P.tbatch(c['query'])
   ou = odril.uncertainty(ds, c['query']['states'], c['query']['actions'], c['q_m0'], c['q_m1'])
   a.flat.copy_(P.T(ds.params)); u = P.N(a._get_action_uncertainty(q['states'], q['actions'], masks=(P.T(c['q_m0']), P.T(c['q_m1']))))
@@ -450,7 +477,7 @@ ACTOR_CASES = [pytest.param(n, h, GENERAL_DEPTHS[i % 4], GENERAL_ACTS[i % 3], id
                for i, (n, h) in enumerate(_pairs(ACTOR_NS, gi.EDGE_HIDDEN_GENERAL_ACTOR, shifts=(0, 1)))]
 
 
-def _actor_calls(family, c, dims, ns, general):
+def _actor_calls(family, c, dims, ns, general, after_step=None):
   """Acting (a sample with fed noise, its log-probability, the greedy action), log pi of given actions and two behavioural_cloning_update steps against oracle/nets.py
   and osac.bc_update: the bounds of test_general_shape_sac_matches_oracle_and_reference's acting part (general) / of test_bc_and_actor_forward_at_edge_widths (fused)."""
   S, A, H, depth, act = c['S'], c['A'], c['H'], c['depth'], c['activation']
@@ -486,6 +513,7 @@ def _actor_calls(family, c, dims, ns, general):
     close(family, P.N(loss), oloss, f'bc loss {k}', rtol=1e-5, atol_scale=1e-5)
     P.close_params(P.N(actor.flat), p, f'size edge {family} bc actor {k}', 2.5e-4, k); close(family, P.N(opt.exp_avg), m, f'bc m {k}', atol_scale=1e-5 * k)
     _note(family + ' (parameters)', (np.abs(P.N(actor.flat).astype(np.float64) - p) / (1e-5 * np.abs(p) + 1e-5 * np.abs(p).max() + 1.01 * 2.5e-4 * k)).max())
+    if after_step is not None: after_step(k, P.N(opt.exp_avg), m)   # (tests/test_value_edges_gpu.py: further comparisons, per slab of the parameter vector)
   return actor
 
 
@@ -513,7 +541,11 @@ FUSED_CASES = [pytest.param(b, h, id=bh(b, h)) for b, h in FUSED_PAIRS]
                          + [pytest.param(48, 64, ONE, id='B48-H64-S1A1')])
 def test_fused_sac_update_at_edge_sizes(batch, hidden, dims):
   """One fused `il.sac_update` against `osac.sac_update` (the body and bounds of test_sac_update_at_edge_widths) at 3, 5, 7, 9 and 17 row tiles."""
-  c = gi.sac_case(SEEDS['fused'] + batch + hidden, dims, hidden, batch, 1)
+  _fused_sac_body(gi.sac_case(SEEDS['fused'] + batch + hidden, dims, hidden, batch, 1), dims, batch, hidden)
+
+
+def _fused_sac_body(c, dims, batch, hidden):
+  """The body of test_fused_sac_update_at_edge_sizes on a prepared case."""
   G._free_last_column(dims, batch, *c['batches'])
   actor, critic, target, log_alpha, ao, co, to = P.make_sac(c)
   assert not actor.general and not critic.general
