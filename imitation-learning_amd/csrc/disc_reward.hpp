@@ -1,8 +1,9 @@
 // Pieces of the GAIL discriminator shared by gail.hip and sac.hip: parameter layout, the one-wave spectral-norm step, and the eval-mode forward +
-// reward head of one 16-row tile (models.py:152-180). k_gail_reward and the critic-loss workgroups of k_sac_chain (inline relabel) run the SAME
+// reward head (disc_head.hpp) of one 16-row tile (models.py:152-180). k_gail_reward and the critic-loss workgroups of k_sac_chain (inline relabel) run the SAME
 // function with the same thread mapping (the first 256 threads of the workgroup), so the rewards are bit-identical on both paths.
 #pragma once
 #include "il_common.hpp"
+#include "disc_head.hpp"
 
 struct DiscLayout { int64_t oW1, ob1, oW2, ob2, P; };
 __host__ __device__ inline DiscLayout disc_layout(int D, int H, int sn) {
@@ -172,10 +173,8 @@ __device__ __forceinline__ void disc_reward_tile(const il_disc& d, const RewardL
     for (int n = sub; n < H; n += 16) zp += (L.W2s[n] / s2) * fmaxf(dot4(L.W1s + n * ldw, X + r * ldX, Dp) / s1 + L.b1s[n], 0.f);
     zp = group16_sum(zp);
     if (sub == 0 && r < nrows) {
-      const float f = zp + b2, z = logit_offset ? f - logit_offset[row0 + r] : f, Dp_ = sigmoid_f(z);
-      float h = d.reward_function == 1 ? -log1pf(-Dp_ + 1e-6f) : logf(Dp_ + 1e-6f) - log1pf(-Dp_ + 1e-6f);
-      if (d.reward_function == 2) h = expf(h) * -h;
-      emit(r, h, z);
+      const float f = zp + b2, z = logit_offset ? f - logit_offset[row0 + r] : f;
+      emit(r, disc_reward_head(d.reward_function, z), z);
     }
   }
 }

@@ -273,14 +273,6 @@ static int check_dril(const il_dril* d, const il_batch* b) {
   return IL_OK;
 }
 
-static int dril_ensure_lds(const void* fn, size_t bytes) {
-  if (bytes <= 64 * 1024) return IL_OK;
-  if (bytes > 160 * 1024) return il_set_error(IL_ERR_UNSUPPORTED, "kernel needs %zu bytes of LDS (> 160 KiB per CU)", bytes);
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) return il_set_error(IL_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", bytes, hipGetErrorString(e));
-  return IL_OK;
-}
-
 // il_dril_bc_step (ep == NULL, one step) and il_dril_bc_epoch_steps: the same two launches per step
 static int dril_bc_steps(const il_dril* d, const il_batch* expert, const float* mask_in, const float* mask_hidden, const float* mask_hidden2, uint32_t noise_offset,
                          float* out_loss, uint32_t flags, const il_epoch* ep, int steps, il_stream_t stream_) {
@@ -290,7 +282,7 @@ static int dril_bc_steps(const il_dril* d, const il_batch* expert, const float* 
   const int nt = ceil_div(expert->n, DT), depth = dril_depth(*d);
   const size_t lds = dril_lds_floats(DT, d->state_dim, d->hidden, depth, 1) * sizeof(float);
   const auto grad = depth == 2 ? k_dril_grad<2> : k_dril_grad<1>;
-  if (int rc = dril_ensure_lds((const void*)grad, lds)) return rc;
+  if (int rc = il_ensure_lds(grad, lds)) return rc;
   hipStream_t st = (hipStream_t)stream_;
   const int64_t P = dril_layout(d->state_dim, d->action_dim, d->hidden, depth).P;
   const DrilMasks mk = {mask_in, {mask_hidden, mask_hidden2}, noise_offset};
@@ -321,7 +313,7 @@ extern "C" int il_dril_uncertainty(const il_dril* d, const il_batch* batch, cons
   IL_CHECK_ARG(out_uncertainty || out_reward, "il_dril_uncertainty: nothing to write");
   const size_t lds = dril_lds_floats(DU * DRIL_ENSEMBLE, d->state_dim, d->hidden, dril_depth(*d), 0) * sizeof(float);
   const auto unc = dril_depth(*d) == 2 ? k_dril_unc<2> : k_dril_unc<1>;
-  if (int rc = dril_ensure_lds((const void*)unc, lds)) return rc;
+  if (int rc = il_ensure_lds(unc, lds)) return rc;
   const DrilMasks mk = {mask_in, {mask_hidden, mask_hidden2}, noise_offset};
   { IL_TRACE("k_dril_unc", (hipStream_t)stream_);
     unc<<<ceil_div(batch->n, DU), 256, lds, (hipStream_t)stream_>>>(*d, *batch, mk, out_uncertainty, out_reward); }

@@ -9,7 +9,9 @@
 //               through the forward values (<G1^,W1> = sigma1 sum dh (h - b1), ...) so G^ is never materialised.
 //               Each workgroup writes one partial gradient slab; no atomics => deterministic.
 // k_gail_reduce one workgroup: slab sum -> grad, AdamW, spectral-norm buffers update.
-// k_gail_reward eval-mode forward + AIRL / GAIL / FAIRL reward head.
+// k_gail_reward eval-mode forward + the reward head.
+// The calls of an update, the log-policy offset and the reward head are disc_head.hpp's, shared with the other three discriminators; the PUGAIL gate and dL/dz are
+// written out in k_gail_grad (the same arithmetic: see there why).
 #include "il_common.hpp"
 #include "mt_device.hpp"
 #include "mlp_tile.hpp"
@@ -190,7 +192,7 @@ __device__ __forceinline__ void gail_grad_body(il_disc d, il_batch pol, il_batch
   // (12 of a one-tile workgroup's 21 us there) are paid once per workgroup instead of once per tile. Every tile still leaves its own slab: same bits.
   const int pass = blockIdx.y, npass = gridDim.y, nt = (B + IL_TILE_R - 1) / IL_TILE_R, tid = threadIdx.x, tile0 = (int)blockIdx.x * tpw;
   int tile = tile0, row0 = tile * IL_TILE_R, nrows = min(IL_TILE_R, B - row0);
-  const int kind = d.loss_function == IL_LOSS_MIXUP ? (pass == 0 ? 3 : 2) : pass;   // 0 policy, 1 expert, 2 gradient-penalty mix, 3 mixup mix
+  const int kind = disc_kind(d, pass);   // 0 policy, 1 expert, 2 gradient-penalty mix, 3 mixup mix
   const DiscLayout lay = disc_layout(D, H, d.spectral_norm);
   const DiscWs wsl = disc_ws(D, H, B);
   if (pu_value_pass && kind != 0 && kind != 1) return;   // the value pass only needs the logits of the policy and the expert call
@@ -358,15 +360,18 @@ __device__ __forceinline__ void gail_grad_body(il_disc d, il_batch pol, il_batch
   if (kind != 2) {
     const float w = L.wt(0)[r];
     const int row = row0 + min(r, nrows - 1);
-    const float* off = kind == 0 ? x.logit_offset_policy : (kind == 1 ? x.logit_offset_expert : (kind == 3 ? x.logit_offset_mix : nullptr));
+    const float* off = disc_logit_offset(x.logit_offset_policy, x.logit_offset_expert, x.logit_offset_mix, kind);
     const float z = off ? f - off[row] : f;   // subtract_log_policy (models.py:175)
     const bool pu = d.loss_function == IL_LOSS_PUGAIL;
     if (pu_value_pass) {   // training.py:100-102 with a finite margin: V = prior mean(w_e bce(z_e, 0)) - mean(w_p bce(z_p, 0)) decides whether the clamped term has a gradient.
       // This launch only leaves the per-tile sums of w softplus(z) (= w bce(z, 0)); the real launch that follows reads them all and decides (every workgroup the same way).
-      const float part = block_sum(sub == 0 && valid ? w * softplus_f(z) : 0.f, L.red);
+      const float part = block_sum(sub == 0 && valid ? w * softplus_f(z) : 0.f, L.red);   // (block-wide, not disc_tile_sum: the row's value sits in one lane of 16)
       if (tid == 0) d.workspace[wsl.pu + (size_t)kind * nt + tile] = part;
       return;
     }
+    // disc_pu_gate and disc_dz of disc_head.hpp, written out: called as functions they change this kernel's instructions (the gate by three scalar instructions, dz by
+    // 450 lines and a different register assignment; profiles/disc_head_refactor.md), and the timed path ships the parent's code unchanged. A change to either is made
+    // here as well; tests/test_gpu_parity.py and tests/test_value_edges_*.py hold this copy against the same oracle as the other three variants.
     float pu_on = 1.f;   // 1: the clamp passes the gradient (always, with nonnegative_margin = inf)
     if (pu && d.pu_clamped) {
       float se = 0.f, sp = 0.f;
@@ -479,8 +484,6 @@ __global__ __launch_bounds__(256) void k_gail_grad_pop(il_disc d, const il_disc*
   gail_grad_body<true>(d, il_batch{}, il_batch{}, nullptr, il_gail_extra{}, dL, polL, expL, GailSampler{}, 0, tpw, smem);
 }
 
-__host__ __device__ inline int gail_calls(const il_disc& d) { return (d.loss_function == IL_LOSS_MIXUP ? 1 : 2) + (d.grad_penalty > 0.f ? 1 : 0); }
-
 // grid = ceil(P / 256): one gradient element per thread, slabs summed in tile order (deterministic)
 // close_epoch (il_gail_disc_step with IL_FLAG_GAIL_CLOSE_EPOCH): no relabel kernel follows on this stream - the stepped parameters are consumed by the
 // critic-loss workgroups of k_sac_chain - so each workgroup reports [IL_SYNC_PARAMS] and the last one closes the side branch's epoch.
@@ -492,7 +495,7 @@ __global__ __launch_bounds__(256) void k_gail_reduce(il_disc d, int apply, const
   const int S = d.state_dim, A = d.state_only ? 0 : d.action_dim, D = S + A, H = d.hidden, B = d.batch;
   const DiscLayout lay = disc_layout(D, H, d.spectral_norm);
   const DiscWs wsl = disc_ws(D, H, B);
-  const int nt = ((B + IL_TILE_R - 1) / IL_TILE_R) * gail_calls(d);  // one slab per (call, tile)
+  const int nt = ((B + IL_TILE_R - 1) / IL_TILE_R) * disc_calls(d);  // one slab per (call, tile)
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   float pp = 0.f, mm = 0.f, vv = 0.f, g = 0.f;
   if (e < lay.P) {
@@ -608,14 +611,6 @@ __global__ __launch_bounds__(256) void k_gail_reward(il_disc d, il_batch b, floa
   }
 }
 
-static int ensure_lds(const void* fn, size_t bytes) {
-  if (bytes <= 64 * 1024) return IL_OK;
-  if (bytes > 160 * 1024) return il_set_error(IL_ERR_UNSUPPORTED, "kernel needs %zu bytes of LDS (> 160 KiB per CU)", bytes);
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) return il_set_error(IL_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", bytes, hipGetErrorString(e));
-  return IL_OK;
-}
-
 // Dynamic LDS of the single-learner k_gail_grad launches: at least 81 KB, so that its workgroups keep a CU each as they did with the round-3 layout (they are resident
 // early and wait for the index draw; two of them per CU would share the issue slots of the preparation every one of them runs). The population launch asks for what
 // the layout needs (two workgroups per CU).
@@ -643,13 +638,13 @@ extern "C" int il_gail_disc_step(const il_disc* d, const il_batch* pol, const il
   const int D = d->state_dim + (d->state_only ? 0 : d->action_dim);
   const int nt = ceil_div(d->batch, IL_TILE_R);
   const size_t lds = disc_lds_single(D, d->hidden);
-  if (int rc = ensure_lds((const void*)k_gail_grad, lds)) return rc;
+  if (int rc = il_ensure_lds(k_gail_grad, lds)) return rc;
   if (d->loss_function == IL_LOSS_PUGAIL && d->pu_clamped) {   // finite nonnegative_margin: a value pass (logits only) ahead of the gradient pass, which reads the clamp decision
     IL_CHECK_ARG(!d->sync, "il_gail_disc_step: PUGAIL with a finite nonnegative_margin runs on one stream (no il_sync hand-off)");
     IL_CHECK_ARG(d->nonnegative_margin >= 0.f, "il_gail_disc_step: nonnegative_margin must be >= 0");
     { IL_TRACE("k_gail_grad", st); k_gail_grad<<<dim3(nt, 2), 256, lds, st>>>(*d, *pol, *exp, eps_gp, x, nullptr, nullptr, nullptr, GailSampler{}, 1); }
   }
-  { IL_TRACE("k_gail_grad", st); k_gail_grad<<<dim3(nt, gail_calls(*d)), 256, lds, st>>>(*d, *pol, *exp, eps_gp, x, nullptr, nullptr, nullptr, GailSampler{}, 0); }
+  { IL_TRACE("k_gail_grad", st); k_gail_grad<<<dim3(nt, disc_calls(*d)), 256, lds, st>>>(*d, *pol, *exp, eps_gp, x, nullptr, nullptr, nullptr, GailSampler{}, 0); }
   const int64_t P = disc_layout(D, d->hidden, d->spectral_norm).P;
   // (1 KB of LDS it never touches: a workgroup with no LDS can be placed on a CU whose LDS a pair-mode workgroup of the SAC branch holds entirely - sac.hip
   // IL_PAIR_LDS_BYTES - and its loads then queue behind that workgroup's weight stream: measured 4.95 -> 9.4 us for this launch, the relabel 4 us later)
@@ -669,13 +664,13 @@ static int gail_disc_step_draw_impl(const il_disc* d, const il_batch* pol, const
   const int nt = ceil_div(d->batch, IL_TILE_R);
   const size_t lds = disc_lds_single(D, d->hidden);
   IL_CHECK_ARG(lds >= sizeof(MtShared), "il_gail_disc_step_draw: discriminator too small to host the sampler's state in its workgroup LDS");
-  if (int rc = ensure_lds((const void*)k_gail_grad, lds)) return rc;
+  if (int rc = il_ensure_lds(k_gail_grad, lds)) return rc;
   GailSampler sa = {mt_state_dev, ring_state_a, idx_a, ring_state_b, idx_b, d->batch, MtStage{}};
   if (stage_rows) {   // the policy batch IS the agent ring read through idx_a: its packed rows start at `states`
     IL_CHECK_ARG(pol->ld_states % 4 == 0 && (reinterpret_cast<uintptr_t>(pol->states) & 15) == 0 && (reinterpret_cast<uintptr_t>(stage_rows) & 15) == 0, "il_gail_disc_step_draw_staged: packed rows of whole 16-byte lanes");
     sa.stage = MtStage{pol->states, stage_rows, (long long)pol->gather_capacity, pol->ld_states / 4};
   }
-  { IL_TRACE("k_gail_grad", st); k_gail_grad<<<dim3(nt + 1, gail_calls(*d)), 256, lds, st>>>(*d, *pol, *exp, nullptr, il_gail_extra{}, nullptr, nullptr, nullptr, sa, 0); }
+  { IL_TRACE("k_gail_grad", st); k_gail_grad<<<dim3(nt + 1, disc_calls(*d)), 256, lds, st>>>(*d, *pol, *exp, nullptr, il_gail_extra{}, nullptr, nullptr, nullptr, sa, 0); }
   const int64_t P = disc_layout(D, d->hidden, d->spectral_norm).P;
   il_peer_bucket px = {};
   if (peer) {
@@ -716,14 +711,14 @@ extern "C" int il_gail_step_population(const il_disc* descs_dev, const il_batch*
   static const int compact = [] { const char* e = getenv("IL_POP_DISC_LDS"); return e && e[0] == '0' ? 0 : 1; }();   // IL_POP_DISC_LDS=0: one workgroup per CU, as in round 3 (A/B)
   const size_t need = disc_lds_floats(D, d->hidden) * sizeof(float);
   const size_t lds = compact || need > (size_t)96 * 1024 ? need : (size_t)96 * 1024, lds_r = compact ? disc_reward_lds_floats(D, d->hidden) * sizeof(float) : lds;
-  if (int rc = ensure_lds((const void*)k_gail_grad_pop, lds)) return rc;
-  if (int rc = ensure_lds((const void*)k_gail_reward, lds_r)) return rc;
+  if (int rc = il_ensure_lds(k_gail_grad_pop, lds)) return rc;
+  if (int rc = il_ensure_lds(k_gail_reward, lds_r)) return rc;
   const int64_t P = disc_layout(D, d->hidden, d->spectral_norm).P;
   il_batch zb = {};
   // tiles per workgroup of the gradient launch (k_gail_grad `tpw`): IL_POP_DISC_TPW, default 4
   static const int tpw_env = [] { const char* e = getenv("IL_POP_DISC_TPW"); const int v = e ? atoi(e) : 4; return v >= 1 && v <= 64 ? v : 4; }();
   const int tpw = tpw_env < nt ? tpw_env : nt;
-  { IL_TRACE("k_gail_grad", st); k_gail_grad_pop<<<dim3(ceil_div(nt, tpw), gail_calls(*d), L), 256, lds, st>>>(*d, descs_dev, policy_dev, expert_dev, tpw); }
+  { IL_TRACE("k_gail_grad", st); k_gail_grad_pop<<<dim3(ceil_div(nt, tpw), disc_calls(*d), L), 256, lds, st>>>(*d, descs_dev, policy_dev, expert_dev, tpw); }
   { IL_TRACE("k_gail_reduce", st); k_gail_reduce<<<dim3((int)((P + 255) / 256), L), 256, 0, st>>>(*d, 1, descs_dev, 0, il_peer_bucket{}); }
   { IL_TRACE("k_gail_reward", st); k_gail_reward<<<dim3(nt, L), 256, lds_r, st>>>(*d, zb, nullptr, nullptr, nullptr, descs_dev, policy_dev, rewards_out_dev); }
   IL_CHECK_LAUNCH("il_gail_step_population");
@@ -762,7 +757,7 @@ extern "C" int il_gail_reward(const il_disc* d, const il_batch* b, float* out_re
   IL_CHECK_ARG(b && out_rewards && b->n > 0, "il_gail_reward: bad arguments");
   const int D = d->state_dim + (d->state_only ? 0 : d->action_dim);
   const size_t lds = disc_reward_lds_floats(D, d->hidden) * sizeof(float);
-  if (int rc = ensure_lds((const void*)k_gail_reward, lds)) return rc;
+  if (int rc = il_ensure_lds(k_gail_reward, lds)) return rc;
   { IL_TRACE("k_gail_reward", stream_); k_gail_reward<<<ceil_div(b->n, IL_TILE_R), 256, lds, (hipStream_t)stream_>>>(*d, *b, out_rewards, out_logits, logit_offset, nullptr, nullptr, nullptr); }
   IL_CHECK_LAUNCH("il_gail_reward");
   return IL_OK;

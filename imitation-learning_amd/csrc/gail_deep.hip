@@ -7,12 +7,13 @@
 //                weights in LDS, forward, closed-form backward - for the penalty the derivative of the input-gradient pass, with the phi'' terms of tanh
 //                re-entering the forward graph (oracle/gail_deep.py has the derivation) - and writes one slab of dL/dW^ plus <dL/dW^, W> per layer.
 //   k_gd_reduce  slab sums, spectral-norm chain rule per call  dW = G^/sigma - <G^, W>/sigma^2 u v^T,  AdamW, u / v of the last call become the buffers.
-//   k_gd_reward  eval-mode forward + AIRL / GAIL / FAIRL head.
+//   k_gd_reward  eval-mode forward + the reward head.
+// The calls of an update, the loss head dL/dz and the reward head are disc_head.hpp's, shared with the other three discriminators.
 #include "il_common.hpp"
+#include "disc_head.hpp"
 #include "gail_deep_tile.hpp"
 
 __host__ __device__ inline int gd_depth(const il_disc_deep& d) { return d.depth == 2 ? 2 : 1; }
-__host__ __device__ inline int gd_calls(const il_disc_deep& d) { return (d.loss_function == IL_LOSS_MIXUP ? 1 : 2) + (d.grad_penalty > 0.f ? 1 : 0); }
 // workspace: slabs [calls][tiles][P + 4] | call context [3][4 sigmas + sn_numel] | pu [2][tiles]: per-tile sums of w softplus(z) of the policy / expert call
 // (PUGAIL with a finite nonnegative_margin)
 struct GdWs { int64_t slabs, ctx, ctx_stride, slab_stride, pu, total; };
@@ -37,8 +38,7 @@ __global__ __launch_bounds__(256) void k_gd_grad(il_disc_deep d, il_batch pol, i
   const int S = d.state_dim, A = d.state_only ? 0 : d.action_dim, D = S + A, H = d.hidden, B = d.batch, tanh_ = d.activation == 1;
   const int tile = blockIdx.x, call = blockIdx.y, nt = gridDim.x, row0 = tile * GD_R, tid = threadIdx.x, nthr = blockDim.x;
   const int nrows = min(GD_R, B - row0);
-  const bool mixup = d.loss_function == IL_LOSS_MIXUP;
-  const int kind = mixup ? (call == 0 ? 3 : 2) : call;   // 0 policy, 1 expert, 2 gradient-penalty mix, 3 mixup mix
+  const int kind = disc_kind(d, call);   // 0 policy, 1 expert, 2 gradient-penalty mix, 3 mixup mix
   const GdLayout lay = gd_layout(D, H, depth, d.spectral_norm);
   const GdWs ws = gd_ws(D, H, depth, B);
   const GdLds l = gd_carve(smem, D, H, depth);
@@ -87,31 +87,17 @@ __global__ __launch_bounds__(256) void k_gd_grad(il_disc_deep d, il_batch pol, i
   gd_forward(l, lay, H, tanh_);
   const float fB = (float)B;
   if (kind != 2) {
-    // ---- first-order call: dL/dz = w (c_sig sigmoid(z) - c_lab) / B (+ entropy bonus), then plain back-propagation
+    // ---- first-order call: dL/dz (disc_head.hpp), then plain back-propagation
     if (tid < GD_R) {
       const int row = row0 + min(tid, nrows - 1);
-      const float* off = kind == 0 ? x.logit_offset_policy : (kind == 1 ? x.logit_offset_expert : (kind == 3 ? x.logit_offset_mix : nullptr));
+      const float* off = disc_logit_offset(x.logit_offset_policy, x.logit_offset_expert, x.logit_offset_mix, kind);
       const float f = l.row[tid], z = off ? f - off[row] : f;
-      const bool pu = d.loss_function == IL_LOSS_PUGAIL;
-      if (pu_value_pass) {   // training.py:100-102 with a finite margin: this launch (policy and expert call, the same power iterations as the real one) only leaves the
-        // per-tile sums of w softplus(z) = w bce(z, 0); the gradient launch reads them all and decides, every workgroup the same way (gail.hip does the same)
-        const float ws_ = tid < nrows ? wt[tid] * softplus_f(z) : 0.f;
-        float part = 0.f;
-        for (int o = 0; o < GD_R; ++o) part += __shfl(ws_, o, GD_R);
+      if (pu_value_pass) {   // this launch (policy and expert call, the same power iterations as the real one) only leaves the per-tile sums of w softplus(z)
+        const float part = disc_tile_sum<GD_R>(tid < nrows ? wt[tid] * softplus_f(z) : 0.f);
         if (tid == 0) d.workspace[ws.pu + (size_t)kind * nt + tile] = part;
       }
-      float pu_on = 1.f;   // 1: the clamp passes the gradient (always, with nonnegative_margin = inf)
-      if (pu && d.pu_clamped && !pu_value_pass) {
-        float se = 0.f, sp = 0.f;
-        for (int t = 0; t < nt; ++t) { sp += d.workspace[ws.pu + t]; se += d.workspace[ws.pu + nt + t]; }
-        pu_on = d.pos_class_prior * (se / fB) - sp / fB >= -d.nonnegative_margin ? 1.f : 0.f;   // torch.clamp(min = -margin): gradient where the input is not below the bound
-      }
-      const float c_sig = pu ? (kind == 1 ? (1.f + pu_on) * d.pos_class_prior : -pu_on) : 1.f;
-      const float c_lab = kind == 3 ? mix_eps(row) : (kind == 1 ? (pu ? d.pos_class_prior : 1.f) : 0.f);
-      const float p = sigmoid_f(z), w = wt[tid];
-      float dz = tid < nrows ? w * (c_sig * p - c_lab) / fB : 0.f;
-      if (d.entropy_bonus > 0.f && tid < nrows) dz += d.entropy_bonus * w * z * p * (1.f - p) / fB;
-      dzr[tid] = dz;
+      const float pu_on = pu_value_pass ? 1.f : disc_pu_gate(d, d.workspace, ws.pu, nt, fB);
+      dzr[tid] = tid < nrows ? disc_dz(d, z, wt[tid], kind, pu_on, kind == 3 ? mix_eps(row) : 0.f, fB) : 0.f;
     }
     if (pu_value_pass) return;   // uniform: every thread of the workgroup leaves here
     __syncthreads();
@@ -142,37 +128,14 @@ __global__ __launch_bounds__(256) void k_gd_reduce(il_disc_deep d, int apply) {
   const int S = d.state_dim, A = d.state_only ? 0 : d.action_dim, D = S + A, H = d.hidden, B = d.batch;
   const GdLayout lay = gd_layout(D, H, depth, d.spectral_norm);
   const GdWs ws = gd_ws(D, H, depth, B);
-  const int nt = (B + GD_R - 1) / GD_R, calls = gd_calls(d);
+  const int nt = (B + GD_R - 1) / GD_R, calls = disc_calls(d);
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e < lay.P) {
-    int layer = -1, n = 0, k = 0, out_l = 0;
-    int64_t o_l = 4, o_run = 4;   // where the layer's u | v sit in a call's context (found with compile-time indices: a table looked up by `layer` would live in scratch memory)
-#pragma unroll
-    for (int i = 0; i <= depth; ++i) {
-      if (e >= lay.oW[i] && e < lay.oW[i] + (int64_t)lay.out[i] * lay.in[i]) { layer = i; n = (int)((e - lay.oW[i]) / lay.in[i]); k = (int)((e - lay.oW[i]) % lay.in[i]); o_l = o_run; out_l = lay.out[i]; }
-      o_run += lay.out[i] + lay.in[i];
-    }
+    const GdLoc loc = gd_locate<DEPTH>(lay, e);
     float g = 0.f;
-    for (int c = 0; c < calls; ++c) {
-      const float* sl = d.workspace + ws.slabs + (size_t)c * nt * ws.slab_stride;
-      float gc = 0.f;
-      for (int t = 0; t < nt; ++t) gc += sl[(size_t)t * ws.slab_stride + e];
-      if (layer >= 0 && d.spectral_norm) {
-        const float* ctx = d.workspace + ws.ctx + (size_t)c * ws.ctx_stride;
-        float ip = 0.f;
-        for (int t = 0; t < nt; ++t) ip += sl[(size_t)t * ws.slab_stride + lay.P + layer];
-        const float sg = ctx[layer], u = ctx[o_l + n], v = ctx[o_l + out_l + k];
-        gc = gc / sg - (ip / (sg * sg)) * (u * v);
-      }
-      g += gc;
-    }
-    d.grad[e] = g;
-    if (apply) {
-      const adam_consts ac = load_adam_consts(d.opt);
-      float pp = d.params[e], mm = d.opt.m[e], vv = d.opt.v[e];
-      adam_update(pp, g, mm, vv, ac);
-      d.params[e] = pp; d.opt.m[e] = mm; d.opt.v[e] = vv;
-    }
+    for (int c = 0; c < calls; ++c)
+      g += gd_slab_sum(d.workspace + ws.slabs + (size_t)c * nt * ws.slab_stride, ws.slab_stride, nt, e, lay.P, d.workspace + ws.ctx + (size_t)c * ws.ctx_stride, loc, d.spectral_norm);
+    adam_apply_one(d.params, d.grad, d.opt, e, g, apply);
   }
   if (blockIdx.x == 0 && d.spectral_norm) {   // the buffers after this update = the last call's iteration
     const float* ctx = d.workspace + ws.ctx + (size_t)(calls - 1) * ws.ctx_stride + 4;
@@ -197,10 +160,8 @@ __global__ __launch_bounds__(256) void k_gd_reward(il_disc_deep d, il_batch b, f
   __syncthreads();
   gd_forward(l, lay, H, tanh_);
   if (tid < nrows) {
-    const float f = l.row[tid], z = logit_offset ? f - logit_offset[row0 + tid] : f, Dp = sigmoid_f(z);
-    float h = d.reward_function == 1 ? -log1pf(-Dp + 1e-6f) : logf(Dp + 1e-6f) - log1pf(-Dp + 1e-6f);
-    if (d.reward_function == 2) h = expf(h) * -h;
-    out_r[row0 + tid] = h;
+    const float f = l.row[tid], z = logit_offset ? f - logit_offset[row0 + tid] : f;
+    out_r[row0 + tid] = disc_reward_head(d.reward_function, z);
     if (out_logit) out_logit[row0 + tid] = z;
   }
 }
@@ -212,13 +173,6 @@ static int check_gd(const il_disc_deep* d) {
   IL_CHECK_ARG(d->depth >= 0 && d->depth <= 2 && (d->activation == 0 || d->activation == 1), "il_disc_deep: depth must be 1 or 2 (0 = 1) and activation 0 (relu) or 1 (tanh)");
   IL_CHECK_ARG(d->params && (!d->spectral_norm || d->sn), "il_disc_deep: null parameter / spectral-norm arena");
   IL_CHECK_ARG(d->reward_function >= 0 && d->reward_function <= 2, "il_disc_deep: reward_function must be 0 (AIRL), 1 (GAIL) or 2 (FAIRL)");
-  return IL_OK;
-}
-static int gd_ensure_lds(const void* fn, size_t bytes) {
-  if (bytes <= 64 * 1024) return IL_OK;
-  if (bytes > 160 * 1024) return il_set_error(IL_ERR_UNSUPPORTED, "il_disc_deep: this shape needs %zu bytes of LDS (> 160 KiB per CU)", bytes);
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) return il_set_error(IL_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", bytes, hipGetErrorString(e));
   return IL_OK;
 }
 
@@ -235,13 +189,13 @@ extern "C" int il_gail_deep_step(const il_disc_deep* d, const il_batch* pol, con
   const size_t lds = gd_lds_floats(D, d->hidden, depth) * sizeof(float);
   const auto grad = depth == 2 ? k_gd_grad<2> : k_gd_grad<1>;
   const auto reduce = depth == 2 ? k_gd_reduce<2> : k_gd_reduce<1>;
-  if (int rc = gd_ensure_lds((const void*)grad, lds)) return rc;
+  if (int rc = il_ensure_lds(grad, lds)) return rc;
   hipStream_t st = (hipStream_t)stream_;
   if (d->loss_function == IL_LOSS_PUGAIL && d->pu_clamped) {   // finite nonnegative_margin: a value pass (logits only) ahead of the gradient pass, which reads the clamp decision
     IL_CHECK_ARG(d->nonnegative_margin >= 0.f, "il_gail_deep_step: nonnegative_margin must be >= 0");
     { IL_TRACE("k_gd_grad", st); grad<<<dim3(nt, 2), 256, lds, st>>>(*d, *pol, *exp, eps_gp, x, 1); }
   }
-  { IL_TRACE("k_gd_grad", st); grad<<<dim3(nt, gd_calls(*d)), 256, lds, st>>>(*d, *pol, *exp, eps_gp, x, 0); }
+  { IL_TRACE("k_gd_grad", st); grad<<<dim3(nt, disc_calls(*d)), 256, lds, st>>>(*d, *pol, *exp, eps_gp, x, 0); }
   const int64_t P = gd_layout(D, d->hidden, depth, d->spectral_norm).P;
   { IL_TRACE("k_gd_reduce", st); reduce<<<(int)((P + 255) / 256), 256, 0, st>>>(*d, (flags & IL_FLAG_GRADS_ONLY) ? 0 : 1); }
   IL_CHECK_LAUNCH("il_gail_deep_step");
@@ -255,7 +209,7 @@ extern "C" int il_gail_deep_reward(const il_disc_deep* d, const il_batch* b, flo
   const int D = d->state_dim + (d->state_only ? 0 : d->action_dim);
   const size_t lds = gd_lds_floats(D, d->hidden, gd_depth(*d)) * sizeof(float);
   const auto reward = gd_depth(*d) == 2 ? k_gd_reward<2> : k_gd_reward<1>;
-  if (int rc = gd_ensure_lds((const void*)reward, lds)) return rc;
+  if (int rc = il_ensure_lds(reward, lds)) return rc;
   { IL_TRACE("k_gd_reward", stream_); reward<<<ceil_div(b->n, GD_R), 256, lds, (hipStream_t)stream_>>>(*d, *b, out_rewards, out_logits, logit_offset); }
   IL_CHECK_LAUNCH("il_gail_deep_reward");
   return IL_OK;

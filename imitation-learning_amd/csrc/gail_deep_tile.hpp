@@ -345,3 +345,32 @@ __device__ __forceinline__ void gd_inner_products(const GdLds& l, const GdLayout
     __syncthreads();
   }
 }
+
+// ---- reduce kernels (k_gd_reduce, k_gsd_reduce): one parameter per thread
+// Which layer's weight matrix parameter `e` (an offset in `lay`'s order) belongs to (-1: a bias), its row n and column k there, and where that layer's u | v sit in a call
+// context [4 sigmas | per layer u | v]. Found with compile-time indices: a table looked up by `layer` would live in scratch memory.
+struct GdLoc { int layer, n, k, out; int64_t o; };
+template <int DEPTH>
+__device__ __forceinline__ GdLoc gd_locate(const GdLayout& lay, int64_t e) {
+  GdLoc c = {-1, 0, 0, 0, 4};
+  int64_t o_run = 4;
+#pragma unroll
+  for (int i = 0; i <= DEPTH; ++i) {
+    if (e >= lay.oW[i] && e < lay.oW[i] + (int64_t)lay.out[i] * lay.in[i]) { c.layer = i; c.n = (int)((e - lay.oW[i]) / lay.in[i]); c.k = (int)((e - lay.oW[i]) % lay.in[i]); c.o = o_run; c.out = lay.out[i]; }
+    o_run += lay.out[i] + lay.in[i];
+  }
+  return c;
+}
+// Element `e` of one call's (or one use's) slabs summed in tile order; for a spectrally normalised weight the chain rule dW = G^/sigma - <G^, W>/sigma^2 u v^T of that
+// call with its context `ctx` (the tiles' <G^, W> of layer i sit at slab[ip0 + i])
+__device__ __forceinline__ float gd_slab_sum(const float* sl, int64_t stride, int nt, int64_t e, int64_t ip0, const float* ctx, const GdLoc& c, int sn) {
+  float gc = 0.f;
+  for (int t = 0; t < nt; ++t) gc += sl[(size_t)t * stride + e];
+  if (c.layer >= 0 && sn) {
+    float ip = 0.f;
+    for (int t = 0; t < nt; ++t) ip += sl[(size_t)t * stride + ip0 + c.layer];
+    const float sg = ctx[c.layer], u = ctx[c.o + c.n], v = ctx[c.o + c.out + c.k];
+    gc = gc / sg - (ip / (sg * sg)) * (u * v);
+  }
+  return gc;
+}

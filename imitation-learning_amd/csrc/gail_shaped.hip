@@ -9,7 +9,9 @@
 //
 // This is an optional configuration (the default has reward_shaping = false) with a few-KB network: like RED / DRIL it is written as plain VALU loops
 // over LDS-resident tiles (32 rows per workgroup), one gradient slab per (call, tile), a reduce + AdamW kernel, and an eval kernel for the rewards.
+// The calls of an update, the loss head dL/dz and the reward head are disc_head.hpp's, shared with the other three discriminators.
 #include "il_common.hpp"
+#include "disc_head.hpp"
 
 #define GS_R 32
 
@@ -21,9 +23,6 @@ __host__ __device__ inline GsLayout gs_layout(int S, int Dg, int H, int sn) {
   l.P = o;
   return l;
 }
-__host__ __device__ inline int gs_calls(const il_disc_shaped& d) { return (d.loss_function == IL_LOSS_MIXUP ? 1 : 2) + (d.grad_penalty > 0.f ? 1 : 0); }   // Mixup: ONE call on the convex combinations (training.py:104-113)
-// what a call runs on: 0 policy, 1 expert, 2 gradient-penalty mix (training.py:116-126), 3 Mixup mix
-__host__ __device__ inline int gs_kind(const il_disc_shaped& d, int call) { return d.loss_function == IL_LOSS_MIXUP ? (call == 0 ? 3 : 2) : call; }
 struct GsWs { int64_t slabs, sn_new, pu, total; };   // pu: [2][nt] per-tile sums of w softplus(z) of the policy / expert call (PUGAIL with a finite nonnegative_margin)
 __host__ __device__ inline GsWs gs_ws(int S, int Dg, int H, int B) {
   GsWs w; const int64_t P = gs_layout(S, Dg, H, 1).P, nt = (B + GS_R - 1) / GS_R;
@@ -195,46 +194,23 @@ __global__ __launch_bounds__(256) void k_gs_grad(il_disc_shaped d, il_batch pol,
   gs_stage_params(l, d, lay, S, Dg, H);
   if (d.spectral_norm) gs_spectral(l, S, Dg, H, call + 1, 2 * call + 1);
   const uint32_t ctr = d.noise_counter ? *d.noise_counter : 0u;
-  const int kind = gs_kind(d, call);
+  const int kind = disc_kind(d, call);
   gs_stage_rows(l, d, pol, exp, kind, kind == 3 ? x.eps_mix : eps_gp, ctr, row0, S, Dg);
   gs_forward(l, S, Dg, H, d.discount);
   const float s1n = l.sc[5], s2n = l.sc[6], s1s = l.sc[7], s2s = l.sc[8], sg = l.sc[4], fB = (float)B;
   float* coef_n = l.row + 3 * GS_R; float* coef_s = l.row + 4 * GS_R; float* dzr = l.row + 5 * GS_R;
   const bool is_gp = kind == 2;
   if (!is_gp) {
-    if (tid < GS_R) {
+    if (tid < GS_R) {   // dL/dz of the tile's rows (disc_head.hpp)
       const int r = tid, row = row0 + r;
-      float dz = 0.f;
-      const bool pu_gate = d.loss_function == IL_LOSS_PUGAIL && d.pu_clamped;
-      if (pu_value_pass) {   // training.py:100-102 with a finite margin: this launch (the same power iterations as the real one) only leaves the per-tile sums of
-        // w softplus(z) = w bce(z, 0) of the policy / expert call; the gradient launch reads them all and decides, every workgroup the same way (gail.hip does the same)
-        float ws_ = 0.f;
-        if (row < B) {
-          const float* off = kind == 0 ? x.logit_offset_policy : x.logit_offset_expert;
-          const float f = l.row[2 * GS_R + r];
-          ws_ = l.row[GS_R + r] * softplus_f(off ? f - off[row] : f);
-        }
-        float part = 0.f;
-        for (int o = 0; o < GS_R; ++o) part += __shfl(ws_, o, GS_R);
+      const float* off = disc_logit_offset(x.logit_offset_policy, x.logit_offset_expert, x.logit_offset_mix, kind);
+      const float f = l.row[2 * GS_R + r], z = off && row < B ? f - off[row] : f, w = l.row[GS_R + r];
+      if (pu_value_pass) {   // this launch (the same power iterations as the real one) only leaves the per-tile sums of w softplus(z) of the policy / expert call
+        const float part = disc_tile_sum<GS_R>(row < B ? w * softplus_f(z) : 0.f);
         if (tid == 0) d.workspace[wsl.pu + (size_t)call * nt + tile] = part;
       }
-      float pu_on = 1.f;   // 1: the clamp passes the gradient (always, with nonnegative_margin = inf)
-      if (pu_gate && !pu_value_pass) {
-        float se = 0.f, sp = 0.f;
-        for (int t = 0; t < nt; ++t) { sp += d.workspace[wsl.pu + t]; se += d.workspace[wsl.pu + nt + t]; }
-        pu_on = d.pos_class_prior * (se / fB) - sp / fB >= -d.nonnegative_margin ? 1.f : 0.f;   // torch.clamp(min = -margin): gradient where the input is not below the bound
-      }
-      if (row < B) {
-        const float* off = kind == 0 ? x.logit_offset_policy : (kind == 1 ? x.logit_offset_expert : x.logit_offset_mix);
-        const float f = l.row[2 * GS_R + r], z = off ? f - off[row] : f, w = l.row[GS_R + r];
-        const bool pu = d.loss_function == IL_LOSS_PUGAIL;
-        // d loss / d z = w (c_sig sigmoid(z) - c_lab) / B: BCE {1, label}; PUGAIL policy {-1, 0}, expert {2 prior, prior} (clamped away: {0, 0}, {prior, prior}); Mixup {1, eps}
-        const float c_sig = pu ? (kind == 1 ? (1.f + pu_on) * d.pos_class_prior : -pu_on) : 1.f;
-        const float c_lab = kind == 3 ? l.row[6 * GS_R + r] : (kind == 1 ? (pu ? d.pos_class_prior : 1.f) : 0.f);
-        const float p = sigmoid_f(z);
-        dz = w * (c_sig * p - c_lab) / fB;
-        if (d.entropy_bonus > 0.f) dz += d.entropy_bonus * w * z * p * (1.f - p) / fB;
-      }
+      const float pu_on = pu_value_pass ? 1.f : disc_pu_gate(d, d.workspace, wsl.pu, nt, fB);
+      const float dz = row < B ? disc_dz(d, z, w, kind, pu_on, kind == 3 ? l.row[6 * GS_R + r] : 0.f, fB) : 0.f;
       dzr[r] = dz; coef_n[r] = dz * (1.f - l.row[r]) * d.discount; coef_s[r] = -dz * (1.f - l.row[r]);
     }
     if (pu_value_pass) return;   // uniform: every thread of the workgroup leaves here
@@ -344,19 +320,12 @@ __global__ __launch_bounds__(256) void k_gs_reduce(il_disc_shaped d, int apply) 
   const int S = d.state_dim, Dg = d.state_only ? S : S + d.action_dim, H = d.hidden;
   const GsLayout lay = gs_layout(S, Dg, H, d.spectral_norm);
   const GsWs wsl = gs_ws(S, Dg, H, d.batch);
-  const int nslabs = ((d.batch + GS_R - 1) / GS_R) * gs_calls(d);
+  const int nslabs = ((d.batch + GS_R - 1) / GS_R) * disc_calls(d);
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e < lay.P) {
-    float pp = d.params[e], mm = 0.f, vv = 0.f;
-    if (apply) { mm = d.opt.m[e]; vv = d.opt.v[e]; }
     float g = 0.f;
     for (int t = 0; t < nslabs; ++t) g += d.workspace[wsl.slabs + (size_t)t * lay.P + e];
-    d.grad[e] = g;
-    if (apply) {
-      const adam_consts ac = load_adam_consts(d.opt);
-      adam_update(pp, g, mm, vv, ac);
-      d.params[e] = pp; d.opt.m[e] = mm; d.opt.v[e] = vv;
-    }
+    adam_apply_one(d.params, d.grad, d.opt, e, g, apply);
   }
   if (blockIdx.x == 0 && d.spectral_norm) {
     const float* o = d.workspace + wsl.sn_new;
@@ -379,10 +348,8 @@ __global__ __launch_bounds__(256) void k_gs_reward(il_disc_shaped d, il_batch b,
   gs_forward(l, S, Dg, H, d.discount);
   if (threadIdx.x < GS_R && row0 + threadIdx.x < b.n) {
     const int row = row0 + threadIdx.x;
-    const float f = l.row[2 * GS_R + threadIdx.x], z = logit_offset ? f - logit_offset[row] : f, Dp = sigmoid_f(z);
-    float h = d.reward_function == 1 ? -log1pf(-Dp + 1e-6f) : logf(Dp + 1e-6f) - log1pf(-Dp + 1e-6f);
-    if (d.reward_function == 2) h = expf(h) * -h;
-    out_r[row] = h;
+    const float f = l.row[2 * GS_R + threadIdx.x], z = logit_offset ? f - logit_offset[row] : f;
+    out_r[row] = disc_reward_head(d.reward_function, z);
     if (out_logit) out_logit[row] = z;
   }
 }
@@ -398,12 +365,6 @@ static int check_gs(const il_disc_shaped* d) {
   if (d->workspace_floats < gs_ws(S, Dg, d->hidden, d->batch).total) return il_set_error(IL_ERR_WORKSPACE, "il_disc_shaped: workspace too small");
   return IL_OK;
 }
-static int gs_ensure_lds(const void* fn, size_t bytes) {
-  if (bytes <= 64 * 1024) return IL_OK;
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) return il_set_error(IL_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", bytes, hipGetErrorString(e));
-  return IL_OK;
-}
 
 extern "C" int il_gail_shaped_step(const il_disc_shaped* d, const il_batch* pol, const il_batch* exp, const float* eps_gp, const il_gail_extra* extra, uint32_t flags, il_stream_t stream_) {
   IL_NO_GATHER(pol, "il_gail_shaped_step"); IL_NO_GATHER(exp, "il_gail_shaped_step");
@@ -415,13 +376,13 @@ extern "C" int il_gail_shaped_step(const il_disc_shaped* d, const il_batch* pol,
   IL_CHECK_ARG(d->loss_function != IL_LOSS_MIXUP || (!x.logit_offset_policy && !x.logit_offset_expert), "il_gail_shaped_step: with Mixup the log-policy offset belongs to the mixed batch (logit_offset_mix)");
   const int S = d->state_dim, Dg = d->state_only ? S : S + d->action_dim;
   const size_t lds = gs_lds_floats(S, Dg, d->hidden) * sizeof(float);
-  if (int rc = gs_ensure_lds((const void*)k_gs_grad, lds)) return rc;
+  if (int rc = il_ensure_lds(k_gs_grad, lds)) return rc;
   hipStream_t st = (hipStream_t)stream_;
   if (d->loss_function == IL_LOSS_PUGAIL && d->pu_clamped) {   // finite nonnegative_margin: a value pass (logits only) ahead of the gradient pass, which reads the clamp decision
     IL_CHECK_ARG(d->nonnegative_margin >= 0.f, "il_gail_shaped_step: nonnegative_margin must be >= 0");
     { IL_TRACE("k_gs_grad", st); k_gs_grad<<<dim3(ceil_div(d->batch, GS_R), 2), 256, lds, st>>>(*d, *pol, *exp, eps_gp, x, 1); }
   }
-  { IL_TRACE("k_gs_grad", st); k_gs_grad<<<dim3(ceil_div(d->batch, GS_R), gs_calls(*d)), 256, lds, st>>>(*d, *pol, *exp, eps_gp, x, 0); }
+  { IL_TRACE("k_gs_grad", st); k_gs_grad<<<dim3(ceil_div(d->batch, GS_R), disc_calls(*d)), 256, lds, st>>>(*d, *pol, *exp, eps_gp, x, 0); }
   const int64_t P = gs_layout(S, Dg, d->hidden, d->spectral_norm).P;
   { IL_TRACE("k_gs_reduce", st); k_gs_reduce<<<(int)((P + 255) / 256), 256, 0, st>>>(*d, (flags & IL_FLAG_GRADS_ONLY) ? 0 : 1); }
   IL_CHECK_LAUNCH("il_gail_shaped_step");
@@ -434,7 +395,7 @@ extern "C" int il_gail_shaped_reward(const il_disc_shaped* d, const il_batch* b,
   IL_CHECK_ARG(b && out_rewards && b->n > 0 && b->next_states && b->terminals, "il_gail_shaped_reward: bad arguments (next_states and terminals are inputs of the shaping term)");
   const int S = d->state_dim, Dg = d->state_only ? S : S + d->action_dim;
   const size_t lds = gs_lds_floats(S, Dg, d->hidden) * sizeof(float);
-  if (int rc = gs_ensure_lds((const void*)k_gs_reward, lds)) return rc;
+  if (int rc = il_ensure_lds(k_gs_reward, lds)) return rc;
   { IL_TRACE("k_gs_reward", (hipStream_t)stream_); k_gs_reward<<<ceil_div(b->n, GS_R), 256, lds, (hipStream_t)stream_>>>(*d, *b, out_rewards, out_logits, logit_offset); }
   IL_CHECK_LAUNCH("il_gail_shaped_reward");
   return IL_OK;

@@ -13,8 +13,10 @@
 //                 own coefficient dz (1 - t) discount / -dz (1 - t). The second-use workgroup also owns g (chain rule applied per tile: it is linear in G^) and,
 //                 in the gradient-penalty call, the whole penalty (the first-use workgroups of that call have nothing to do and leave at once).
 //   k_gsd_reduce  slab sums in (call, use, tile) order, chain rule per (call, use) for h, AdamW, the last call's second-use (u, v) become the buffers.
-//   k_gsd_reward  eval-mode forward (no power iteration: both uses see the same weights) + AIRL / GAIL / FAIRL head.
+//   k_gsd_reward  eval-mode forward (no power iteration: both uses see the same weights) + the reward head.
+// The calls of an update, the loss head dL/dz and the reward head are disc_head.hpp's, shared with the other three discriminators.
 #include "il_common.hpp"
+#include "disc_head.hpp"
 #include "gail_deep_tile.hpp"
 
 struct GsdLayout { int64_t oWg, obg, oh, P; };   // g, then h's layers in gd_layout order from `oh`
@@ -26,9 +28,6 @@ __host__ __device__ inline GsdLayout gsd_layout(int S, int Dg, int H, int depth,
 }
 __host__ __device__ inline int gsd_depth(const il_disc_shaped_deep& d) { return d.depth == 2 ? 2 : 1; }
 __host__ __device__ inline int gsd_dg(const il_disc_shaped_deep& d) { return d.state_only ? d.state_dim : d.state_dim + d.action_dim; }
-__host__ __device__ inline int gsd_calls(const il_disc_shaped_deep& d) { return (d.loss_function == IL_LOSS_MIXUP ? 1 : 2) + (d.grad_penalty > 0.f ? 1 : 0); }
-// what a call runs on: 0 policy, 1 expert, 2 gradient-penalty mix (training.py:116-126), 3 Mixup mix (training.py:104-113)
-__host__ __device__ inline int gsd_kind(const il_disc_shaped_deep& d, int call) { return d.loss_function == IL_LOSS_MIXUP ? (call == 0 ? 3 : 2) : call; }
 __host__ __device__ inline int64_t gsd_sn_numel(int S, int Dg, int H, int depth) { return 1 + Dg + gd_sn_numel(S, H, depth); }   // ug | vg | h: per layer u | v
 // workspace: slabs [3 calls][2 uses][tiles][P + 4: the parameters, then <G^, W> of h's layers] | context [3][2][4 sigmas of h + h's u | v] |
 //            g's (u, v) after the update [1 + Dg] | pu [2][tiles]: per-tile sums of w softplus(z) of the policy / expert call (PUGAIL with a finite nonnegative_margin)
@@ -205,7 +204,7 @@ __global__ __launch_bounds__(256) void k_gsd_grad(il_disc_shaped_deep d, il_batc
   const int tile = blockIdx.x, call = blockIdx.y, nt = gridDim.x, row0 = tile * GD_R, tid = threadIdx.x, nthr = blockDim.x;
   const int q = pu_value_pass ? 1 : (int)blockIdx.z;
   const int nrows = min(GD_R, B - row0);
-  const int kind = gsd_kind(d, call);
+  const int kind = disc_kind(d, call);
   if (kind == 2 && q == 0) return;   // the penalty goes through the second use only (k_gsd_reduce skips this slab)
   const GsdLayout lay = gsd_layout(S, Dg, H, DEPTH, d.spectral_norm);
   const GdLayout layh = gd_layout(S, H, DEPTH, d.spectral_norm);
@@ -225,31 +224,17 @@ __global__ __launch_bounds__(256) void k_gsd_grad(il_disc_shaped_deep d, il_batc
   const float sg = g.gsc[2], fB = (float)B;
   float* dzr = g.rw + 6 * GD_R; float* coef = g.rw + 7 * GD_R; float* c2 = g.rw + 9 * GD_R; float* kr = g.rw + 10 * GD_R;
   if (kind != 2) {
-    // ---- first-order call: dL/dz = w (c_sig sigmoid(z) - c_lab) / B (+ entropy bonus); this use's share of it goes back through h
+    // ---- first-order call: dL/dz (disc_head.hpp); this use's share of it goes back through h
     if (tid < GD_R) {
       const int row = row0 + min(tid, nrows - 1);
-      const float* off = kind == 0 ? x.logit_offset_policy : (kind == 1 ? x.logit_offset_expert : x.logit_offset_mix);
+      const float* off = disc_logit_offset(x.logit_offset_policy, x.logit_offset_expert, x.logit_offset_mix, kind);
       const float f = g.rw[5 * GD_R + tid], z = off ? f - off[row] : f, w = g.rw[GD_R + tid], t = g.rw[tid];
-      const bool pu = d.loss_function == IL_LOSS_PUGAIL;
-      if (pu_value_pass) {   // training.py:100-102 with a finite margin: this launch (policy and expert call, the same power iterations as the real one) only leaves the
-        // per-tile sums of w softplus(z) = w bce(z, 0); the gradient launch reads them all and decides, every workgroup the same way (gail.hip does the same)
-        const float ws_ = tid < nrows ? w * softplus_f(z) : 0.f;
-        float part = 0.f;
-        for (int o = 0; o < GD_R; ++o) part += __shfl(ws_, o, GD_R);
+      if (pu_value_pass) {   // this launch (policy and expert call, the same power iterations as the real one) only leaves the per-tile sums of w softplus(z)
+        const float part = disc_tile_sum<GD_R>(tid < nrows ? w * softplus_f(z) : 0.f);
         if (tid == 0) d.workspace[ws.pu + (size_t)kind * nt + tile] = part;
       }
-      float pu_on = 1.f;   // 1: the clamp passes the gradient (always, with nonnegative_margin = inf)
-      if (pu && d.pu_clamped && !pu_value_pass) {
-        float se = 0.f, sp = 0.f;
-        for (int tt = 0; tt < nt; ++tt) { sp += d.workspace[ws.pu + tt]; se += d.workspace[ws.pu + nt + tt]; }
-        pu_on = d.pos_class_prior * (se / fB) - sp / fB >= -d.nonnegative_margin ? 1.f : 0.f;   // torch.clamp(min = -margin): gradient where the input is not below the bound
-      }
-      // BCE {1, label}; PUGAIL policy {-1, 0}, expert {2 prior, prior} (clamped away: {0, 0}, {prior, prior}); Mixup {1, eps}
-      const float c_sig = pu ? (kind == 1 ? (1.f + pu_on) * d.pos_class_prior : -pu_on) : 1.f;
-      const float c_lab = kind == 3 ? g.rw[8 * GD_R + tid] : (kind == 1 ? (pu ? d.pos_class_prior : 1.f) : 0.f);
-      const float p = sigmoid_f(z);
-      float dz = tid < nrows ? w * (c_sig * p - c_lab) / fB : 0.f;
-      if (d.entropy_bonus > 0.f && tid < nrows) dz += d.entropy_bonus * w * z * p * (1.f - p) / fB;
+      const float pu_on = pu_value_pass ? 1.f : disc_pu_gate(d, d.workspace, ws.pu, nt, fB);
+      const float dz = tid < nrows ? disc_dz(d, z, w, kind, pu_on, g.rw[8 * GD_R + tid], fB) : 0.f;
       dzr[tid] = dz;
       coef[tid] = q == 0 ? dz * (1.f - t) * d.discount : -dz * (1.f - t);
     }
@@ -318,40 +303,18 @@ __global__ __launch_bounds__(256) void k_gsd_reduce(il_disc_shaped_deep d, int a
   const GsdLayout lay = gsd_layout(S, Dg, H, depth, d.spectral_norm);
   const GdLayout layh = gd_layout(S, H, depth, d.spectral_norm);
   const GsdWs ws = gsd_ws(S, Dg, H, depth, B);
-  const int nt = (B + GD_R - 1) / GD_R, calls = gsd_calls(d);
+  const int nt = (B + GD_R - 1) / GD_R, calls = disc_calls(d);
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e < lay.P) {
-    int layer = -1, n = 0, k = 0, out_l = 0;
-    int64_t o_l = 4, o_run = 4;   // where the layer's u | v sit in a (call, use) context (compile-time indices: a table looked up by `layer` would live in scratch memory)
-    const int64_t eh = e - lay.oh;
-#pragma unroll
-    for (int i = 0; i <= depth; ++i) {
-      if (eh >= layh.oW[i] && eh < layh.oW[i] + (int64_t)layh.out[i] * layh.in[i]) { layer = i; n = (int)((eh - layh.oW[i]) / layh.in[i]); k = (int)((eh - layh.oW[i]) % layh.in[i]); o_l = o_run; out_l = layh.out[i]; }
-      o_run += layh.out[i] + layh.in[i];
-    }
+    const GdLoc loc = gd_locate<DEPTH>(layh, e - lay.oh);   // (g's parameters, in front of h's, are in no layer of h: their chain rule was applied per tile)
     float gsum = 0.f;
     for (int c = 0; c < calls; ++c)
       for (int q = 0; q < 2; ++q) {
-        if (gsd_kind(d, c) == 2 && q == 0) continue;   // nothing was written there
-        const float* sl = d.workspace + ws.slabs + ((size_t)c * 2 + q) * nt * ws.slab_stride;
-        float gc = 0.f;
-        for (int t = 0; t < nt; ++t) gc += sl[(size_t)t * ws.slab_stride + e];
-        if (layer >= 0 && d.spectral_norm) {
-          const float* ctx = d.workspace + ws.ctx + ((size_t)c * 2 + q) * ws.ctx_stride;
-          float ip = 0.f;
-          for (int t = 0; t < nt; ++t) ip += sl[(size_t)t * ws.slab_stride + lay.P + layer];
-          const float sg = ctx[layer], u = ctx[o_l + n], v = ctx[o_l + out_l + k];
-          gc = gc / sg - (ip / (sg * sg)) * (u * v);
-        }
-        gsum += gc;
+        if (disc_kind(d, c) == 2 && q == 0) continue;   // nothing was written there
+        const size_t cq = (size_t)c * 2 + q;
+        gsum += gd_slab_sum(d.workspace + ws.slabs + cq * nt * ws.slab_stride, ws.slab_stride, nt, e, lay.P, d.workspace + ws.ctx + cq * ws.ctx_stride, loc, d.spectral_norm);
       }
-    d.grad[e] = gsum;
-    if (apply) {
-      const adam_consts ac = load_adam_consts(d.opt);
-      float pp = d.params[e], mm = d.opt.m[e], vv = d.opt.v[e];
-      adam_update(pp, gsum, mm, vv, ac);
-      d.params[e] = pp; d.opt.m[e] = mm; d.opt.v[e] = vv;
-    }
+    adam_apply_one(d.params, d.grad, d.opt, e, gsum, apply);
   }
   if (blockIdx.x == 0 && d.spectral_norm) {   // the buffers after this update: g's from the last call, h's from the last call's second use
     const float* og = d.workspace + ws.sn_g;
@@ -381,10 +344,8 @@ __global__ __launch_bounds__(256) void k_gsd_reward(il_disc_shaped_deep d, il_ba
   gsd_forward<DEPTH>(l, g, layh, d, lay, b, b, 0, 1, -1, nullptr, row0, nrows, S, A, Dg, H, tanh_);
   if (tid < nrows) {
     const int row = row0 + tid;
-    const float f = g.rw[5 * GD_R + tid], z = logit_offset ? f - logit_offset[row] : f, Dp = sigmoid_f(z);
-    float h = d.reward_function == 1 ? -log1pf(-Dp + 1e-6f) : logf(Dp + 1e-6f) - log1pf(-Dp + 1e-6f);
-    if (d.reward_function == 2) h = expf(h) * -h;
-    out_r[row] = h;
+    const float f = g.rw[5 * GD_R + tid], z = logit_offset ? f - logit_offset[row] : f;
+    out_r[row] = disc_reward_head(d.reward_function, z);
     if (out_logit) out_logit[row] = z;
   }
 }
@@ -398,13 +359,6 @@ static int check_gsd(const il_disc_shaped_deep* d) {
                "il_disc_shaped_deep: reward_function in {0,1,2}, loss_function BCE, PUGAIL or Mixup");
   IL_CHECK_ARG(!d->spectral_norm || d->sn, "il_disc_shaped_deep: spectral-norm buffers missing");
   if (d->workspace_floats < gsd_ws(S, Dg, d->hidden, gsd_depth(*d), d->batch).total) return il_set_error(IL_ERR_WORKSPACE, "il_disc_shaped_deep: workspace too small");
-  return IL_OK;
-}
-static int gsd_ensure_lds(const void* fn, size_t bytes) {
-  if (bytes <= 64 * 1024) return IL_OK;
-  if (bytes > 160 * 1024) return il_set_error(IL_ERR_UNSUPPORTED, "il_disc_shaped_deep: this shape needs %zu bytes of LDS (> 160 KiB per CU)", bytes);
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) return il_set_error(IL_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", bytes, hipGetErrorString(e));
   return IL_OK;
 }
 
@@ -423,13 +377,13 @@ extern "C" int il_gail_shaped_deep_step(const il_disc_shaped_deep* d, const il_b
   const size_t lds = gsd_lds_floats(S, Dg, d->hidden, depth) * sizeof(float);
   const auto grad = depth == 2 ? k_gsd_grad<2> : k_gsd_grad<1>;
   const auto reduce = depth == 2 ? k_gsd_reduce<2> : k_gsd_reduce<1>;
-  if (int rc = gsd_ensure_lds((const void*)grad, lds)) return rc;
+  if (int rc = il_ensure_lds(grad, lds)) return rc;
   hipStream_t st = (hipStream_t)stream_;
   if (d->loss_function == IL_LOSS_PUGAIL && d->pu_clamped) {   // finite nonnegative_margin: a value pass (logits only) ahead of the gradient pass, which reads the clamp decision
     IL_CHECK_ARG(d->nonnegative_margin >= 0.f, "il_gail_shaped_deep_step: nonnegative_margin must be >= 0");
     { IL_TRACE("k_gsd_grad", st); grad<<<dim3(nt, 2, 1), 256, lds, st>>>(*d, *pol, *exp, eps_gp, x, 1); }
   }
-  { IL_TRACE("k_gsd_grad", st); grad<<<dim3(nt, gsd_calls(*d), 2), 256, lds, st>>>(*d, *pol, *exp, eps_gp, x, 0); }
+  { IL_TRACE("k_gsd_grad", st); grad<<<dim3(nt, disc_calls(*d), 2), 256, lds, st>>>(*d, *pol, *exp, eps_gp, x, 0); }
   const int64_t P = gsd_layout(S, Dg, d->hidden, depth, d->spectral_norm).P;
   { IL_TRACE("k_gsd_reduce", st); reduce<<<(int)((P + 255) / 256), 256, 0, st>>>(*d, (flags & IL_FLAG_GRADS_ONLY) ? 0 : 1); }
   IL_CHECK_LAUNCH("il_gail_shaped_deep_step");
@@ -443,7 +397,7 @@ extern "C" int il_gail_shaped_deep_reward(const il_disc_shaped_deep* d, const il
   const int S = d->state_dim, Dg = d->state_only ? S : S + d->action_dim, depth = gsd_depth(*d);
   const size_t lds = gsd_lds_floats(S, Dg, d->hidden, depth) * sizeof(float);
   const auto reward = depth == 2 ? k_gsd_reward<2> : k_gsd_reward<1>;
-  if (int rc = gsd_ensure_lds((const void*)reward, lds)) return rc;
+  if (int rc = il_ensure_lds(reward, lds)) return rc;
   { IL_TRACE("k_gsd_reward", (hipStream_t)stream_); reward<<<ceil_div(b->n, GD_R), 256, lds, (hipStream_t)stream_>>>(*d, *b, out_rewards, out_logits, logit_offset); }
   IL_CHECK_LAUNCH("il_gail_shaped_deep_reward");
   return IL_OK;

@@ -324,12 +324,6 @@ static int g_check_shape(const GNet& s, const char* who) {
   return IL_OK;
 }
 static size_t g_lds(int F) { return (size_t)16 * (round_up16(F) + 4) * sizeof(float); }
-static int g_lds_ok(const void* fn, size_t bytes) {
-  if (bytes <= 64 * 1024) return IL_OK;
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) return il_set_error(IL_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", bytes, hipGetErrorString(e));
-  return IL_OK;
-}
 // hidden activations of `nets` networks: [net][layer 1 .. depth][H][Bp]; output [net][out][Bp]
 static inline int64_t g_hidden_floats(const GNet& s, int Bp) { return (int64_t)s.depth * s.H * Bp; }
 
@@ -343,7 +337,7 @@ static int g_forward(hipStream_t st, const GNet& s, const float* P, int64_t p_ns
     a.YT = l == s.depth ? OT : HT + (int64_t)l * s.H * Bp; a.y_ns = l == s.depth ? (int64_t)s.out * Bp : h_ns;
     a.Bp = Bp; a.act = l == s.depth ? G_ACT_NONE : s.act;
     const size_t lds = g_lds(L.K);
-    if (int rc = g_lds_ok((const void*)k_g_linear, lds)) return rc;
+    if (int rc = il_ensure_lds(k_g_linear, lds)) return rc;
     { IL_TRACE("k_g_linear", st); k_g_linear<<<dim3(Bp / 16, (L.N + 63) / 64, nets), 256, lds, st>>>(a); }
   }
   return IL_OK;
@@ -367,7 +361,7 @@ static int g_backward(hipStream_t st, const GNet& s, const float* P, int64_t p_n
       a.dXT = l > 0 ? dZT + (int64_t)(l - 1) * s.H * Bp : dX0T; a.dx_ns = l > 0 ? h_ns : (int64_t)s.in * Bp;
       a.Bp = Bp; a.act = s.act;
       const size_t lds = g_lds(L.N);
-      if (int rc = g_lds_ok((const void*)k_g_bwd, lds)) return rc;
+      if (int rc = il_ensure_lds(k_g_bwd, lds)) return rc;
       { IL_TRACE("k_g_bwd", st); k_g_bwd<<<dim3(Bp / 16, (L.K + 63) / 64, nets), 256, lds, st>>>(a); }
     }
   }
@@ -896,8 +890,8 @@ static int g_sac_update_tiles(const il_sac* d, const il_batch* b, const GNet& an
   const bool pack_a = gt_packable(an, d->actor), pack_c = gt_packable(cn, d->critic) && gt_packable(cn, d->target) && (Ps & 3) == 0;
   float* ga = grads_only ? d->actor_grad : W + ws.ga; float* gc = grads_only ? d->critic_grad : W + ws.gc;
   const size_t lds_f = gt_fwd_lds(an) > gt_fwd_lds(cn) ? gt_fwd_lds(an) : gt_fwd_lds(cn), lds_b = gt_bwd_lds(an) > gt_bwd_lds(cn) ? gt_bwd_lds(an) : gt_bwd_lds(cn);
-  if (int rc = g_lds_ok((const void*)k_gt_fwd, lds_f)) return rc;
-  if (int rc = g_lds_ok((const void*)k_gt_bwd, lds_b)) return rc;
+  if (int rc = il_ensure_lds(k_gt_fwd, lds_f)) return rc;
+  if (int rc = il_ensure_lds(k_gt_bwd, lds_b)) return rc;
   const int th_a = gt_threads(an.H), th_c = gt_threads(cn.H), th_m = th_a > th_c ? th_a : th_c;
   // 0. lane-ordered copies of every H x H layer (the critics' are kept in step by their optimiser launch below: the policy pass reads the stepped critics)
   {
@@ -1081,7 +1075,7 @@ extern "C" int il_actor_act_general(const float* actor, int32_t S, int32_t A, in
   const GActWs ws = g_act_ws(S, A, H, depth, Bp);
   if (gt_env() && gt_shape_ok(an)) {   // tile engine: one launch (rows -> every layer -> head)
     const size_t lds = gt_fwd_lds(an);
-    if (int rc = g_lds_ok((const void*)k_gt_fwd, lds)) return rc;
+    if (int rc = il_ensure_lds(k_gt_fwd, lds)) return rc;
     GtFwd f = {}; f.n = n; f.Bp = Bp;
     GtFwdPass& p0 = f.p[0]; p0.net = GtNet{actor, S, H, depth, 2 * A, activation, nullptr, nullptr}; p0.f1 = states; p0.ld1 = ld_states; p0.K1 = S; p0.head = 1; p0.eps = eps; p0.seed = noise_seed; p0.ctr = noise_offset;
     p0.stream_id = IL_STREAM_ACT; p0.greedy = greedy; p0.a_rows = out_action; p0.ld_a = A; p0.logp = out_logp;
@@ -1130,8 +1124,8 @@ static int bc_step_general(float* actor, float* actor_grad, const il_adam* opt, 
   float* G = actor_grad ? actor_grad : workspace + ws.g;
   if (gt_env() && gt_shape_ok(an)) {   // tile engine: forward, BC seed + backward, every layer's dW + AdamW: three launches
     const size_t lds_f = gt_fwd_lds(an), lds_b = gt_bwd_lds(an);
-    if (int rc = g_lds_ok((const void*)k_gt_fwd, lds_f)) return rc;
-    if (int rc = g_lds_ok((const void*)k_gt_bwd, lds_b)) return rc;
+    if (int rc = il_ensure_lds(k_gt_fwd, lds_f)) return rc;
+    if (int rc = il_ensure_lds(k_gt_bwd, lds_b)) return rc;
     const GtNet net = {actor, S, H, depth, 2 * A, activation, nullptr, nullptr};
     GtFwd f = {}; f.n = n; f.Bp = Bp;
     GtFwdPass& p0 = f.p[0]; p0.net = net; p0.f1 = b->states; p0.ld1 = b->ld_states; p0.K1 = S; p0.X0T = workspace + ws.x; p0.HT = workspace + ws.h; p0.OT = workspace + ws.o;
@@ -1293,7 +1287,7 @@ extern "C" int il_act_step_general(const float* actor, int32_t S, int32_t A, int
   a.row = il_ring_row_floats(S, A); a.seed = noise_seed; a.offset = noise_offset; a.version = mirror_version; a.mirror_stride = mirror_stride;
   if (gt_env() && gt_shape_ok(an)) {   // the predicate of il_actor_act_general: whatever the per-function path does for a shape, the worker does the same arithmetic
     const size_t lds = gt_fwd_lds(an);
-    if (int rc = g_lds_ok((const void*)k_act_step_general, lds)) return rc;
+    if (int rc = il_ensure_lds(k_act_step_general, lds)) return rc;
     { IL_TRACE("k_act_step_general", st); k_act_step_general<<<1, gt_threads(H), lds, st>>>(a); }
     IL_CHECK_LAUNCH("il_act_step_general (tile engine)");
     return IL_OK;

@@ -256,12 +256,6 @@ __global__ __launch_bounds__(256) void k_gmmil_direct(il_batch pol, il_batch exp
   }
   IL_ST_END(IL_ST_GMMIL);
 }
-template <class K>
-static int gmmil_ensure_lds(K fn, size_t bytes) {
-  if (bytes <= 64 * 1024) return IL_OK;
-  const hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  return e == hipSuccess ? IL_OK : il_set_error(IL_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", bytes, hipGetErrorString(e));
-}
 // ---------------------------------------------------------------------------------------------
 // k_gmmil_sx (round 5): the pair arithmetic with the ROW operand in scalar registers. In k_gmmil_direct a thread's 4 x 4 pairs need two ds_read_b128 per
 // feature (its 4 rows, its 4 columns) for 16 packed instructions: with two workgroups per CU the LDS pipe (8 waves x 16 clocks per feature) is as busy as the SIMDs
@@ -804,7 +798,7 @@ static int gmmil_mfma_launch_(const il_batch* pol, const il_batch* exp, int S, i
   const GmmilWs w = gmmil_ws(pol->n, exp->n, D);
   const size_t lds = (size_t)GmfLds<NKQ, COLS>::total * sizeof(float);
   auto kern = k_gmmil_mfma<NKQ, LANES, COLS>;   // (one identifier: the host emulator's launch macro splits its arguments at commas)
-  if (int rc = gmmil_ensure_lds(kern, lds)) return rc;
+  if (int rc = il_ensure_lds(kern, lds)) return rc;
   const int nE = (w.b2p + COLS - 1) / COLS, nX = (w.b1p + COLS - 1) / COLS;
   IL_TRACE("k_gmmil_tile", st);
   kern<<<dim3((w.b1p / GMF_ROWS) * (nE + nX), 1, 1), 256, lds, st>>>(*pol, *exp, S, D, g1, g2, workspace, out_r, out_sim, out_self);
@@ -859,7 +853,7 @@ extern "C" int il_gmmil_reward(const il_batch* pol, const il_batch* exp, int32_t
   }
   if (gmmil_sx_on(S, A, D, state_only, lanes)) {
     const size_t lds = gmmil_sx_lds(D);
-    if (int rc = gmmil_ensure_lds(k_gmmil_sx<0>, lds)) return rc;
+    if (int rc = il_ensure_lds(k_gmmil_sx<0>, lds)) return rc;
     IL_TRACE("k_gmmil_tile", st);   // (the trace name of the pair launch, whichever kernel runs it)
     k_gmmil_sx<0><<<dim3(w.b1p / GSX_ROWS, (w.njt * GT + GSX_COLS - 1) / GSX_COLS, 2), 512, lds, st>>>(*pol, *exp, S, D, g1, g2, workspace, nullptr, 0, out_rewards, out_sim, out_self);
   } else {
@@ -878,7 +872,7 @@ static int gmmil_pop_launch_(const il_gmmil_learner* learners, int n_learners, i
   const int64_t wgs = (int64_t)n_learners * W;
   IL_CHECK_ARG(wgs <= 0x7fffffffll, "il_gmmil_reward_population: %lld workgroups (%d learners x %d) exceed a grid dimension's range", (long long)wgs, n_learners, W);
   auto kern = k_gmmil_mfma_pop<NKQ, LANES, COLS>;   // (one identifier: the host emulator's launch macro splits its arguments at commas)
-  if (int rc = gmmil_ensure_lds(kern, lds)) return rc;
+  if (int rc = il_ensure_lds(kern, lds)) return rc;
   IL_TRACE("k_gmmil_tile_population", st);
   kern<<<dim3(W, n_learners, 1), 256, lds, st>>>(learners, n1, n2, S, D);
   IL_CHECK_LAUNCH("il_gmmil_reward_population");
@@ -930,7 +924,7 @@ extern "C" int il_gmmil_sqdist(const il_batch* a, const il_batch* b, int32_t S, 
   const int lanes = gmmil_lanes(a, b, S, A, state_only);
   if (gmmil_sx_on(S, A, D, state_only, lanes)) {
     const size_t lds = gmmil_sx_lds(D);
-    if (int rc = gmmil_ensure_lds(k_gmmil_sx<1>, lds)) return rc;
+    if (int rc = il_ensure_lds(k_gmmil_sx<1>, lds)) return rc;
     IL_TRACE("k_gmmil_tile", st);
     k_gmmil_sx<1><<<dim3(w.b1p / GSX_ROWS, (w.b2p + GSX_COLS - 1) / GSX_COLS, 1), 512, lds, st>>>(*a, *b, S, D, 0.f, 0.f, workspace, out, 0, nullptr, nullptr, nullptr);
   } else {

@@ -24,6 +24,16 @@ int il_set_error(int code, const char* fmt, ...);
     if (e__ != hipSuccess) return il_set_error(IL_ERR_HIP, "%s: %s", name, hipGetErrorString(e__)); \
   } while (0)
 
+// Dynamic LDS of a launch of kernel `fn`: up to 64 KiB needs nothing, up to the CU's 160 KiB the kernel's opt-in (it attaches to the kernel: every kernel launched with
+// more than 64 KiB asks for its own), more cannot run.
+template <class K>
+inline int il_ensure_lds(K fn, size_t bytes) {
+  if (bytes <= 64 * 1024) return IL_OK;
+  if (bytes > 160 * 1024) return il_set_error(IL_ERR_UNSUPPORTED, "kernel needs %zu bytes of LDS (> 160 KiB per CU)", bytes);
+  const hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  return e == hipSuccess ? IL_OK : il_set_error(IL_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", bytes, hipGetErrorString(e));
+}
+
 // ---------------------------------------------------------------------------------------------
 // MFMA v_mfma_f32_16x16x4_f32: D[16x16] += A[16x4] * B[4x16], exact fp32 (bitwise an fmaf chain).
 //   lane l supplies A[i = l&15][k = l>>4] and B[k = l>>4][j = l&15];
@@ -273,6 +283,16 @@ __device__ __forceinline__ void adam_update(float& p, float g, float& m, float& 
   v = __fadd_rn(__fmul_rn(v, c.beta2), __fmul_rn(__fmul_rn(c.one_m_b2, g), g));   // mul_ + addcmul_ ((value*g)*g)
   const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), c.bc2_sqrt), c.eps);
   p = __fsub_rn(p, __fmul_rn(c.step_size, __fdiv_rn(m, denom)));                  // addcdiv_
+}
+
+// One parameter's end of a gradient-reduce kernel: the summed gradient is stored and, with `apply`, the element takes its AdamW step (the producer launch has ticked `opt`)
+__device__ __forceinline__ void adam_apply_one(float* params, float* grad, const il_adam& opt, int64_t e, float g, int apply) {
+  grad[e] = g;
+  if (!apply) return;
+  const adam_consts ac = load_adam_consts(opt);
+  float pp = params[e], mm = opt.m[e], vv = opt.v[e];
+  adam_update(pp, g, mm, vv, ac);
+  params[e] = pp; opt.m[e] = mm; opt.v[e] = vv;
 }
 
 // ---------------------------------------------------------------------------------------------

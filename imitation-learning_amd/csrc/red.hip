@@ -298,14 +298,6 @@ static int check_red(const il_red* d, const il_batch* b) {
   return IL_OK;
 }
 
-static int red_ensure_lds(const void* fn, size_t bytes) {
-  if (bytes <= 64 * 1024) return IL_OK;
-  if (bytes > 160 * 1024) return il_set_error(IL_ERR_UNSUPPORTED, "kernel needs %zu bytes of LDS (> 160 KiB per CU)", bytes);
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e != hipSuccess) return il_set_error(IL_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", bytes, hipGetErrorString(e));
-  return IL_OK;
-}
-
 // il_red_step (ep == NULL, one step) and il_red_epoch_steps: the same two launches per step
 static int red_steps(const il_red* d, const il_batch* expert, const float* mask_in, const float* mask_h1, const float* mask_h2, uint32_t noise_offset, float* out_loss,
                      uint32_t flags, const il_epoch* ep, int steps, il_stream_t stream_) {
@@ -315,7 +307,7 @@ static int red_steps(const il_red* d, const il_batch* expert, const float* mask_
   const int D = d->state_dim + (d->state_only ? 0 : d->action_dim), nt = ceil_div(expert->n, RT), depth = red_depth(*d);
   const size_t lds = red_lds_floats(D, d->hidden, depth) * sizeof(float);
   const auto grad = depth == 2 ? k_red_grad<2> : k_red_grad<1>;
-  if (int rc = red_ensure_lds((const void*)grad, lds)) return rc;
+  if (int rc = il_ensure_lds(grad, lds)) return rc;
   hipStream_t st = (hipStream_t)stream_;
   const int64_t P = red_layout(D, d->hidden, depth).P;
   const RedMasks mk = {mask_in, {mask_h1, mask_h2}, noise_offset, 1};   // target_estimation_update runs in train mode (train.py:115-123 precede :147)
@@ -348,7 +340,7 @@ extern "C" int il_red_forward(const il_red* d, const il_batch* batch, int32_t tr
   const int D = d->state_dim + (d->state_only ? 0 : d->action_dim);
   const size_t lds = red_lds_floats(D, d->hidden, red_depth(*d)) * sizeof(float);
   const auto eval = red_depth(*d) == 2 ? k_red_eval<2> : k_red_eval<1>;
-  if (int rc = red_ensure_lds((const void*)eval, lds)) return rc;
+  if (int rc = il_ensure_lds(eval, lds)) return rc;
   il_red dd = *d; dd.out_pred = out_pred; dd.out_target = out_target;
   const RedMasks mk = {mask_in, {mask_h1, mask_h2}, noise_offset, training ? 1 : 0};
   { IL_TRACE("k_red_eval", (hipStream_t)stream_); eval<<<ceil_div(batch->n, RT), 256, lds, (hipStream_t)stream_>>>(dd, *batch, mk, out_reward); }
@@ -369,7 +361,7 @@ extern "C" int il_red_reward_population(const il_red* descs_dev, const il_batch*
   const int D = d->state_dim + (d->state_only ? 0 : d->action_dim), depth = red_depth(*d);
   const size_t lds = red_lds_floats(D, d->hidden, depth) * sizeof(float);
   const auto eval = depth == 2 ? k_red_eval_population<2> : k_red_eval_population<1>;
-  if (int rc = red_ensure_lds((const void*)eval, lds)) return rc;   // (the > 64 KiB opt-in attaches to a kernel: k_red_eval's does not cover this one)
+  if (int rc = il_ensure_lds(eval, lds)) return rc;   // (the > 64 KiB opt-in attaches to a kernel: k_red_eval's does not cover this one)
   { IL_TRACE("k_red_eval_population", (hipStream_t)stream_); eval<<<dim3(ceil_div(d->batch, RT), n_learners), 256, lds, (hipStream_t)stream_>>>(*d, descs_dev, batches_dev, rewards_out_dev); }
   IL_CHECK_LAUNCH("il_red_reward_population");
   return IL_OK;

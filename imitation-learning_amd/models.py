@@ -62,14 +62,15 @@ def _mlp_shape(model_cfg, what):
   return hidden, depth, act, not fused
 
 
-def _mlp(in_dim: int, hidden: int, out_dim: int, final_gain: float = 1.0, depth: int = 2, activation: str = 'relu') -> nn.Sequential:
-  """`depth` x (Linear - activation) - Linear with the reference's init (orthogonal, gain calculate_gain(activation) hidden / final_gain last, zero bias; models.py:48-66)."""
+def _mlp(in_dim: int, hidden: int, out_dim: int, final_gain: float = 1.0, depth: int = 2, activation: str = 'relu', wrap=None) -> nn.Sequential:
+  """`depth` x (Linear - activation) - Linear with the reference's init (orthogonal, gain calculate_gain(activation) hidden / final_gain last, zero bias; models.py:48-66).
+  `wrap`: applied to each initialised Linear before the next one is built (spectral norm: its u, v draws come between the layers' own, as in the reference)."""
   dims, layers = [in_dim] + [hidden] * depth + [out_dim], []
   for i in range(depth + 1):
     lin = nn.Linear(dims[i], dims[i + 1])
     nn.init.orthogonal_(lin.weight, gain=nn.init.calculate_gain(activation) if i < depth else final_gain)
     nn.init.constant_(lin.bias, 0)
-    layers.append(lin)
+    layers.append(wrap(lin) if wrap else lin)
     if i < depth:
       layers.append(_ACTIVATION_MODULES[activation]())
   return nn.Sequential(*layers)
@@ -97,6 +98,14 @@ class _FlatModule(nn.Module):
     self.flat = flat
     for p in params:
       p.requires_grad_(False)  # gradients are produced by the HIP kernels, never by autograd
+
+  def _adopt_all(self, device, numel=None):
+    """`_adopt` with the arena in parameters() order, nothing in between (`numel`: what the library's layout says it holds)."""
+    offs, o = [], 0
+    for p in self.parameters():
+      offs.append(o); o += p.numel()
+    assert numel is None or o == int(numel)
+    self._adopt(o, offs, device or default_device())
 
   @property
   def device(self):
@@ -381,225 +390,143 @@ class GAILDiscriminator(_FlatModule):
       return super().__new__(DeepGAILDiscriminator)     # depth 2 and / or tanh: the general kernels (gail_deep.hip)
     return super().__new__(cls)
 
-  def __init__(self, state_size: int, action_size: int, imitation_cfg, discount: float, device=None):
-    super().__init__()
+  # What the host layer (training.py) asks a discriminator for: its descriptor builder there, its step / reward entry points of the library, and whether UpdatePlan's
+  # two-stream schedule of the fused depth-1 kernels serves it (the other variants run their per-function entry points inside the plan)
+  descriptor, step_entry, reward_entry, fused = 'disc_descriptor', 'il_gail_disc_step', 'il_gail_reward', True
+
+  def _init_config(self, state_size: int, action_size: int, imitation_cfg, discount: float):
+    nn.Module.__init__(self)
     model_cfg = imitation_cfg.discriminator
     self.discount, self.state_only = discount, bool(imitation_cfg.state_only)
-    self.reward_shaping, self.subtract_log_policy, self.reward_function = model_cfg.reward_shaping, model_cfg.subtract_log_policy, model_cfg.reward_function
+    self.reward_shaping, self.subtract_log_policy, self.reward_function = bool(model_cfg.reward_shaping), model_cfg.subtract_log_policy, model_cfg.reward_function
     self.spectral_norm = bool(imitation_cfg.spectral_norm)
-    if self.reward_shaping or model_cfg.depth != 1 or model_cfg.activation != 'relu':
+    self.depth, self.activation = int(model_cfg.depth), str(model_cfg.activation)
+    self.state_size, self.action_size, self.hidden = state_size, action_size, int(model_cfg.hidden_size)
+    self.in_dim = state_size if self.state_only else state_size + action_size
+    return parametrizations.spectral_norm if self.spectral_norm else None   # `_mlp`'s per-Linear wrapper
+
+  def _own_sn_buffers(self, mods, numel):
+    """`self.sn` = [u | v] of each spectrally normalised Linear of `mods`, in order: the values torch initialised, with the modules' buffers re-pointed at the slices.
+    The parametrization modules stay only for that initialisation and for the state_dict keys; the kernels own u, v."""
+    self.sn, o = torch.zeros(int(numel), device=self.flat.device), 0
+    if self.spectral_norm:
+      with torch.no_grad():
+        for mod in (m.parametrizations.weight[0] for m in mods):
+          for name in ('_u', '_v'):
+            view = self.sn[o:o + mod._buffers[name].numel()]
+            view.copy_(mod._buffers[name]); mod._buffers[name] = view; o += view.numel()
+      assert o == self.sn.numel()
+    self.eval()
+
+  def __init__(self, state_size: int, action_size: int, imitation_cfg, discount: float, device=None):
+    self._init_config(state_size, action_size, imitation_cfg, discount)
+    if self.reward_shaping or self.depth != 1 or self.activation != 'relu':
       raise NotImplementedError('GAILDiscriminator: the HIP path implements depth=1, activation=relu without reward shaping '
                                 '(the closed-form gradient-penalty backward assumes it); no torch fallback on this path')
-    self.state_size, self.action_size, self.hidden = state_size, action_size, model_cfg.hidden_size
-    self.in_dim = state_size if self.state_only else state_size + action_size
-    l1, l2 = nn.Linear(self.in_dim, self.hidden), nn.Linear(self.hidden, 1)
+    l1, l2 = nn.Linear(self.in_dim, self.hidden), nn.Linear(self.hidden, 1)   # (both built before either is initialised: not `_mlp`'s order, and the order fixes the RNG stream)
     nn.init.orthogonal_(l1.weight, gain=sqrt(2.0)); nn.init.constant_(l1.bias, 0)
     if self.spectral_norm: l1 = parametrizations.spectral_norm(l1)
     nn.init.orthogonal_(l2.weight, gain=1.0); nn.init.constant_(l2.bias, 0)
     if self.spectral_norm: l2 = parametrizations.spectral_norm(l2)
     self.g = nn.Sequential(l1, nn.ReLU(), l2)
-    offs, o = [], 0
-    for p in self.parameters():
-      offs.append(o); o += p.numel()
-    dev = device or default_device()
-    self._adopt(o, offs, dev)
-    H, D = self.hidden, self.in_dim
-    self.sn = torch.zeros(2 * H + D + 1, device=dev)  # u1[H] | v1[D] | u2[1] | v2[H]
-    if self.spectral_norm:
-      with torch.no_grad():
-        for mod, (ou, nu, ov, nv) in ((self.g[0].parametrizations.weight[0], (0, H, H, D)), (self.g[2].parametrizations.weight[0], (H + D, 1, H + D + 1, H))):
-          u, v = self.sn[ou:ou + nu], self.sn[ov:ov + nv]
-          u.copy_(mod._u); v.copy_(mod._v)
-          mod._buffers['_u'], mod._buffers['_v'] = u, v
-    self.eval()
+    self._adopt_all(device)
+    self._own_sn_buffers((self.g[0], self.g[2]), 2 * self.hidden + self.in_dim + 1)  # u1[H] | v1[D] | u2[1] | v2[H]
 
   def views(self):
     H, D = self.hidden, self.in_dim
     return dict(u1=self.sn[:H], v1=self.sn[H:H + D], u2=self.sn[H + D:H + D + 1], v2=self.sn[H + D + 1:])
 
+  def _reward_inputs(self, state, action, next_state, terminal):
+    return state, action
+
   def predict_reward(self, state: Tensor, action: Tensor, next_state=None, terminal=None, log_policy=None) -> Tensor:
-    from .training import gail_predict_reward
+    from .training import _predict_reward
     assert (log_policy is not None) == bool(self.subtract_log_policy), 'pass log_policy exactly when subtract_log_policy is set (make_gail_input does)'
-    return gail_predict_reward(self, state, action, log_policy=log_policy)
+    return _predict_reward(self, *self._reward_inputs(state, action, next_state, terminal), log_policy=log_policy)
 
   def forward(self, state: Tensor, action: Tensor, next_state=None, terminal=None, log_policy=None) -> Tensor:
-    from .training import gail_predict_reward
-    return gail_predict_reward(self, state, action, want_logits=True, log_policy=log_policy)[1]
+    from .training import _predict_reward
+    return _predict_reward(self, *self._reward_inputs(state, action, next_state, terminal), log_policy=log_policy, want_logits=True)[1]
 
 
-class ShapedGAILDiscriminator(GAILDiscriminator):
+class _ShapedDiscriminator(GAILDiscriminator):
+  """What the two reward-shaping discriminators share: f = g(s, a) + (1 - terminal)(discount h(s') - h(s)) with g = Linear(Dg, 1) under the default nn.Linear init, like
+  the reference (models.py:158), built before the potential h; the next state and the terminal flag are inputs of every evaluation."""
+  descriptor, fused = 'shaped_descriptor', False
+
+  def _init_shaped(self, state_size, action_size, imitation_cfg, discount):
+    wrap = self._init_config(state_size, action_size, imitation_cfg, discount)
+    self.reward_shaping = True
+    return wrap
+
+  def _build(self, wrap, device, numel, sn_numel):
+    self.g = (wrap or (lambda layer: layer))(nn.Linear(self.in_dim, 1))
+    self.h = _mlp(self.state_size, self.hidden, 1, depth=self.depth, activation=self.activation, wrap=wrap)   # models.py:49-70 `_create_fcnn`
+    self._adopt_all(device, numel)
+    self._own_sn_buffers([self.g] + [self.h[2 * l] for l in range(self.depth + 1)], sn_numel)
+
+  def _reward_inputs(self, state, action, next_state, terminal):
+    assert next_state is not None and terminal is not None, 'reward shaping: pass next_state and terminal (make_gail_input does)'
+    return state, action, next_state, terminal
+
+
+class ShapedGAILDiscriminator(_ShapedDiscriminator):
   """GAIL discriminator with reward shaping (reference models.py:152-180, reward_shaping=True): g = Linear(Dg, 1) is the reward, h = Linear(S, H)-ReLU-
   Linear(H, 1) the potential, f = g(s, a) + (1 - terminal)(discount h(s') - h(s)); every weight optionally under spectral norm.  Created through
   `GAILDiscriminator(...)` when `imitation.discriminator.reward_shaping` is set.  Flat arena = parameters() order, buffers `self.sn` =
   ug[1] | vg[Dg] | u1[H] | v1[S] | u2[1] | v2[H]; same RNG consumption at construction as the reference (default-initialised g, orthogonal h)."""
+  step_entry, reward_entry = 'il_gail_shaped_step', 'il_gail_shaped_reward'
 
   def __init__(self, state_size: int, action_size: int, imitation_cfg, discount: float, device=None):
-    nn.Module.__init__(self)
-    model_cfg = imitation_cfg.discriminator
-    self.discount, self.state_only = discount, bool(imitation_cfg.state_only)
-    self.reward_shaping, self.subtract_log_policy, self.reward_function = True, model_cfg.subtract_log_policy, model_cfg.reward_function
-    self.spectral_norm = bool(imitation_cfg.spectral_norm)
-    if model_cfg.depth != 1 or model_cfg.activation != 'relu' or model_cfg.hidden_size > 256:   # (other depths / activations are ShapedDeepGAILDiscriminator's)
+    wrap = self._init_shaped(state_size, action_size, imitation_cfg, discount)
+    if self.depth != 1 or self.activation != 'relu' or self.hidden > 256:   # (other depths / activations are ShapedDeepGAILDiscriminator's)
       raise NotImplementedError('GAILDiscriminator (reward shaping, depth-1 ReLU potential): hidden_size <= 256; no torch fallback')
-    self.state_size, self.action_size, self.hidden = state_size, action_size, model_cfg.hidden_size
-    self.in_dim = state_size if self.state_only else state_size + action_size
-    sn = parametrizations.spectral_norm if self.spectral_norm else (lambda layer: layer)
-    self.g = sn(nn.Linear(self.in_dim, 1))   # default nn.Linear init, like the reference (models.py:158)
-    l1 = nn.Linear(state_size, self.hidden); nn.init.orthogonal_(l1.weight, gain=sqrt(2.0)); nn.init.constant_(l1.bias, 0); l1 = sn(l1)
-    l2 = nn.Linear(self.hidden, 1); nn.init.orthogonal_(l2.weight, gain=1.0); nn.init.constant_(l2.bias, 0); l2 = sn(l2)
-    self.h = nn.Sequential(l1, nn.ReLU(), l2)
-    offs, o = [], 0
-    for p in self.parameters():
-      offs.append(o); o += p.numel()
-    assert o == int(_lib.lib().il_disc_shaped_numel(state_size, action_size, self.hidden, int(self.state_only)))
-    dev = device or default_device()
-    self._adopt(o, offs, dev)
     H, D, S = self.hidden, self.in_dim, state_size
-    self.sn = torch.zeros(2 + D + 2 * H + S, device=dev)
+    self._build(wrap, device, _lib.lib().il_disc_shaped_numel(state_size, action_size, H, int(self.state_only)), 2 + D + 2 * H + S)
     self._sn_slices = dict(ug=(0, 1), vg=(1, D), u1=(1 + D, H), v1=(1 + D + H, S), u2=(1 + D + H + S, 1), v2=(2 + D + H + S, H))
-    if self.spectral_norm:
-      with torch.no_grad():
-        for mod, (ku, kv) in ((self.g.parametrizations.weight[0], ('ug', 'vg')), (self.h[0].parametrizations.weight[0], ('u1', 'v1')), (self.h[2].parametrizations.weight[0], ('u2', 'v2'))):
-          u, v = self.views()[ku], self.views()[kv]
-          u.copy_(mod._u); v.copy_(mod._v)
-          mod._buffers['_u'], mod._buffers['_v'] = u, v
-    self.eval()
 
   def views(self):
     return {k: self.sn[o:o + n] for k, (o, n) in self._sn_slices.items()}
 
-  def predict_reward(self, state: Tensor, action: Tensor, next_state=None, terminal=None, log_policy=None) -> Tensor:
-    from .training import shaped_predict_reward
-    assert next_state is not None and terminal is not None, 'reward shaping: pass next_state and terminal (make_gail_input does)'
-    assert (log_policy is not None) == bool(self.subtract_log_policy)
-    return shaped_predict_reward(self, state, action, next_state, terminal, log_policy=log_policy)
 
-  def forward(self, state: Tensor, action: Tensor, next_state=None, terminal=None, log_policy=None) -> Tensor:
-    from .training import shaped_predict_reward
-    return shaped_predict_reward(self, state, action, next_state, terminal, log_policy=log_policy, want_logits=True)[1]
-
-
-class ShapedDeepGAILDiscriminator(GAILDiscriminator):
+class ShapedDeepGAILDiscriminator(_ShapedDiscriminator):
   """GAIL discriminator with reward shaping whose potential is any `_create_fcnn` shape (reference models.py:152-180 with reward_shaping=True and
   discriminator.depth in {1, 2}, activation in {relu, tanh}): g = Linear(Dg, 1), h = [Linear - act] x depth - Linear(H, 1) on the state, every Linear optionally under
   spectral norm. Created through `GAILDiscriminator(...)` when the potential is not the depth-1 ReLU shape ShapedGAILDiscriminator serves. Flat arena = parameters()
   order; `self.sn` = ug[1] | vg[Dg] | per layer of h [u | v]; same module order, state_dict keys and RNG consumption at construction as the reference."""
+  step_entry, reward_entry = 'il_gail_shaped_deep_step', 'il_gail_shaped_deep_reward'
 
   def __init__(self, state_size: int, action_size: int, imitation_cfg, discount: float, device=None):
-    nn.Module.__init__(self)
-    model_cfg = imitation_cfg.discriminator
-    self.discount, self.state_only = discount, bool(imitation_cfg.state_only)
-    self.reward_shaping, self.subtract_log_policy, self.reward_function = True, model_cfg.subtract_log_policy, model_cfg.reward_function
-    self.spectral_norm = bool(imitation_cfg.spectral_norm)
-    self.depth, self.activation = int(model_cfg.depth), str(model_cfg.activation)
-    self.state_size, self.action_size, self.hidden = state_size, action_size, int(model_cfg.hidden_size)
-    self.in_dim = state_size if self.state_only else state_size + action_size
+    wrap = self._init_shaped(state_size, action_size, imitation_cfg, discount)
     if self.depth not in (1, 2) or self.activation not in ('relu', 'tanh') or self.hidden > 128 or self.hidden < 2 or state_size > 128 or self.in_dim > 256:
       raise NotImplementedError(f'GAILDiscriminator (reward shaping): the HIP path implements a potential of depth 1-2 with relu / tanh, hidden_size <= 128, state <= 128 '
                                 f'(got depth={self.depth}, activation={self.activation}, hidden_size={self.hidden}, state={state_size}); no torch fallback')
-    L = _lib.lib()
-    lds = int(L.il_disc_shaped_deep_lds_bytes(state_size, action_size, self.hidden, self.depth, int(self.state_only)))
+    L, shape = _lib.lib(), (state_size, action_size, self.hidden, self.depth, int(self.state_only))
+    lds = int(L.il_disc_shaped_deep_lds_bytes(*shape))
     if lds > 160 * 1024:
       raise NotImplementedError(f'GAILDiscriminator (reward shaping): state {state_size} x hidden {self.hidden} x depth {self.depth} needs {lds} bytes of LDS per workgroup (> 160 KiB)')
-    sn = parametrizations.spectral_norm if self.spectral_norm else (lambda layer: layer)
-    self.g = sn(nn.Linear(self.in_dim, 1))   # default nn.Linear init, like the reference (models.py:158)
-    act = nn.ReLU if self.activation == 'relu' else nn.Tanh
-    dims, layers = [state_size] + [self.hidden] * self.depth, []
-    for a, b in zip(dims[:-1], dims[1:]):   # models.py:49-70 `_create_fcnn`
-      lin = nn.Linear(a, b)
-      nn.init.orthogonal_(lin.weight, gain=nn.init.calculate_gain(self.activation)); nn.init.constant_(lin.bias, 0)
-      layers += [sn(lin), act()]
-    last = nn.Linear(self.hidden, 1)
-    nn.init.orthogonal_(last.weight, gain=1.0); nn.init.constant_(last.bias, 0)
-    self.h = nn.Sequential(*layers, sn(last))
-    offs, o = [], 0
-    for p in self.parameters():
-      offs.append(o); o += p.numel()
-    assert o == int(L.il_disc_shaped_deep_numel(state_size, action_size, self.hidden, self.depth, int(self.state_only)))
-    dev = device or default_device()
-    self._adopt(o, offs, dev)
-    self.sn = torch.zeros(int(L.il_disc_shaped_deep_sn_numel(state_size, action_size, self.hidden, self.depth, int(self.state_only))), device=dev)
-    if self.spectral_norm:
-      mods, o = [self.g.parametrizations.weight[0]] + [self.h[2 * l].parametrizations.weight[0] for l in range(self.depth + 1)], 0
-      with torch.no_grad():
-        for mod in mods:
-          nu, nv = mod._u.numel(), mod._v.numel()
-          u, v = self.sn[o:o + nu], self.sn[o + nu:o + nu + nv]
-          u.copy_(mod._u); v.copy_(mod._v)
-          mod._buffers['_u'], mod._buffers['_v'] = u, v
-          o += nu + nv
-      assert o == self.sn.numel()
-    self.eval()
-
-  def predict_reward(self, state: Tensor, action: Tensor, next_state=None, terminal=None, log_policy=None) -> Tensor:
-    from .training import shaped_predict_reward
-    assert next_state is not None and terminal is not None, 'reward shaping: pass next_state and terminal (make_gail_input does)'
-    assert (log_policy is not None) == bool(self.subtract_log_policy)
-    return shaped_predict_reward(self, state, action, next_state, terminal, log_policy=log_policy)
-
-  def forward(self, state: Tensor, action: Tensor, next_state=None, terminal=None, log_policy=None) -> Tensor:
-    from .training import shaped_predict_reward
-    return shaped_predict_reward(self, state, action, next_state, terminal, log_policy=log_policy, want_logits=True)[1]
+    self._build(wrap, device, L.il_disc_shaped_deep_numel(*shape), L.il_disc_shaped_deep_sn_numel(*shape))
 
 
 class DeepGAILDiscriminator(GAILDiscriminator):
   """GAIL discriminator of any `_create_fcnn` shape without reward shaping (reference models.py:152-162): depth 1-2, relu / tanh, every Linear optionally
   under spectral norm.  Created through `GAILDiscriminator(...)` for configurations other than depth 1 / relu (which keep the fast path).  Flat arena =
   parameters() order, `self.sn` = per layer [u | v]; same module order, state_dict keys and RNG consumption at construction as the reference."""
+  descriptor, step_entry, reward_entry, fused = 'deep_descriptor', 'il_gail_deep_step', 'il_gail_deep_reward', False
 
   def __init__(self, state_size: int, action_size: int, imitation_cfg, discount: float, device=None):
-    nn.Module.__init__(self)
-    model_cfg = imitation_cfg.discriminator
-    self.discount, self.state_only = discount, bool(imitation_cfg.state_only)
-    self.reward_shaping, self.subtract_log_policy, self.reward_function = False, model_cfg.subtract_log_policy, model_cfg.reward_function
-    self.spectral_norm = bool(imitation_cfg.spectral_norm)
-    self.depth, self.activation = int(model_cfg.depth), str(model_cfg.activation)
-    self.state_size, self.action_size, self.hidden = state_size, action_size, int(model_cfg.hidden_size)
-    self.in_dim = state_size if self.state_only else state_size + action_size
+    wrap = self._init_config(state_size, action_size, imitation_cfg, discount)
+    self.reward_shaping = False
     if self.depth not in (1, 2) or self.activation not in ('relu', 'tanh') or self.hidden > 128 or self.in_dim > 128:
       raise NotImplementedError(f'GAILDiscriminator: the HIP path implements depth 1-2 with relu / tanh, hidden_size <= 128, input <= 128 '
                                 f'(got depth={self.depth}, activation={self.activation}, hidden_size={self.hidden}); no torch fallback')
-    lds = int(_lib.lib().il_disc_deep_lds_bytes(self.in_dim, self.hidden, self.depth))
+    L, shape = _lib.lib(), (self.in_dim, self.hidden, self.depth)
+    lds = int(L.il_disc_deep_lds_bytes(*shape))
     if lds > 160 * 1024:
       raise NotImplementedError(f'GAILDiscriminator: input {self.in_dim} x hidden {self.hidden} x depth {self.depth} needs {lds} bytes of LDS per workgroup (> 160 KiB)')
-    sn = parametrizations.spectral_norm if self.spectral_norm else (lambda layer: layer)
-    act = nn.ReLU if self.activation == 'relu' else nn.Tanh
-    dims, layers = [self.in_dim] + [self.hidden] * self.depth, []
-    for a, b in zip(dims[:-1], dims[1:]):   # models.py:49-70 `_create_fcnn`
-      lin = nn.Linear(a, b)
-      nn.init.orthogonal_(lin.weight, gain=nn.init.calculate_gain(self.activation)); nn.init.constant_(lin.bias, 0)
-      layers += [sn(lin), act()]
-    last = nn.Linear(self.hidden, 1)
-    nn.init.orthogonal_(last.weight, gain=1.0); nn.init.constant_(last.bias, 0)
-    self.g = nn.Sequential(*layers, sn(last))
-    offs, o = [], 0
-    for p in self.parameters():
-      offs.append(o); o += p.numel()
-    assert o == int(_lib.lib().il_disc_deep_numel(self.in_dim, self.hidden, self.depth))
-    dev = device or default_device()
-    self._adopt(o, offs, dev)
-    self.sn = torch.zeros(int(_lib.lib().il_disc_deep_sn_numel(self.in_dim, self.hidden, self.depth)), device=dev)
-    self._sn_slices, o = [], 0
-    for l in range(self.depth + 1):
-      n_out, n_in = (1 if l == self.depth else self.hidden), (self.in_dim if l == 0 else self.hidden)
-      self._sn_slices.append(((o, n_out), (o + n_out, n_in))); o += n_out + n_in
-    if self.spectral_norm:
-      with torch.no_grad():
-        for l, ((ou, nu), (ov, nv)) in enumerate(self._sn_slices):
-          mod = self.g[2 * l].parametrizations.weight[0]
-          u, v = self.sn[ou:ou + nu], self.sn[ov:ov + nv]
-          u.copy_(mod._u); v.copy_(mod._v)
-          mod._buffers['_u'], mod._buffers['_v'] = u, v
-    self.eval()
-
-  def predict_reward(self, state: Tensor, action: Tensor, next_state=None, terminal=None, log_policy=None) -> Tensor:
-    from .training import deep_predict_reward
-    assert (log_policy is not None) == bool(self.subtract_log_policy)
-    return deep_predict_reward(self, state, action, log_policy=log_policy)
-
-  def forward(self, state: Tensor, action: Tensor, next_state=None, terminal=None, log_policy=None) -> Tensor:
-    from .training import deep_predict_reward
-    return deep_predict_reward(self, state, action, log_policy=log_policy, want_logits=True)[1]
+    self.g = _mlp(self.in_dim, self.hidden, 1, depth=self.depth, activation=self.activation, wrap=wrap)   # models.py:49-70 `_create_fcnn`
+    self._adopt_all(device, L.il_disc_deep_numel(*shape))
+    self._own_sn_buffers([self.g[2 * l] for l in range(self.depth + 1)], L.il_disc_deep_sn_numel(*shape))
 
 
 class GMMILDiscriminator(nn.Module):

@@ -155,9 +155,9 @@ def target_estimation_update(discriminator, expert_transition: Dict[str, Tensor]
 
 
 # ----------------------------------------------------------------------------------------------- GAIL
-def disc_descriptor(disc: GAILDiscriminator, batch_size: int, opt: AdamW, imitation_cfg=None, grad_penalty: float = 0.0, entropy_bonus: float = 0.0, tag=None,
-                    seed_offset: int = 0) -> _lib.Disc:
-  dev = disc.flat.device
+def _fill_disc(d, disc, batch_size: int, opt, imitation_cfg, ws: Tensor, grad_penalty: float = 0.0, entropy_bonus: float = 0.0, tag=None, seed_offset: int = 0):
+  """The fields the four discriminator descriptors (il_disc, il_disc_shaped, il_disc_deep, il_disc_shaped_deep) share, under the same names: shape, flags, loss, optimiser,
+  workspace and the noise stream - the learner's ONE update counter (advanced by the actor step of sac_update): fresh gradient-penalty / Mixup draws per update."""
   loss_function, prior, margin = 'BCE', 0.0, float('inf')
   if imitation_cfg is not None:
     loss_function, prior = imitation_cfg.loss_function, float(_cfg_value(imitation_cfg, 'pos_class_prior', 0.0) or 0.0)
@@ -165,155 +165,89 @@ def disc_descriptor(disc: GAILDiscriminator, batch_size: int, opt: AdamW, imitat
       raise ValueError(f'adversarial_imitation_update: unknown loss_function={loss_function}')
     margin = float(_cfg_value(imitation_cfg, 'nonnegative_margin', float('inf')))
     grad_penalty, entropy_bonus = float(imitation_cfg.grad_penalty), float(imitation_cfg.entropy_bonus)
-  floats = int(_lib.lib().il_disc_workspace_floats(disc.in_dim, disc.hidden, batch_size))
-  ws = _workspace('disc', floats, dev, tag)
-  v = disc.views()
-  d = _lib.Disc()
-  d.state_dim, d.action_dim, d.hidden, d.batch = disc.state_size, disc.action_size, disc.hidden, batch_size
-  d.spectral_norm, d.state_only, d.reward_function = int(disc.spectral_norm), int(disc.state_only), REWARD_FUNCTIONS[disc.reward_function]
-  d.params, d.u1, d.v1, d.u2, d.v2 = disc.flat.data_ptr(), v['u1'].data_ptr(), v['v1'].data_ptr(), v['u2'].data_ptr(), v['v2'].data_ptr()
-  if opt is not None:
-    d.grad, d.opt = opt.grad.data_ptr(), opt.desc()
-  else:
-    d.grad = ws.data_ptr()  # reward only: never written
-  d.grad_penalty, d.entropy_bonus = grad_penalty, entropy_bonus
-  d.workspace, d.workspace_floats = ws.data_ptr(), ws.numel()
-  d._ws = ws   # the descriptor holds a raw pointer: keep the arena alive with it (a later, larger request under the same key replaces the cached tensor)
-  d.noise_seed, d.noise_counter = (_noise_seed() + seed_offset) & (2**64 - 1), _noise_counter(dev, tag).data_ptr()
-  d.loss_function, d.pos_class_prior = LOSS_FUNCTIONS[loss_function], prior
-  if loss_function == 'PUGAIL' and margin != float('inf'):   # training.py:102: torch.clamp(..., min=-nonnegative_margin) on the batch-wide value (a value pass precedes the gradients)
-    d.pu_clamped, d.nonnegative_margin = 1, margin
-  return d
-
-
-def _shaped_general(disc) -> bool:
-  return type(disc).__name__ == 'ShapedDeepGAILDiscriminator'   # a depth-2 and / or tanh potential: gail_shaped_deep.hip, same arguments
-
-
-def shaped_descriptor(disc, batch_size: int, opt, imitation_cfg=None):
-  """il_disc_shaped (depth-1 ReLU potential, gail_shaped.hip) or il_disc_shaped_deep (any potential, gail_shaped_deep.hip) for a reward-shaping discriminator."""
-  dev = disc.flat.device
-  loss_function, prior, grad_penalty, entropy_bonus, margin = 'BCE', 0.0, 0.0, 0.0, float('inf')
-  if imitation_cfg is not None:
-    loss_function, prior = imitation_cfg.loss_function, float(_cfg_value(imitation_cfg, 'pos_class_prior', 0.0) or 0.0)
-    if loss_function not in LOSS_FUNCTIONS:
-      raise ValueError(f'adversarial_imitation_update: unknown loss_function={loss_function}')
-    margin = float(_cfg_value(imitation_cfg, 'nonnegative_margin', float('inf')))
-    grad_penalty, entropy_bonus = float(imitation_cfg.grad_penalty), float(imitation_cfg.entropy_bonus)
-  if _shaped_general(disc):
-    ws = _workspace('disc_shaped', int(_lib.lib().il_disc_shaped_deep_workspace_floats(disc.state_size, disc.action_size, disc.hidden, disc.depth, batch_size, int(disc.state_only))), dev)
-    d = _lib.DiscShapedDeep()
-    d.depth, d.activation, d.sn = disc.depth, int(disc.activation == 'tanh'), disc.sn.data_ptr()
-  else:
-    ws = _workspace('disc_shaped', int(_lib.lib().il_disc_shaped_workspace_floats(disc.state_size, disc.action_size, disc.hidden, batch_size, int(disc.state_only))), dev)
-    v = disc.views()
-    d = _lib.DiscShaped()
-    d.ug, d.vg, d.u1, d.v1, d.u2, d.v2 = (v[k].data_ptr() for k in ('ug', 'vg', 'u1', 'v1', 'u2', 'v2'))
   d.state_dim, d.action_dim, d.hidden, d.batch = disc.state_size, disc.action_size, disc.hidden, batch_size
   d.spectral_norm, d.state_only, d.reward_function, d.loss_function = int(disc.spectral_norm), int(disc.state_only), REWARD_FUNCTIONS[disc.reward_function], LOSS_FUNCTIONS[loss_function]
   d.params = disc.flat.data_ptr()
   if opt is not None:
     d.grad, d.opt = opt.grad.data_ptr(), opt.desc()
-  d.grad_penalty, d.entropy_bonus, d.pos_class_prior, d.discount = grad_penalty, entropy_bonus, prior, float(disc.discount)
+  d.grad_penalty, d.entropy_bonus, d.pos_class_prior = grad_penalty, entropy_bonus, prior
   d.workspace, d.workspace_floats = ws.data_ptr(), ws.numel()
   d._ws = ws   # the descriptor holds a raw pointer: keep the arena alive with it (a later, larger request under the same key replaces the cached tensor)
-  d.noise_seed, d.noise_counter = _noise_seed() & (2**64 - 1), _noise_counter(dev, None).data_ptr()   # the learner's ONE update counter (advanced by the actor step of sac_update): fresh GP / Mixup draws per update
-  if loss_function == 'PUGAIL' and margin != float('inf'):   # training.py:102, as in disc_descriptor
+  d.noise_seed, d.noise_counter = (_noise_seed() + seed_offset) & (2**64 - 1), _noise_counter(disc.flat.device, tag).data_ptr()
+  if loss_function == 'PUGAIL' and margin != float('inf'):   # training.py:102: torch.clamp(..., min=-nonnegative_margin) on the batch-wide value (a value pass precedes the gradients)
     d.pu_clamped, d.nonnegative_margin = 1, margin
   return d
+
+
+def disc_descriptor(disc: GAILDiscriminator, batch_size: int, opt: AdamW, imitation_cfg=None, grad_penalty: float = 0.0, entropy_bonus: float = 0.0, tag=None,
+                    seed_offset: int = 0) -> _lib.Disc:
+  """il_disc for the depth-1 ReLU discriminator (gail.hip); `tag` / `seed_offset`: a learner of a population (its own workspace, update counter and noise key)."""
+  ws = _workspace('disc', int(_lib.lib().il_disc_workspace_floats(disc.in_dim, disc.hidden, batch_size)), disc.flat.device, tag)
+  v = disc.views()
+  d = _fill_disc(_lib.Disc(), disc, batch_size, opt, imitation_cfg, ws, grad_penalty, entropy_bonus, tag, seed_offset)
+  d.u1, d.v1, d.u2, d.v2 = v['u1'].data_ptr(), v['v1'].data_ptr(), v['u2'].data_ptr(), v['v2'].data_ptr()
+  if opt is None:
+    d.grad = ws.data_ptr()  # reward only: never written
+  return d
+
+
+def shaped_descriptor(disc, batch_size: int, opt, imitation_cfg=None):
+  """il_disc_shaped (depth-1 ReLU potential, gail_shaped.hip) or il_disc_shaped_deep (any potential, gail_shaped_deep.hip) for a reward-shaping discriminator."""
+  L, dev = _lib.lib(), disc.flat.device
+  if disc.step_entry == 'il_gail_shaped_deep_step':
+    ws = _workspace('disc_shaped', int(L.il_disc_shaped_deep_workspace_floats(disc.state_size, disc.action_size, disc.hidden, disc.depth, batch_size, int(disc.state_only))), dev)
+    d = _lib.DiscShapedDeep()
+    d.depth, d.activation, d.sn = disc.depth, int(disc.activation == 'tanh'), disc.sn.data_ptr()
+  else:
+    ws = _workspace('disc_shaped', int(L.il_disc_shaped_workspace_floats(disc.state_size, disc.action_size, disc.hidden, batch_size, int(disc.state_only))), dev)
+    v = disc.views()
+    d = _lib.DiscShaped()
+    d.ug, d.vg, d.u1, d.v1, d.u2, d.v2 = (v[k].data_ptr() for k in ('ug', 'vg', 'u1', 'v1', 'u2', 'v2'))
+  d.discount = float(disc.discount)
+  return _fill_disc(d, disc, batch_size, opt, imitation_cfg, ws)
 
 
 def deep_descriptor(disc, batch_size: int, opt, imitation_cfg=None) -> _lib.DiscDeep:
   """il_disc_deep for a DeepGAILDiscriminator (depth 1-2, relu / tanh; gail_deep.hip)."""
-  dev = disc.flat.device
-  loss_function, prior, grad_penalty, entropy_bonus, margin = 'BCE', 0.0, 0.0, 0.0, float('inf')
-  if imitation_cfg is not None:
-    loss_function, prior = imitation_cfg.loss_function, float(_cfg_value(imitation_cfg, 'pos_class_prior', 0.0) or 0.0)
-    if loss_function not in LOSS_FUNCTIONS:
-      raise ValueError(f'adversarial_imitation_update: unknown loss_function={loss_function}')
-    margin = float(_cfg_value(imitation_cfg, 'nonnegative_margin', float('inf')))
-    grad_penalty, entropy_bonus = float(imitation_cfg.grad_penalty), float(imitation_cfg.entropy_bonus)
-  L = _lib.lib()
-  ws = _workspace('disc_deep', int(L.il_disc_deep_workspace_floats(disc.in_dim, disc.hidden, disc.depth, batch_size)), dev)
+  ws = _workspace('disc_deep', int(_lib.lib().il_disc_deep_workspace_floats(disc.in_dim, disc.hidden, disc.depth, batch_size)), disc.flat.device)
   d = _lib.DiscDeep()
-  d.state_dim, d.action_dim, d.hidden, d.batch = disc.state_size, disc.action_size, disc.hidden, batch_size
-  d.spectral_norm, d.state_only, d.reward_function, d.loss_function = int(disc.spectral_norm), int(disc.state_only), REWARD_FUNCTIONS[disc.reward_function], LOSS_FUNCTIONS[loss_function]
-  d.depth, d.activation = disc.depth, int(disc.activation == 'tanh')
-  d.params, d.sn = disc.flat.data_ptr(), disc.sn.data_ptr()
-  if opt is not None:
-    d.grad, d.opt = opt.grad.data_ptr(), opt.desc()
-  d.grad_penalty, d.entropy_bonus, d.pos_class_prior = grad_penalty, entropy_bonus, prior
-  d.workspace, d.workspace_floats = ws.data_ptr(), ws.numel()
-  d._ws = ws   # the descriptor holds a raw pointer: keep the arena alive with it (a later, larger request under the same key replaces the cached tensor)
-  d.noise_seed, d.noise_counter = _noise_seed() & (2**64 - 1), _noise_counter(dev, None).data_ptr()   # the learner's ONE update counter (advanced by the actor step of sac_update): fresh GP / Mixup draws per update
-  if loss_function == 'PUGAIL' and margin != float('inf'):   # training.py:102, as in disc_descriptor
-    d.pu_clamped, d.nonnegative_margin = 1, margin
-  return d
+  d.depth, d.activation, d.sn = disc.depth, int(disc.activation == 'tanh'), disc.sn.data_ptr()
+  return _fill_disc(d, disc, batch_size, opt, imitation_cfg, ws)
 
 
-def deep_predict_reward(disc, state: Tensor, action: Tensor, log_policy: Optional[Tensor] = None, want_logits: bool = False):
+def _predict_reward(disc, state: Tensor, action: Tensor, next_state: Optional[Tensor] = None, terminal: Optional[Tensor] = None, log_policy: Optional[Tensor] = None,
+                    want_logits: bool = False):
+  """models.py:173-180 in eval mode through the discriminator's own reward entry point; next_state / terminal: the shaping term's inputs, unread otherwise."""
   dev = disc.flat.device
-  state, action = _f32(state, dev), _f32(action, dev)
+  state, action = state.to(dev, torch.float32), action.to(dev, torch.float32)   # (no copy of what already is: the kernels read rows at their stride)
   n = state.size(0)
-  d = deep_descriptor(disc, n, None)
+  d = globals()[disc.descriptor](disc, n, None)
   dummy = torch.zeros(n, device=dev)
-  b = batch_desc(dict(states=state, actions=action, rewards=dummy, next_states=state, terminals=dummy, weights=dummy, absorbing=dummy))
-  out, logits = torch.empty(n, device=dev), (torch.empty(n, device=dev) if want_logits else None)
-  off = _f32(log_policy, dev)
-  _lib.check(_lib.lib().il_gail_deep_reward(C.byref(d), C.byref(b), _lib.ptr(out), _lib.ptr(logits), _lib.ptr(off), _lib.stream_ptr()))
+  terminal = dummy if terminal is None else terminal.to(dev, torch.float32).contiguous()   # named: the il_batch below holds raw pointers
+  b = batch_desc(dict(states=state, actions=action, rewards=dummy, next_states=state if next_state is None else next_state, terminals=terminal, weights=dummy, absorbing=dummy))
+  out, logits, off = torch.empty(n, device=dev), (torch.empty(n, device=dev) if want_logits else None), _f32(log_policy, dev)
+  _lib.check(getattr(_lib.lib(), disc.reward_entry)(C.byref(d), C.byref(b), _lib.ptr(out), _lib.ptr(logits), _lib.ptr(off), _lib.stream_ptr()))
   return (out, logits) if want_logits else out
 
 
-def _shaped_batch(state, action, next_state, terminal, weight=None):
-  w = weight if weight is not None else terminal
-  return batch_desc(dict(states=state, actions=action, rewards=w, next_states=next_state, terminals=terminal, weights=w, absorbing=w))
+def gail_predict_reward(disc: GAILDiscriminator, state: Tensor, action: Tensor, want_logits: bool = False, log_policy: Optional[Tensor] = None):
+  return _predict_reward(disc, state, action, log_policy=log_policy, want_logits=want_logits)
+
+
+def deep_predict_reward(disc, state: Tensor, action: Tensor, log_policy: Optional[Tensor] = None, want_logits: bool = False):
+  return _predict_reward(disc, state, action, log_policy=log_policy, want_logits=want_logits)
 
 
 def shaped_predict_reward(disc, state: Tensor, action: Tensor, next_state: Tensor, terminal: Tensor, log_policy: Optional[Tensor] = None, want_logits: bool = False):
   """models.py:173-180 for the reward-shaping discriminator (eval mode)."""
-  dev = disc.flat.device
-  n = state.size(0)
-  d = shaped_descriptor(disc, n, None)
-  terminal = terminal.to(dev, torch.float32).contiguous()   # named: the il_batch below holds raw pointers
-  b = _shaped_batch(state, action, next_state, terminal)
-  out, logits, off = torch.empty(n, device=dev), (torch.empty(n, device=dev) if want_logits else None), _f32(log_policy, dev)
-  reward = _lib.lib().il_gail_shaped_deep_reward if _shaped_general(disc) else _lib.lib().il_gail_shaped_reward
-  _lib.check(reward(C.byref(d), C.byref(b), _lib.ptr(out), _lib.ptr(logits), _lib.ptr(off), _lib.stream_ptr()))
-  return (out, logits) if want_logits else out
+  return _predict_reward(disc, state, action, next_state, terminal, log_policy, want_logits)
 
 
-def adversarial_imitation_update(actor, discriminator: GAILDiscriminator, transitions: Dict[str, Tensor], expert_transitions: Dict[str, Tensor], discriminator_optimiser: AdamW,
-                                 imitation_cfg, *, eps_gp: Optional[Tensor] = None, eps_mix: Optional[Tensor] = None, flags: int = 0):
-  """Reference training.py:85-134: loss_function BCE / PUGAIL (any nonnegative_margin) / Mixup, + gradient penalty, spectral norm, entropy bonus,
-  subtract_log_policy.  `eps_gp` / `eps_mix`: the U(0,1) and Beta(alpha, alpha) draws (None: drawn here). `flags` = IL_FLAG_GRADS_ONLY: the gradient is left in
-  `discriminator_optimiser.grad` (the optimiser is ticked, the spectral-norm buffers advance) and the caller applies it after averaging it over ranks (parallel.DataParallelUpdate)."""
-  dev = discriminator.flat.device
-  B = transitions['states'].size(0)
-  pb, eb = batch_desc(transitions), batch_desc(expert_transitions)
-  e = _f32(eps_gp, dev)
+def _gail_extra(actor, discriminator, transitions, expert_transitions, imitation_cfg, eps_mix: Optional[Tensor]):
+  """il_gail_extra of one update - the Mixup draws and the log pi(a|s) offsets of subtract_log_policy - and the tensors its raw pointers need alive."""
+  dev, B = discriminator.flat.device, transitions['states'].size(0)
   x, keep = _lib.GailExtra(), []
-  if getattr(discriminator, 'reward_shaping', False):   # models.py:157-160: its own kernels (k_gs_* for the depth-1 ReLU potential, k_gsd_* for the others)
-    d = shaped_descriptor(discriminator, B, discriminator_optimiser, imitation_cfg)
-    if imitation_cfg.loss_function == 'Mixup':   # training.py:104-113 on every field of the transition (the kernel mixes next_states and terminals too)
-      alpha = float(_cfg_value(imitation_cfg, 'mixup_alpha', 1.0))
-      if eps_mix is None and (alpha != 1.0 or discriminator.subtract_log_policy):
-        eps_mix = torch.distributions.Beta(torch.full((B,), alpha), torch.full((B,), alpha)).sample()
-      if eps_mix is not None:
-        keep.append(_f32(eps_mix, dev)); x.eps_mix = keep[-1].data_ptr()
-      if discriminator.subtract_log_policy:
-        e2 = keep[-1].unsqueeze(1)
-        mix = lambda k: e2 * _f32(expert_transitions[k], dev) + (1 - e2) * _f32(transitions[k], dev)
-        keep.append(actor.log_prob(mix('states'), mix('actions')))
-        x.logit_offset_mix = keep[-1].data_ptr()
-    elif discriminator.subtract_log_policy:
-      keep += [actor.log_prob(transitions['states'], transitions['actions']), actor.log_prob(expert_transitions['states'], expert_transitions['actions'])]
-      x.logit_offset_policy, x.logit_offset_expert = keep[-2].data_ptr(), keep[-1].data_ptr()
-    step = _lib.lib().il_gail_shaped_deep_step if _shaped_general(discriminator) else _lib.lib().il_gail_shaped_step
-    _lib.check(step(C.byref(d), C.byref(pb), C.byref(eb), _lib.ptr(e), C.byref(x), int(flags), _lib.stream_ptr()))
-    return
-  deep = type(discriminator).__name__ == 'DeepGAILDiscriminator'   # depth 2 and / or tanh: the general kernels, same arguments
-  d = (deep_descriptor if deep else disc_descriptor)(discriminator, B, discriminator_optimiser, imitation_cfg)
-  if imitation_cfg.loss_function == 'Mixup':
+  if imitation_cfg.loss_function == 'Mixup':   # training.py:104-113 on every field of the transition (the shaping kernels mix next_states and terminals too)
     alpha = float(_cfg_value(imitation_cfg, 'mixup_alpha', 1.0))
     if eps_mix is None and (alpha != 1.0 or discriminator.subtract_log_policy):   # Beta(1, 1) = U(0, 1) normally comes from the on-chip Philox stream; other alphas,
       eps_mix = torch.distributions.Beta(torch.full((B,), alpha), torch.full((B,), alpha)).sample()   # and draws this function needs itself, are made here like the reference's
@@ -327,20 +261,20 @@ def adversarial_imitation_update(actor, discriminator: GAILDiscriminator, transi
   elif discriminator.subtract_log_policy:   # models.py:144: log pi(a|s) of both batches, no graph
     keep += [actor.log_prob(transitions['states'], transitions['actions']), actor.log_prob(expert_transitions['states'], expert_transitions['actions'])]
     x.logit_offset_policy, x.logit_offset_expert = keep[-2].data_ptr(), keep[-1].data_ptr()
-  step = _lib.lib().il_gail_deep_step if deep else _lib.lib().il_gail_disc_step
-  _lib.check(step(C.byref(d), C.byref(pb), C.byref(eb), _lib.ptr(e), C.byref(x), int(flags), _lib.stream_ptr()))
+  return x, keep
 
 
-def gail_predict_reward(disc: GAILDiscriminator, state: Tensor, action: Tensor, want_logits: bool = False, log_policy: Optional[Tensor] = None):
-  dev = disc.flat.device
-  n = state.size(0)
-  d = disc_descriptor(disc, n, None)
-  dummy = torch.zeros(n, device=dev)
-  b = batch_desc(dict(states=state, actions=action, rewards=dummy, next_states=state, terminals=dummy, weights=dummy, absorbing=dummy))
-  out, logits = torch.empty(n, device=dev), (torch.empty(n, device=dev) if want_logits else None)
-  off = _f32(log_policy, dev)
-  _lib.check(_lib.lib().il_gail_reward(C.byref(d), C.byref(b), _lib.ptr(out), _lib.ptr(logits), _lib.ptr(off), _lib.stream_ptr()))
-  return (out, logits) if want_logits else out
+def adversarial_imitation_update(actor, discriminator: GAILDiscriminator, transitions: Dict[str, Tensor], expert_transitions: Dict[str, Tensor], discriminator_optimiser: AdamW,
+                                 imitation_cfg, *, eps_gp: Optional[Tensor] = None, eps_mix: Optional[Tensor] = None, flags: int = 0):
+  """Reference training.py:85-134: loss_function BCE / PUGAIL (any nonnegative_margin) / Mixup, + gradient penalty, spectral norm, entropy bonus,
+  subtract_log_policy.  `eps_gp` / `eps_mix`: the U(0,1) and Beta(alpha, alpha) draws (None: drawn here). `flags` = IL_FLAG_GRADS_ONLY: the gradient is left in
+  `discriminator_optimiser.grad` (the optimiser is ticked, the spectral-norm buffers advance) and the caller applies it after averaging it over ranks (parallel.DataParallelUpdate).
+  The discriminator names its descriptor and its kernels (models.py): the fused depth-1 ReLU ones, k_gd_* for depth 2 / tanh, k_gs_* / k_gsd_* with reward shaping."""
+  pb, eb = batch_desc(transitions), batch_desc(expert_transitions)
+  e = _f32(eps_gp, discriminator.flat.device)
+  d = globals()[discriminator.descriptor](discriminator, transitions['states'].size(0), discriminator_optimiser, imitation_cfg)
+  x, keep = _gail_extra(actor, discriminator, transitions, expert_transitions, imitation_cfg, eps_mix)
+  _lib.check(getattr(_lib.lib(), discriminator.step_entry)(C.byref(d), C.byref(pb), C.byref(eb), _lib.ptr(e), C.byref(x), int(flags), _lib.stream_ptr()))
 
 
 # ----------------------------------------------------------------------------------------------- GMMIL
@@ -509,14 +443,13 @@ class UpdatePlan:
       self._dyn_set = False
     if algorithm == 'GAIL':
       host_mixup = imitation_cfg is not None and imitation_cfg.loss_function == 'Mixup' and float(_cfg_value(imitation_cfg, 'mixup_alpha', 1.0)) != 1.0
-      deep = type(discriminator).__name__ == 'DeepGAILDiscriminator'   # depth 2 / tanh: the general kernels, per-function path
       pu_margin = imitation_cfg is not None and imitation_cfg.loss_function == 'PUGAIL' and float(_cfg_value(imitation_cfg, 'nonnegative_margin', float('inf'))) != float('inf')
       # The discriminator variants outside the fused depth-1 kernels' two-stream schedule - a finite PUGAIL margin (a value pass ahead of the gradients), subtract_log_policy
       # (two actor passes), reward shaping, depth-2 / tanh discriminators - run their per-function entry points (adversarial_imitation_update + predict_reward, the calls of
       # train.py:178-194) INSIDE the plan, on the gathered rows: every input is device-resident, so the same launches are captured with the rest of the update. They keep
       # plain stream dependencies (no device-side hand-off, no data-parallel or population form).
       sub = bool(imitation_cfg is not None and discriminator.subtract_log_policy)
-      self._variant = bool(imitation_cfg is not None and (deep or pu_margin or sub or getattr(discriminator, 'reward_shaping', False)))
+      self._variant = bool(imitation_cfg is not None and (not discriminator.fused or pu_margin or sub))
       if self._variant:
         if learner_id is not None:
           raise NotImplementedError('UpdatePlan: a population of GAIL learners with a finite PUGAIL margin / subtract_log_policy / reward shaping / a depth-2 or tanh discriminator')
