@@ -247,6 +247,8 @@ _SIGNATURES = {
     'il_red_step': (C.c_int, [C.POINTER(Red), C.POINTER(Batch), _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P]),
     'il_red_forward': (C.c_int, [C.POINTER(Red), C.POINTER(Batch), C.c_int32, _P, _P, _P, C.c_uint32, _P, _P, _P, _P]),
     'il_red_reward_population': (C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(Red), _P]),
+    'il_dril_reward_population': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(Dril), C.c_uint32, _P]),
+    'il_bc_step_population': (C.c_int, [_P, _P, C.c_int32, C.POINTER(Sac), _P, C.c_uint32, _P]),
     # device-resident expert epochs: the per-function sibling's arguments + (il_epoch*, steps)
     'il_bc_epoch_steps': (C.c_int, [_P, _P, C.POINTER(Adam), C.c_int32, C.c_int32, C.c_int32, C.POINTER(Batch), _P, C.c_int64, _P, C.c_uint32, C.POINTER(Epoch), C.c_int32, _P]),
     'il_bc_epoch_workspace_floats_general': (C.c_int64, [C.c_int32] * 5),

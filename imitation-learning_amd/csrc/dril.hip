@@ -8,6 +8,7 @@
 //   k_dril_grad    one workgroup per 32 rows: masked forward, tanh-Gaussian log-prob of the (clamped) expert action, backward, gradient slab
 //   k_dril_apply   slab sum -> grad (+ AdamW)
 //   k_dril_unc     8 rows x 5 ensemble members per workgroup: exp(log_prob) under 5 independent masks, unbiased variance, +-1 reward
+//   k_dril_unc_population   the same tile with the learner as a grid dimension (seed sweeps: il_dril_reward_population)
 // Dropout keep-masks are either supplied (parity tests feed the masks the reference drew) or drawn on chip (Philox, one uniform per element).
 #include "il_common.hpp"
 
@@ -236,9 +237,10 @@ __global__ __launch_bounds__(256) void k_dril_apply(il_dril d, int nt, int apply
   if (e == 0 && cursor) epoch_advance(cursor);   // the last launch of an epoch step
 }
 
+// One 8-row x 5-member tile of the uncertainty launch: what k_dril_unc and k_dril_unc_population both run (mk.ctr already holds the device counter's part).
+// (descriptors by value, the tile's first row and the LDS base taken here: the form in which hipcc kept k_dril_unc's register figures, profiles/dril_population_isa.txt)
 template <int DEPTH>
-__global__ __launch_bounds__(256) void k_dril_unc(il_dril d, il_batch b, DrilMasks mk, float* __restrict__ out_unc, float* __restrict__ out_reward) {
-  if (d.noise_counter) mk.ctr += *d.noise_counter;
+__device__ __forceinline__ void dril_unc_tile(il_dril d, il_batch b, DrilMasks mk, float* __restrict__ out_unc, float* __restrict__ out_reward) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int V = DU * DRIL_ENSEMBLE;
   const DrilLds L = dril_carve(smem, V, d.state_dim, d.hidden, DEPTH, 0);   // forward only: the keep-scales are not kept
@@ -263,12 +265,41 @@ __global__ __launch_bounds__(256) void k_dril_unc(il_dril d, il_batch b, DrilMas
   }
 }
 
-static int check_dril(const il_dril* d, const il_batch* b) {
-  IL_CHECK_ARG(d && b, "il_dril: null descriptor");
+template <int DEPTH>
+__global__ __launch_bounds__(256) void k_dril_unc(il_dril d, il_batch b, DrilMasks mk, float* __restrict__ out_unc, float* __restrict__ out_reward) {
+  if (d.noise_counter) mk.ctr += *d.noise_counter;
+  dril_unc_tile<DEPTH>(d, b, mk, out_unc, out_reward);
+}
+
+// Population axis of k_dril_unc (il_dril_reward_population): gridDim.y selects the learner. The shape (dims, hidden, depth, activation, both dropout probabilities, batch:
+// what sizes the LDS tile and the grid and sets the keep probability) is the host descriptor's, passed by value; what a learner owns comes from its device descriptor:
+// the parameter arena, the threshold q (set_uncertainty_threshold gives every seed its own), the Philox key and the device counter behind its masks. No supplied masks:
+// the keep-masks always come from the Philox stream. The tile is dril_unc_tile as k_dril_unc<DEPTH> runs it: same bits.
+template <int DEPTH>
+__global__ __launch_bounds__(256) void k_dril_unc_population(il_dril d, const il_dril* __restrict__ dL, const il_batch* __restrict__ bL, float* const* __restrict__ rewardL,
+                                                             float* const* __restrict__ uncL, uint32_t noise_offset) {
+  const int lrn = blockIdx.y;
+  il_batch b = bL[lrn];
+  globalize(b);
+  b.n = min(b.n, d.batch);   // the grid and the output buffers are sized by the shape's batch
+  d.params = as_global(dL[lrn].params); d.q = dL[lrn].q; d.noise_seed = dL[lrn].noise_seed;
+  const uint32_t* counter = as_global(dL[lrn].noise_counter);
+  DrilMasks mk = {nullptr, {nullptr, nullptr}, noise_offset};
+  if (counter) mk.ctr += *counter;
+  dril_unc_tile<DEPTH>(d, b, mk, uncL ? as_global(uncL[lrn]) : nullptr, as_global(rewardL[lrn]));
+}
+
+static int check_dril_shape(const il_dril* d) {
   IL_CHECK_ARG(d->state_dim >= 1 && d->state_dim <= 128 && d->action_dim >= 1 && 2 * d->action_dim <= 16 && d->hidden >= 2 && d->hidden <= 256 && d->hidden % 2 == 0,
                "il_dril: unsupported dims (state=%d, action=%d, hidden=%d)", d->state_dim, d->action_dim, d->hidden);
   IL_CHECK_ARG(d->p_in >= 0.f && d->p_in < 1.f && d->p >= 0.f && d->p < 1.f, "il_dril: dropout probabilities must be in [0,1)");
   IL_CHECK_ARG(d->depth >= 0 && d->depth <= 2 && (d->activation == 0 || d->activation == 1), "il_dril: depth must be 1 or 2 (0 = 1) and activation 0 (tanh) or 1 (relu)");
+  return IL_OK;
+}
+
+static int check_dril(const il_dril* d, const il_batch* b) {
+  IL_CHECK_ARG(d && b, "il_dril: null descriptor");
+  if (int rc = check_dril_shape(d)) return rc;
   IL_CHECK_ARG(d->params && b->n > 0 && b->states && b->actions, "il_dril: null parameters / batch");
   return IL_OK;
 }
@@ -318,5 +349,26 @@ extern "C" int il_dril_uncertainty(const il_dril* d, const il_batch* batch, cons
   { IL_TRACE("k_dril_unc", (hipStream_t)stream_);
     unc<<<ceil_div(batch->n, DU), 256, lds, (hipStream_t)stream_>>>(*d, *batch, mk, out_uncertainty, out_reward); }
   IL_CHECK_LAUNCH("il_dril_uncertainty");
+  return IL_OK;
+}
+
+// population axis: the Monte-Carlo-dropout reward (and uncertainty) of n_learners DRIL ensembles of one shape in one launch
+extern "C" int il_dril_reward_population(const il_dril* descs_dev, const il_batch* batches_dev, float* const* rewards_out_dev, float* const* uncertainty_out_dev,
+                                         int32_t n_learners, const il_dril* shape_host, uint32_t noise_offset, il_stream_t stream_) {
+  IL_CHECK_ARG(shape_host, "il_dril_reward_population: null shape descriptor");
+  IL_CHECK_ARG(descs_dev && batches_dev && rewards_out_dev, "il_dril_reward_population: null device array (descriptors %p, batches %p, reward pointers %p)", (const void*)descs_dev,
+               (const void*)batches_dev, (const void*)rewards_out_dev);
+  IL_CHECK_ARG(n_learners >= 1 && n_learners <= 65535, "il_dril_reward_population: n_learners=%d must be in 1..65535 (the learner is a grid dimension)", n_learners);
+  if (int rc = check_dril_shape(shape_host)) return rc;
+  IL_CHECK_ARG(shape_host->batch > 0, "il_dril_reward_population: batch=%d must be > 0", shape_host->batch);
+  const il_dril* d = shape_host;
+  const int depth = dril_depth(*d);
+  const size_t lds = dril_lds_floats(DU * DRIL_ENSEMBLE, d->state_dim, d->hidden, depth, 0) * sizeof(float);
+  if (lds > 160 * 1024) return il_set_error(IL_ERR_UNSUPPORTED, "il_dril_reward_population: the 40-row tile needs %zu bytes of LDS (> 160 KiB per CU)", lds);
+  const auto unc = depth == 2 ? k_dril_unc_population<2> : k_dril_unc_population<1>;
+  if (int rc = il_ensure_lds(unc, lds)) return rc;   // (the > 64 KiB opt-in attaches to a kernel: k_dril_unc's does not cover this one)
+  { IL_TRACE("k_dril_unc_population", (hipStream_t)stream_);
+    unc<<<dim3(ceil_div(d->batch, DU), n_learners), 256, lds, (hipStream_t)stream_>>>(*d, descs_dev, batches_dev, rewards_out_dev, uncertainty_out_dev, noise_offset); }
+  IL_CHECK_LAUNCH("il_dril_reward_population");
   return IL_OK;
 }

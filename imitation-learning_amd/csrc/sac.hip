@@ -2918,9 +2918,23 @@ extern "C" int il_sac_apply_actor_grads(const il_sac* d, il_stream_t stream_) {
 // backward to the pre-activations -- one tile kernel (activations stay in LDS between forward and backward) -- then the
 // shared k_dw_adam.  grid = nt
 // ---------------------------------------------------------------------------------------------
+// POP: the population twin (il_bc_step_population), grid (nt, n_learners): blockIdx.y selects the learner, whose il_sac (actor arena, the actor's optimiser state, workspace)
+// and expert il_batch are loaded from the device arrays in place of the by-value arguments; `b` then only carries the shape's batch in b.n. A learner whose batch descriptor
+// does not fit the shape (rows != batch, or a gather table: the host cannot see either) is skipped: nothing of it is read or written. One body for both instantiations (as a
+// kernel template and not a __device__ function of two kernels: hipcc compiled the inlined function with other address arithmetic than k_bc_tile had,
+// profiles/dril_population_isa.txt).
+__device__ __forceinline__ bool bc_pop_batch_ok(const il_batch& b, int B) { return b.n == B && !b.gather; }
+template <bool POP>
 __global__ __launch_bounds__(1024) void k_bc_tile(const float* __restrict__ actor, il_adam opt, int S, int A, int H, il_batch b, float* __restrict__ W,
-                                                 float* __restrict__ loss_part, il_epoch ep) {
-  if (ep.cursor) epoch_bind(ep, b, blockIdx.x == 0 && threadIdx.x == 0);   // device-resident epoch: b is the expert ring, this step's rows through the order table
+                                                 float* __restrict__ loss_part, il_epoch ep, const il_sac* __restrict__ dL, const il_batch* __restrict__ bL,
+                                                 float* const* __restrict__ lossL) {
+  if (POP) {
+    const int Bshape = b.n;
+    il_sac d = dL[blockIdx.y]; b = bL[blockIdx.y];
+    globalize(d); globalize(b);
+    if (!bc_pop_batch_ok(b, Bshape)) return;
+    actor = d.actor; opt = d.actor_opt; W = d.workspace; loss_part = lossL ? as_global(lossL[blockIdx.y]) : nullptr;
+  } else if (ep.cursor) epoch_bind(ep, b, blockIdx.x == 0 && threadIdx.x == 0);   // device-resident epoch: b is the expert ring, this step's rows through the order table
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int B = b.n, tile = blockIdx.x, row0 = tile * IL_TILE_R, tid = threadIdx.x;
   const int Sp = round_up16(S), ldx = Sp + 4, ldh = H + 4, ldz = 20;
@@ -3029,7 +3043,7 @@ static int bc_steps(float* actor, float* actor_grad, const il_adam* opt, int32_t
   for (int s = 0; s < steps; ++s) {
     // (k_repack stays in every step: k_dw_adam_tiles does not keep the lane-ordered copies of the actor's W2 in step - DwArgs::pk_f / pk_b are the block form's)
     { IL_TRACE("k_repack", st); k_repack<<<dim3(repack_blocks(H), 1), 256, 0, st>>>(tmp, 0x1u, nullptr); }
-    { IL_TRACE("k_bc_tile", st); k_bc_tile<<<nt, tile_threads(H), tile_lds_bytes(round_up16(S + A), H), st>>>(actor, *opt, S, A, H, *b, workspace, out_loss_partials, e); }
+    { IL_TRACE("k_bc_tile", st); k_bc_tile<false><<<nt, tile_threads(H), tile_lds_bytes(round_up16(S + A), H), st>>>(actor, *opt, S, A, H, *b, workspace, out_loss_partials, e, nullptr, nullptr, nullptr); }
     if (ep) { IL_TRACE("k_dw_adam_bc", st); k_dw_adam_tiles_epoch<<<a.n_dw_blocks, 256, 0, st>>>(a, e.cursor); }
     else { IL_TRACE("k_dw_adam_bc", st); launch_dw_adam(a, a.n_dw_blocks, st); }
   }
@@ -3046,6 +3060,54 @@ extern "C" int il_bc_epoch_steps(float* actor, float* actor_grad, const il_adam*
                                  int64_t workspace_floats, float* out_loss_partials, uint32_t flags, const il_epoch* epoch, int32_t steps, il_stream_t stream_) {
   IL_CHECK_EPOCH(epoch, ring, steps, "il_bc_epoch_steps");
   return bc_steps(actor, actor_grad, opt, S, A, H, ring, workspace, workspace_floats, out_loss_partials, flags, epoch, steps, stream_);
+}
+
+// Population axis of il_bc_step (il_bc_step_population): gridDim.y (z for k_repack) selects the learner. The dims and the batch are the host descriptor's; what a learner
+// owns comes from its il_sac on the device: the actor arena, the actor's optimiser state and the workspace; its expert batch from bL (k_bc_tile<true>).
+// k_dw_adam_tiles with il_bc_step's argument set built on the device, as bc_steps fills it (ep == NULL): one network, x0 = the expert batch's states (row-major), no
+// log alpha, no target step, no noise-counter bump. The same dw_adam_kernel<false> body on the same per-learner grid: same jobs, same sums, same bits.
+__global__ __launch_bounds__(256) void k_dw_adam_bc_population(il_sac z, const il_sac* __restrict__ dL, const il_batch* __restrict__ bL) {
+  __shared__ __attribute__((aligned(16))) float smem[2 * DWS * DWS_LD];
+  const int lrn = blockIdx.y;
+  il_sac d = dL[lrn]; il_batch b = bL[lrn];
+  globalize(d); globalize(b);
+  if (!bc_pop_batch_ok(b, z.batch)) return;
+  const int S = z.state_dim, A = z.action_dim, H = z.hidden, B = z.batch;
+  const SacWs ws = sac_ws(S, A, H, B);
+  DwArgs a = {};
+  a.params = d.actor; a.grads = d.actor_grad; a.opt = d.actor_opt; a.grads_only = 0;
+  a.n_nets = 1; a.in_dim = S; a.hidden = H; a.out_dim = 2 * A; a.batch = B;
+  a.x0 = b.states; a.ld_x0 = b.ld_states; a.x0_transposed = 0;
+  a.h1 = d.workspace + ws.a_h1; a.h2 = d.workspace + ws.a_h2; a.dz1 = d.workspace + ws.a_dz1; a.dz2 = d.workspace + ws.a_dz2;
+  a.dz3 = d.workspace + ws.a_dz3;
+  a.n_dw_blocks = dw_blocks(S, H, 2 * A, 1);
+  dw_adam_kernel<false>(a, nullptr, smem);
+}
+// behavioural_cloning_update (il_bc_step) of n_learners actors of one shape on their own expert batches: bc_steps(ep = NULL, steps = 1) with the learner as a grid dimension
+extern "C" int il_bc_step_population(const il_sac* descs_dev, const il_batch* expert_batches_dev, int32_t n_learners, const il_sac* shape_host, float* const* loss_partials_dev,
+                                     uint32_t flags, il_stream_t stream_) {
+  IL_CHECK_ARG(shape_host, "il_bc_step_population: null shape descriptor");
+  IL_CHECK_ARG(descs_dev && expert_batches_dev, "il_bc_step_population: null device array (descriptors %p, expert batches %p)", (const void*)descs_dev, (const void*)expert_batches_dev);
+  IL_CHECK_ARG(n_learners >= 1 && n_learners <= 65535, "il_bc_step_population: n_learners=%d must be in 1..65535 (the learner is a grid dimension)", n_learners);
+  IL_CHECK_ARG(!(flags & IL_FLAG_GRADS_ONLY), "il_bc_step_population: IL_FLAG_GRADS_ONLY is not supported on the population path");
+  const il_sac* d = shape_host;
+  const int S = d->state_dim, A = d->action_dim, H = d->hidden, B = d->batch, L = n_learners;
+  IL_CHECK_ARG(H % 64 == 0 && H >= 64 && H <= 256, "il_bc_step_population: hidden=%d must be a multiple of 64 in [64,256]", H);
+  IL_CHECK_ARG(B > 0 && B % IL_TILE_R == 0, "il_bc_step_population: batch=%d must be a positive multiple of %d", B, IL_TILE_R);
+  IL_CHECK_ARG(S >= 1 && A >= 1 && 2 * A <= 16, "il_bc_step_population: state_dim=%d / action_dim=%d unsupported (2A <= 16)", S, A);
+  const SacWs ws = sac_ws(S, A, H, B);
+  if (d->workspace_floats < ws.total)   // every learner's workspace is built for the shape: the host descriptor's size stands for all of them
+    return il_set_error(IL_ERR_WORKSPACE, "il_bc_step_population: workspace too small (%lld < %lld floats)", (long long)d->workspace_floats, (long long)ws.total);
+  hipStream_t st = (hipStream_t)stream_;
+  const int nt = B / IL_TILE_R;
+  const il_sac z = *d;
+  // (k_repack in every step, as in bc_steps: the tiles dW launch does not keep the lane-ordered copies of the actor's W2 in step)
+  { IL_TRACE("k_repack", st); k_repack<<<dim3(repack_blocks(H), 1, L), 256, 0, st>>>(z, 0x1u, descs_dev); }
+  { IL_TRACE("k_bc_tile", st); il_batch zb = {}; zb.n = B;
+    k_bc_tile<true><<<dim3(nt, L), tile_threads(H), tile_lds_bytes(round_up16(S + A), H), st>>>(nullptr, il_adam{}, S, A, H, zb, nullptr, nullptr, il_epoch{}, descs_dev, expert_batches_dev, loss_partials_dev); }
+  { IL_TRACE("k_dw_adam_bc", st); k_dw_adam_bc_population<<<dim3(dw_blocks(S, H, 2 * A, 1), L), 256, 0, st>>>(z, descs_dev, expert_batches_dev); }
+  IL_CHECK_LAUNCH("il_bc_step_population");
+  return IL_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1434,8 +1434,9 @@ class BatchedPopulationPlan:
   dimension, so one update of the whole population costs 11 launches instead of 11 N.  This is the route from the latency-bound
   single-learner regime towards the HBM roofline.  Every learner keeps its own replay ring, MT19937 index stream,
   networks, optimiser state, scratch and Philox counter (build the `UpdatePlan`s with distinct `learner_id`s).  SAC, GAIL (`il_gail_step_population`: discriminator step +
-  relabel), RED (`il_red_reward_population`: every learner's eval-mode reward under its own predictor, target and sigma_1) and GMMIL (`il_gmmil_reward_population`: every
-  learner's kernel-mean-embedding reward on its own batches, under its own frozen bandwidths, with its own workspace) learners; GAIL's, RED's and GMMIL's reward launches run
+  relabel), DRIL (`il_dril_reward_population`: every learner's Monte-Carlo-dropout reward under its own ensemble, threshold, Philox key and counter; with `bc_aux` also
+  `il_bc_step_population`, the behavioural-cloning auxiliary step of every actor on its own expert batch, in front of the forward kernels), RED (`il_red_reward_population`: every learner's eval-mode reward under its own predictor, target and sigma_1) and GMMIL (`il_gmmil_reward_population`: every
+  learner's kernel-mean-embedding reward on its own batches, under its own frozen bandwidths, with its own workspace) learners; GAIL's, DRIL's, RED's and GMMIL's reward launches run
   on a second stream beside the reward-independent forward kernels (IL_POP_OVERLAP=0: in stream order).  GMMIL: the FIRST run() is eager - every learner fixes its
   bandwidths from its first batch on the host (models.py:193-195), one read per learner, once - and cannot be captured; from the second on an update is the same launches
   as for the others."""
@@ -1457,7 +1458,7 @@ class BatchedPopulationPlan:
     for p in self.plans:
       p._set_device_sync(False)   # one stream, one set of launches for all learners: plain stream order
     p0 = self.plans[0]
-    assert all(p.algorithm == p0.algorithm and p.B == p0.B for p in self.plans) and p0.algorithm in ('SAC', 'GAIL', 'RED', 'GMMIL'), 'the population launches exist for SAC, GAIL, RED and GMMIL learners of one batch size'
+    assert all(p.algorithm == p0.algorithm and p.B == p0.B for p in self.plans) and p0.algorithm in ('SAC', 'GAIL', 'RED', 'GMMIL', 'DRIL'), 'the population launches exist for SAC, GAIL, RED, GMMIL and DRIL learners of one batch size'
     if p0.algorithm == 'RED':
       shape = lambda r: (r.state_dim, r.action_dim, r.hidden, r.depth, r.activation, r.state_only, r.batch)   # what sizes il_red_reward_population's tile and grid
       assert all(shape(p.red) == shape(p0.red) for p in self.plans), 'BatchedPopulationPlan(RED): the discriminators of one population share dims, hidden, depth, activation, state_only and batch'
@@ -1466,6 +1467,12 @@ class BatchedPopulationPlan:
       shape = lambda d: (d.state_size, d.action_size, bool(d.state_only))   # with B: what sizes il_gmmil_reward_population's grid, column block and workspaces
       assert all(shape(p.discriminator) == shape(p0.discriminator) for p in self.plans), 'BatchedPopulationPlan(GMMIL): the learners of one population share state_size, action_size and state_only'
       assert not any(p.mix_expert or p.bc_aux for p in self.plans), 'BatchedPopulationPlan(GMMIL): mixed batches / the BC auxiliary step have no population launches'
+    if p0.algorithm == 'DRIL':
+      shape = lambda d: (d.state_dim, d.action_dim, d.hidden, d.depth, d.activation, d.p_in, d.p, d.batch)   # what sizes il_dril_reward_population's tile and grid and sets its keep probability
+      assert all(shape(p.dril) == shape(p0.dril) for p in self.plans), 'BatchedPopulationPlan(DRIL): the ensembles of one population share dims, hidden, depth, activation, both dropout probabilities and batch'
+      assert all(p.discriminator.q is not None for p in self.plans), 'BatchedPopulationPlan(DRIL): set_uncertainty_threshold first (train.py:126)'
+      assert not any(p.mix_expert for p in self.plans), 'BatchedPopulationPlan(DRIL): mixed batches have no population launches'
+      assert len({p.bc_aux for p in self.plans}) == 1, 'BatchedPopulationPlan(DRIL): the BC auxiliary step (il_bc_step_population) runs for every learner of a population or for none'
     if any(getattr(p, 'general', False) for p in self.plans):
       raise NotImplementedError('BatchedPopulationPlan: actor / critic shapes outside depth 2 / ReLU / hidden <= 256 / action_size <= 8 have no population launches (PopulationPlan runs them as independent graph branches)')
     self.algorithm, self.B, self.L, dev = p0.algorithm, p0.B, len(self.plans), p0.rows.device
@@ -1487,10 +1494,16 @@ class BatchedPopulationPlan:
     if self.algorithm == 'RED':   # every learner's own predictor / target arenas and sigma_1 (set_sigma): read on the device from its descriptor
       self.red_descs = _device_array([p.red for p in self.plans], dev)
       self.reward_ptrs = torch.tensor([p.rewards.data_ptr() for p in self.plans], dtype=torch.int64, device=dev)
+    self.bc_aux = False
+    if self.algorithm == 'DRIL':   # every learner's own ensemble, threshold q, Philox key and device counter (UpdatePlan pointed it at the learner's SAC counter): read on the device from its descriptor
+      self.dril_descs = _device_array([p.dril for p in self.plans], dev)
+      self.reward_ptrs = torch.tensor([p.rewards.data_ptr() for p in self.plans], dtype=torch.int64, device=dev)
+      self.bc_aux = bool(p0.bc_aux)
+      if self.bc_aux: self.expert_batches = _device_array([p.eb for p in self.plans], dev)
     self.gmmil_learners = None   # GMMIL: the il_gmmil_learner array, built once every learner's bandwidths are frozen (after the first run())
     self.graph = None
     self._prepared = False
-    self.side = torch.cuda.Stream() if self.algorithm in ('GAIL', 'RED', 'GMMIL') and os.environ.get('IL_POP_OVERLAP', '1') != '0' else None
+    self.side = torch.cuda.Stream() if self.algorithm in ('GAIL', 'RED', 'GMMIL', 'DRIL') and os.environ.get('IL_POP_OVERLAP', '1') != '0' else None
 
   def run(self):
     if self.subs is not None:
@@ -1503,7 +1516,7 @@ class BatchedPopulationPlan:
         main.wait_stream(s)
       return
     L, st, p0 = _lib.lib(), _lib.stream_ptr(), self.plans[0]
-    prepared = _lib.IL_FLAG_SAC_PREPARED if self._prepared else 0
+    prepared = _lib.IL_FLAG_SAC_PREPARED if (self._prepared and not self.bc_aux) else 0   # the BC auxiliary step moves the actor every update: its lane-ordered copies are re-derived (UpdatePlan.run: flag = 0)
     _lib.check(L.il_replay_sample_population(_lib.ptr(self.sample_args), self.L, self.B, self.max_row, st))
     if self.algorithm == 'RED':
       assert not any(p.discriminator.training for p in self.plans), 'BatchedPopulationPlan(RED): discriminator.eval() first (train.py:147)'
@@ -1519,7 +1532,11 @@ class BatchedPopulationPlan:
       if self.gmmil_learners is None: self._gmmil_freeze()
       d0 = p0.discriminator
       gmmil_args = (_lib.ptr(self.gmmil_learners), self.L, self.B, self.B, d0.state_size, d0.action_size, int(d0.state_only), self.gmmil_whole_lanes, self.gmmil_ws_floats)
-    if self.algorithm in ('GAIL', 'RED', 'GMMIL') and self.side is not None:
+    if self.algorithm == 'DRIL':
+      # the Monte-Carlo-dropout reward of every learner at the offset UpdatePlan uses. It only READS the learners' noise counters, which the actor optimiser launch of the
+      # SKIP_FORWARD half bumps: behind the join below, and in front of the next update's fork (side.wait_stream(main)), so both schedules read the value plan.run() reads
+      dril_args = (_lib.ptr(self.dril_descs), _lib.ptr(self.batches), _lib.ptr(self.reward_ptrs), None, self.L, C.byref(p0.dril), 0x40000000)
+    if self.algorithm in ('GAIL', 'RED', 'GMMIL', 'DRIL') and self.side is not None:
       # The discriminator kernels (48 small workgroups per learner, latency-bound: ~60 us of a ~450 us replay at 32 learners) run on a second stream beside the
       # reward-independent forward kernels of every learner and join before the critic loss. One fork / join per replay (its ~10 us of queue signalling is paid once
       # for the whole population, unlike in the single-learner update where it is why the branches hand over on the device instead).
@@ -1530,8 +1547,12 @@ class BatchedPopulationPlan:
           _lib.check(L.il_gail_step_population(_lib.ptr(self.disc_descs), _lib.ptr(self.batches), _lib.ptr(self.expert_batches), _lib.ptr(self.reward_ptrs), self.L, C.byref(p0.disc), _lib.stream_ptr()))
         elif self.algorithm == 'RED':   # the eval-mode reward of every learner (8 workgroups per learner at batch 256), the same fork and join
           _lib.check(L.il_red_reward_population(_lib.ptr(self.red_descs), _lib.ptr(self.batches), _lib.ptr(self.reward_ptrs), self.L, C.byref(p0.red), _lib.stream_ptr()))
+        elif self.algorithm == 'DRIL':   # 5-member ensembles, 8 rows per workgroup (32 workgroups per learner at batch 256), the same fork and join
+          _lib.check(L.il_dril_reward_population(*dril_args, _lib.stream_ptr()))
         else:   # GMMIL: every learner's reward (16 workgroups per learner at batch 128), the same fork and join
           _lib.check(L.il_gmmil_reward_population(*gmmil_args, _lib.stream_ptr()))
+      if self.bc_aux:   # train.py:201 on the main stream, in front of the forward kernels that read the actor it moves; the reward launch reads neither the actor nor its workspace
+        _lib.check(L.il_bc_step_population(_lib.ptr(self.sac_descs), _lib.ptr(self.expert_batches), self.L, C.byref(p0.sac), None, 0, st))
       _lib.check(L.il_sac_update_population(_lib.ptr(self.sac_descs), _lib.ptr(self.batches), self.L, C.byref(p0.sac), prepared | _lib.IL_FLAG_SAC_FORWARD_ONLY, st))
       main.wait_stream(self.side)
       _lib.check(L.il_sac_update_population(_lib.ptr(self.sac_descs), _lib.ptr(self.batches), self.L, C.byref(p0.sac), _lib.IL_FLAG_SAC_SKIP_FORWARD, st))
@@ -1542,6 +1563,10 @@ class BatchedPopulationPlan:
         _lib.check(L.il_red_reward_population(_lib.ptr(self.red_descs), _lib.ptr(self.batches), _lib.ptr(self.reward_ptrs), self.L, C.byref(p0.red), st))
       if self.algorithm == 'GMMIL':
         _lib.check(L.il_gmmil_reward_population(*gmmil_args, st))
+      if self.algorithm == 'DRIL':
+        _lib.check(L.il_dril_reward_population(*dril_args, st))
+        if self.bc_aux:
+          _lib.check(L.il_bc_step_population(_lib.ptr(self.sac_descs), _lib.ptr(self.expert_batches), self.L, C.byref(p0.sac), None, 0, st))
       _lib.check(L.il_sac_update_population(_lib.ptr(self.sac_descs), _lib.ptr(self.batches), self.L, C.byref(p0.sac), prepared, st))
     self._prepared = True
 

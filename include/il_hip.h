@@ -335,6 +335,16 @@ int il_sac_handoff_timeouts(const il_sac* d, uint32_t* out_host);
 int il_bc_step(float* actor, float* actor_grad, const il_adam* opt, int32_t state_dim, int32_t action_dim, int32_t hidden,
                const il_batch* batch, float* workspace, int64_t workspace_floats, float* out_loss_partials, uint32_t flags,
                il_stream_t stream); /* workspace >= il_sac_workspace_floats(S,A,H,B); out_loss_partials [B/16] (sum/B = loss) or NULL */
+/* Population axis of il_bc_step (train.py:201, imitation.bc_aux_loss, in a seed sweep): one behavioural-cloning step of n_learners actors of one shape, each on its own
+ * expert batch, in il_bc_step's three launches with the learner as a grid dimension (k_repack of the actor, k_bc_tile_population on grid (batch / 16, n_learners), the dW /
+ * AdamW launch on il_bc_step's per-learner grid). Every parameter, moment, step count and loss partial is bit-identical to il_bc_step(actor_l, ..., &expert_batch_l, ...)
+ * per learner. Conventions of il_sac_update_population: shape_host gives state_dim, action_dim, hidden, batch and workspace_floats; what a learner owns comes from ITS
+ * il_sac on the device: actor, actor_opt (its step count advances once per learner) and workspace. loss_partials_dev: NULL, or n_learners pointers to float[batch / 16].
+ * Nothing but the actor moves: no log alpha, no target step, no noise-counter bump. IL_ERR_ARG for a null array or shape, n_learners outside 1..65535,
+ * IL_FLAG_GRADS_ONLY, hidden outside 64..256 in multiples of 64, a batch that is no positive multiple of 16 or 2A > 16; IL_ERR_WORKSPACE for a short workspace; nothing is
+ * launched then. The expert batch descriptors live on the device: a learner whose descriptor has rows != batch or a gather table is skipped by the launches. */
+int il_bc_step_population(const il_sac* descs_dev, const il_batch* expert_batches_dev, int32_t n_learners, const il_sac* shape_host, float* const* loss_partials_dev,
+                          uint32_t flags, il_stream_t stream);
 /* train.py:152 `actor(state).sample()` / models.py:101-102 get_greedy_action for n states: out_action [n,A].
  * eps [n,A] or NULL (Philox with noise_seed/noise_offset); greedy != 0 => tanh(mean). out_logp may be NULL. */
 int il_actor_act(const float* actor, int32_t state_dim, int32_t action_dim, int32_t hidden, const float* states, int32_t ld_states,
@@ -730,6 +740,16 @@ int il_dril_bc_step(const il_dril* d, const il_batch* expert, const float* mask_
  * repeat_interleave order or NULL. out_uncertainty [n] and / or out_reward [n] = (uncertainty <= d->q ? +1 : -1). */
 int il_dril_uncertainty(const il_dril* d, const il_batch* batch, const float* mask_in, const float* mask_hidden, const float* mask_hidden2, uint32_t noise_offset,
                         float* out_uncertainty, float* out_reward, il_stream_t stream);
+/* Population axis: the Monte-Carlo-dropout reward of n_learners DRIL ensembles of one shape in ONE launch (k_dril_unc_population), grid (ceil(batch / 8), n_learners);
+ * rewards_out_dev[l] -> float[batch] and, when uncertainty_out_dev is given, uncertainty_out_dev[l] -> float[batch], every value bit-identical to
+ * il_dril_uncertainty(&desc_l, &batch_l, NULL, NULL, NULL, noise_offset, unc_l, reward_l). Conventions of il_red_reward_population: device arrays indexed by the learner id
+ * and one host descriptor for the shape (state_dim, action_dim, hidden, depth, activation, p_in, p, batch: what sizes the tile and the grid and sets the keep
+ * probability). What a learner owns is read from ITS device descriptor: params, q (set_uncertainty_threshold gives every seed its own), noise_seed and noise_counter,
+ * which is dereferenced on the device like il_dril_uncertainty's. There are no supplied masks: the keep-masks always come from the Philox stream. IL_ERR_ARG for a null
+ * array or shape, n_learners outside 1..65535, batch <= 0 or a shape outside il_dril_uncertainty's limits; IL_ERR_UNSUPPORTED when the 40-row tile needs more than
+ * 160 KiB of LDS (about 103 KB at the largest supported dims); nothing is launched then. */
+int il_dril_reward_population(const il_dril* descs_dev, const il_batch* batches_dev, float* const* rewards_out_dev, float* const* uncertainty_out_dev, int32_t n_learners,
+                              const il_dril* shape_host, uint32_t noise_offset, il_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Data-parallel gradient exchange as ONE kernel per sync point over peer-mapped windows (the reference has no multi-GPU path: this is the

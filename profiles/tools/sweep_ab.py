@@ -8,7 +8,8 @@
 (c) counts as faster than (b) only if its median beats (b)'s by more than (b)'s spread (max - min) of this job; the default of +sweep.schedule follows from that at both L.
   python profiles/tools/sweep_ab.py [--steps 4000] [--repeats 5] [--learners 4 16] [--algorithms GAIL SAC] [--out profiles/sweep_ab.txt]
 (--algorithms RED: the same three forms with the predictor's pretraining cut to 100 iterations per learner; --algorithms GMMIL: at batch 128, the batch of every shipped GMMIL
-configuration, where one reward launch is 16 workgroups)"""
+configuration, where one reward launch is 16 workgroups; --algorithms DRIL: the shipped configuration, i.e. with imitation.bc_aux_loss - il_dril_reward_population and
+il_bc_step_population per update - and the ensemble's pretraining cut to 100 iterations per learner)"""
 import argparse
 import os
 import sys
@@ -37,7 +38,7 @@ def say(text):
 
 
 def overrides(algorithm, steps, start):
-  extra = ['imitation.pretraining.iterations=100'] if algorithm == 'RED' else []   # (the predictor's pretraining sits in front of the clock: kept short, the job measures the loop)
+  extra = ['imitation.pretraining.iterations=100'] if algorithm in ('RED', 'DRIL') else []   # (the predictor's / ensemble's pretraining sits in front of the clock: kept short, the job measures the loop)
   batch = 128 if algorithm == 'GMMIL' else 256
   return [f'algorithm={algorithm}', 'env=halfcheetah', f'steps={steps}', f'training.start={start}', f'training.batch_size={batch}', 'check_time_usage=true', 'logging.interval=1000',
           '+synthetic_env.dataset_trajectories=6'] + extra

@@ -11,7 +11,7 @@ the row-by-row loop.
 
 Sweeps:  python train.py -m seed=1,2,3 algorithm=GAIL env=halfcheetah  (Hydra's multirun: comma lists, Cartesian product, outputs/<algorithm>_<env>_sweeper/<time>/<job>/).
 Jobs that differ only in their seed train as ONE population in lockstep (`train_sweep`: `il.BatchedPopulationPlan` for the update, `il.PopulationActingWorker` or one
-`il.ActingWorker` per learner for acting: `+sweep.schedule=population|per_learner`, the same bits either way; GMMIL sweeps only when that key is given); every other sweep runs its jobs one after another, and says so.
+`il.ActingWorker` per learner for acting: `+sweep.schedule=population|per_learner`, the same bits either way; GMMIL and DRIL sweeps only when that key is given); every other sweep runs its jobs one after another, and says so.
 """
 import os
 import sys
@@ -412,8 +412,12 @@ def _fused_shape(model_cfg) -> bool:
 def sweep_fallback_reason(cfg):
   """None when a seed sweep of this configuration can train as one population (what il.BatchedPopulationPlan and il.PopulationActingWorker take); otherwise the reason
   its jobs run one after another through train()."""
-  if cfg.algorithm not in ('SAC', 'GAIL', 'RED', 'GMMIL'):
-    return f'algorithm={cfg.algorithm} has no population launches (SAC, GAIL and RED have), and GMMIL under an explicit +sweep.schedule'
+  explicit = (cfg.get('sweep', {}) or {}).get('schedule') is not None
+  if cfg.algorithm not in ('SAC', 'GAIL', 'RED', 'GMMIL') and not (cfg.algorithm == 'DRIL' and explicit):
+    reason = f'algorithm={cfg.algorithm} has no population launches (SAC, GAIL and RED have), and GMMIL under an explicit +sweep.schedule'
+    if cfg.algorithm == 'DRIL':   # opt-in, as for GMMIL: a DRIL sweep without the key runs as it always has
+      reason += f'; DRIL trains as one population (il_dril_reward_population, il_bc_step_population) only when +sweep.schedule={"|".join(SWEEP_SCHEDULES)} is given'
+    return reason
   if cfg.algorithm == 'GMMIL' and (cfg.get('sweep', {}) or {}).get('schedule') is None:
     # opt-in: a GMMIL sweep without the key runs as it always has; with it, its first update is eager (every learner's bandwidths) and the rest are population launches
     return f'algorithm=GMMIL trains as one population (il_gmmil_reward_population) only when +sweep.schedule={"|".join(SWEEP_SCHEDULES)} is given'
@@ -423,10 +427,10 @@ def sweep_fallback_reason(cfg):
     return 'actor and critic of different hidden sizes have no population launches'
   if cfg.training.batch_size % 16 != 0:
     return f'training.batch_size={cfg.training.batch_size} is not a multiple of 16'
-  # RED and GMMIL with prefill_memory: the expert rows are moved into the agent ring once, in front of the loop (train.py:134, 192); nothing is edited between the launches
-  if cfg.imitation.mix_expert_data != 'none' and not (cfg.algorithm in ('RED', 'GMMIL') and cfg.imitation.mix_expert_data == 'prefill_memory'):
+  # RED, GMMIL and DRIL with prefill_memory: the expert rows are moved into the agent ring once, in front of the loop (train.py:134, 192); nothing is edited between the launches
+  if cfg.imitation.mix_expert_data != 'none' and not (cfg.algorithm in ('RED', 'GMMIL', 'DRIL') and cfg.imitation.mix_expert_data == 'prefill_memory'):
     return f'imitation.mix_expert_data={cfg.imitation.mix_expert_data} edits the batches between the launches'
-  if cfg.imitation.bc_aux_loss:
+  if cfg.imitation.bc_aux_loss and cfg.algorithm != 'DRIL':   # DRIL (every shipped configuration sets it): il_bc_step_population in front of the forward launches
     return 'imitation.bc_aux_loss adds an actor step per update that the population launches do not have'
   if int(cfg.distributed.world_size) != 1:
     return 'distributed.world_size > 1: a population is a single-GPU mode'
@@ -493,7 +497,7 @@ def train_sweep(cfgs, prefixes):
   """The loop of train() in lockstep over L learners that differ only in their seed: per lockstep step ONE population act launch, L host environment steps and ONE
   append launch (`+acting.schedule=fused`: one launch for both); on update steps ONE population update (il.BatchedPopulationPlan); on evaluation steps
   evaluate_population. Every learner has its own seeds, index stream, environments, rings, networks, optimisers and `learner_id`; job l writes what a single run writes
-  under prefixes[l] (GAIL and RED: with a discriminator.pth; GMMIL, as in train(): without one - its bandwidths are fixed by each learner's first batch, in the first, eager,
+  under prefixes[l] (GAIL, RED and DRIL: with a discriminator.pth; GMMIL, as in train(): without one - its bandwidths are fixed by each learner's first batch, in the first, eager,
   update, and live in no file). Returns the mean normalised score per job."""
   L = len(cfgs)
   assert L >= 1 and len(prefixes) == L
@@ -536,6 +540,9 @@ def train_sweep(cfgs, prefixes):
       ln.discriminator_optimiser = il.AdamW(ln.discriminator, lr=cfg.imitation.learning_rate, weight_decay=cfg.imitation.weight_decay)
     elif cfg.algorithm == 'GMMIL':   # no parameters and no optimiser: its state is the two bandwidths the learner's first batch fixes
       ln.discriminator = il.GMMILDiscriminator(S, A, cfg.imitation)
+    elif cfg.algorithm == 'DRIL':   # the dropout policy ensemble (train.py:73)
+      ln.discriminator = il.DropoutSoftActor(S, A, cfg.imitation.discriminator)
+      ln.discriminator_optimiser = il.AdamW(ln.discriminator, lr=cfg.imitation.learning_rate, weight_decay=cfg.imitation.weight_decay)
     ln.metrics = dict(train_steps=[], train_returns=[], test_steps=[], test_returns=[], test_returns_normalized=[], update_steps=[], predicted_rewards=[], alphas=[], entropies=[], Q_values=[])
     ln.score = []
     start_time += time.time() - built
@@ -554,13 +561,25 @@ def train_sweep(cfgs, prefixes):
         start_time += ln.metrics['pre_training_time']
       if cfg.imitation.mix_expert_data == 'prefill_memory': ln.memory.transfer_transitions(ln.expert_memory)
       ln.discriminator.eval()   # train.py:147, in front of the plan: from here on the predictor's dropout is off
+    if cfg.algorithm == 'DRIL':   # train.py:114-134 in train()'s order, while this learner's seed is the process seed (the ensemble's descriptors read their Philox key from it): ensemble pretraining, its own threshold, the prefill
+      if pretraining_schedule(cfg) == 'plan' and cfg.imitation.pretraining.iterations > 0:
+        il.PretrainPlan('DRIL', ln.discriminator, ln.discriminator_optimiser, ln.expert_memory, B, torch.Generator().manual_seed(cfg.seed)).run(cfg.imitation.pretraining.iterations)
+      else:
+        for batch in expert_batches(cfg, ln.expert_memory, S, A, cfg.imitation.pretraining.iterations):
+          il.behavioural_cloning_update(ln.discriminator, batch, ln.discriminator_optimiser)
+      ln.discriminator.set_uncertainty_threshold(ln.expert_memory['states'][:ln.expert_memory.size], ln.expert_memory['actions'][:ln.expert_memory.size], cfg.imitation.quantile_cutoff)
+      if cfg.check_time_usage:
+        ln.metrics['pre_training_time'] = time.time() - began
+        start_time += ln.metrics['pre_training_time']
+      if cfg.imitation.mix_expert_data == 'prefill_memory': ln.memory.transfer_transitions(ln.expert_memory)
     if cfg.algorithm == 'GMMIL' and cfg.imitation.mix_expert_data == 'prefill_memory': ln.memory.transfer_transitions(ln.expert_memory)   # train.py:192, once, in front of the loop
     ln.plan = il.UpdatePlan(cfg.algorithm, ln.actor, ln.critic, ln.log_alpha, ln.target_critic, ln.memory, ln.actor_optimiser, ln.critic_optimiser, ln.temperature_optimiser, B,
                             cfg.reinforcement.discount, entropy_target, cfg.reinforcement.polyak_factor, expert_memory=ln.expert_memory, discriminator=ln.discriminator,
-                            discriminator_optimiser=ln.discriminator_optimiser, imitation_cfg=cfg.imitation if cfg.algorithm == 'GAIL' else None, overlap=False, learner_id=i)
+                            discriminator_optimiser=ln.discriminator_optimiser, imitation_cfg=cfg.imitation if cfg.algorithm == 'GAIL' else None, overlap=False, learner_id=i,
+                            bc_aux=bool(cfg.imitation.bc_aux_loss))   # (sweep_fallback_reason: set for DRIL learners only)
     ln.plan.main_feeds_ring = True
     ln.plan.watch_timeouts()
-    if ln.discriminator is not None: ln.discriminator.eval()   # train.py:147
+    if ln.discriminator is not None and cfg.algorithm != 'DRIL': ln.discriminator.eval()   # train.py:147 (the DRIL ensemble keeps its dropout, i.e. train mode, on purpose)
     learners.append(ln)
   plans = [ln.plan for ln in learners]
 
@@ -654,7 +673,7 @@ def train_sweep(cfgs, prefixes):
       _, trajectories = evaluate_agent(ln.actor, ln.eval_env, cfg.evaluation.episodes, return_trajectories=True, render=cfg.render)
       torch.save(trajectories, f'{ln.prefix}trajectories.pth')
     torch.save(dict(actor=ln.actor.state_dict(), critic=ln.critic.state_dict(), log_alpha=ln.log_alpha), f'{ln.prefix}agent.pth')
-    if cfg.algorithm in ('GAIL', 'RED'): torch.save(ln.discriminator.state_dict(), f'{ln.prefix}discriminator.pth')   # train.py:238
+    if cfg.algorithm in ('DRIL', 'GAIL', 'RED'): torch.save(ln.discriminator.state_dict(), f'{ln.prefix}discriminator.pth')   # train.py:238
     torch.save(m, f'{ln.prefix}metrics.pth')
     scores.append(float(np.mean(ln.score)) if ln.score else float('nan'))
   return scores
