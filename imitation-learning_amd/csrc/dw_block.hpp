@@ -48,7 +48,7 @@ struct DwPeer { il_peer_bucket x; int64_t alpha_at; };
 // clocks = 3.9 us - the duration of the launch, whatever the schedule of the loads (round 3 A/B: all operand lanes ahead of the MFMAs, 16 lanes per operand in flight:
 // no change; the same jobs at 16 per CU inside k_sac_chain: 4x longer). Here the 256 threads of a workgroup fetch the two [32 features][B] panels with every wave
 // instruction covering whole lines (64 lanes = 2 features x 512 contiguous bytes), 16 KB per tile instead of 32 KB, park them in LDS in two 128-row chunks (all
-// loads of both chunks are requested up front, with the block's p / m / v lanes), and each wave runs ONE 16 x 16 tile out of LDS with dw_tile's accumulators and MFMA
+// loads of both chunks are requested up front, with the block's p / m / v lanes and the optimiser's constants), and each wave runs ONE 16 x 16 tile out of LDS with dw_tile's accumulators and MFMA
 // order (row groups ascending; k-steps 0, 2 -> acc0 and 1, 3 -> acc1): same bits. The epilogue goes through LDS like dw_block64's: AdamW row-wise on 16-byte lanes
 // (128-byte row segments per 8 threads instead of 4-byte pieces of 16 rows), the updated block once more for the column-wise lane order of the PB copy.
 // ---------------------------------------------------------------------------------------------
@@ -62,10 +62,44 @@ struct DwPeer { il_peer_bucket x; int64_t alpha_at; };
 // then the four g as (g0 + g1) + (g2 + g3)), so the bias keeps its bits too. With it a network's whole optimiser step is nbh^2 + 2 nbh uniform workgroups (H = 256: 80)
 // and no wave-per-tile job is left: those were 72 % of the launch's line requests (32 KB of half-line gathers each).
 // `boff` >= 0: parameter offset of the bias of this dZ (only looked at by blocks with k0 == 0).
-// Gate: called by every thread once the block's p / m / v lanes are requested and before its operands are; true = leave without storing anything (sac.hip's overlapped
-// launches wait there for the launch that produces dZ, and a poisoned learner stops there)
-struct DwNoGate { __device__ __forceinline__ bool operator()(const DwArgs&) const { return false; } };
-template <bool PEER = false, class Gate = DwNoGate>
+// One request batch: p / m / v (+ the bias's operands), the optimiser's constants, the sixteen operand lanes and the gate's word are all requested before the first wait - a
+// block job's duration is its number of DEPENDENT memory trips (one wave per SIMD, nothing else on the CU), and the constants and the gate depend on nothing the job
+// computes. The constants are read up front because every caller's optimiser is ticked (adam_tick) by an EARLIER launch: the chain / policy-critic launches of sac.hip,
+// the loss kernels of the population and behavioural-cloning paths, general.hip's backward launch (its `tick`). LATE_CONSTS keeps them behind the products: for a caller
+// that ticks inside the dW launch (none today), and for the population launch and general.hip's k_gt_dw32, whose 128-register budgets (four waves per SIMD) have no room for one more lane in flight.
+// Gate (all static, called by every thread of the workgroup):
+//   ordered(a)   true = the launch that produces the operands may still be running (sac.hip's overlapped schedule): wait(a) runs once p / m / v are requested and BEFORE the
+//                operands and the constants are (true = leave without storing anything), and the constants keep their place behind the products
+//   request(a)   otherwise: a word requested behind the first trip's operand lanes (the youngest entry of the wave's load queue: no operand waits for it) ...
+//   leave(a, w, lds)  ... and looked at across the epilogue's barrier between the products and the first store of any kind; true (workgroup-uniform) = leave without storing
+//                anything. `lds`: 8 bytes of the workgroup's LDS that nobody else uses around that barrier
+// The optimiser's constants as a request and a take: lane l asks for float l % 8 of the eight (ONE register per lane in flight beside the operand lanes, where
+// load_adam_consts' two 16-byte loads per lane are eight), and the take - by all 64 lanes of the wave, once the value has arrived - broadcasts them into scalar registers.
+__device__ __forceinline__ float adam_consts_request(const il_adam& o) { return gload(reinterpret_cast<const float*>(o.step) + 4 + (threadIdx.x & 7)); }
+__device__ __forceinline__ adam_consts adam_consts_take(float r) {
+  const int v = __float_as_int(r);
+  adam_consts c;
+  c.decay = __int_as_float(__builtin_amdgcn_readlane(v, 0)); c.one_m_b1 = __int_as_float(__builtin_amdgcn_readlane(v, 1));
+  c.beta2 = __int_as_float(__builtin_amdgcn_readlane(v, 2)); c.one_m_b2 = __int_as_float(__builtin_amdgcn_readlane(v, 3));
+  c.step_size = __int_as_float(__builtin_amdgcn_readlane(v, 4)); c.bc2_sqrt = __int_as_float(__builtin_amdgcn_readlane(v, 5));
+  c.eps = __int_as_float(__builtin_amdgcn_readlane(v, 6)); c.has_decay = __int_as_float(__builtin_amdgcn_readlane(v, 7)) != 0.f;
+  return c;
+}
+// the same constants out of their two 16-byte lanes as ONE thread requested them (floats 4 .. 7 and 8 .. 11 of `step`): built where they are used, so that no compare of a
+// lane that is still on its way stands between two requests
+__device__ __forceinline__ adam_consts adam_consts_of(const f32x4& lo, const f32x4& hi) {
+  adam_consts c;
+  c.decay = lo[0]; c.one_m_b1 = lo[1]; c.beta2 = lo[2]; c.one_m_b2 = lo[3]; c.step_size = hi[0]; c.bc2_sqrt = hi[1]; c.eps = hi[2]; c.has_decay = hi[3] != 0.f;
+  return c;
+}
+struct DwNoGate {
+  typedef int word;
+  static __device__ __forceinline__ bool ordered(const DwArgs&) { return false; }
+  static __device__ __forceinline__ bool wait(const DwArgs&) { return false; }
+  static __device__ __forceinline__ word request(const DwArgs&) { return 0; }
+  static __device__ __forceinline__ bool leave(const DwArgs&, word, float*) { __syncthreads(); return false; }
+};
+template <bool PEER = false, class Gate = DwNoGate, bool LATE_CONSTS = false>
 __device__ __forceinline__ void dw_block32(const DwArgs& a, const float* __restrict__ dzT, int Nvalid, const float* __restrict__ xT, int Kvalid, int n0, int k0, int64_t poff,
                                            int64_t boff, float* __restrict__ pkf, float* __restrict__ pkb, float* smem, const DwPeer* pp = nullptr, int pjob = -1) {
   float* Zs = smem; float* Xs = smem + DWS * DWS_LD;
@@ -102,10 +136,15 @@ __device__ __forceinline__ void dw_block32(const DwArgs& a, const float* __restr
   const bool bias_owner = do_bias && tid < 128 && bg == 0 && n0 + bf < Nvalid;
   float bpp = 0.f, bmm = 0.f, bvv = 0.f;
   if (bias_owner && !a.grads_only) { const int64_t o = boff + n0 + bf; bpp = gload(a.params + o); bmm = gload(a.opt.m + o); bvv = gload(a.opt.v + o); }   // the bias's Adam operands: with the block's, up front
-  if (Gate()(a)) return;
+  const bool ordered = Gate::ordered(a);   // (wave-uniform: a kernel argument)
+  if (ordered && Gate::wait(a)) return;
+  const bool late_consts = LATE_CONSTS || ordered;
+  float ac_lane = 0.f;
+  if (!a.grads_only && !late_consts) ac_lane = adam_consts_request(a.opt);
+  typename Gate::word gate_word = 0;
   f32x4 acc0 = zero4(), acc1 = zero4();
-  for (int r0 = 0; r0 < B; r0 += 2 * DWS_ROWS) {   // two chunks per trip, all their loads in flight together (B = 256: one trip)
-    f32x4 zr[2][4], xr[2][4];
+  f32x4 zr[2][4], xr[2][4];
+  const auto request = [&](const int r0) {   // a trip = two chunks, all their loads in flight together (B = 256: one trip)
 #pragma unroll
     for (int c = 0; c < 2; ++c)
 #pragma unroll
@@ -113,6 +152,11 @@ __device__ __forceinline__ void dw_block32(const DwArgs& a, const float* __restr
         const int rr = min(r0 + c * DWS_ROWS, B - DWS_ROWS) + sr;   // (B % 256 == 128: the second chunk of the last trip re-reads the first and is not used)
         zr[c][u] = gload4(dzT + (size_t)min(n0 + sf + 8 * u, Nvalid - 1) * B + rr); xr[c][u] = gload4(xT + (size_t)min(k0 + sf + 8 * u, Kvalid - 1) * B + rr);
       }
+  };
+  request(0);
+  if (!ordered) gate_word = Gate::request(a);   // the last request of the batch
+  for (int r0 = 0; r0 < B; r0 += 2 * DWS_ROWS) {
+    if (r0 > 0) request(r0);   // (the previous trip's lanes are in LDS and read)
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
@@ -144,14 +188,14 @@ __device__ __forceinline__ void dw_block32(const DwArgs& a, const float* __restr
     for (int r = 0; r < 4; ++r) Gs[(16 * ti + 4 * g + r) * DWS_GLD + 16 * tq + j] = t[r];
   }
   adam_consts ac = {};
-  if (!a.grads_only) ac = load_adam_consts(a.opt);
+  if (!a.grads_only) { if (late_consts) ac_lane = adam_consts_request(a.opt); ac = adam_consts_take(ac_lane); }
   float bsum = 0.f;
   if (do_bias && tid < 128) {   // (all 64 lanes of waves 0, 1 take part in the shuffles)
     bsum = (bs4[0] + bs4[1]) + (bs4[2] + bs4[3]);
     bsum += __shfl_xor(bsum, 1, 64);
     bsum += __shfl_xor(bsum, 2, 64);
   }
-  __syncthreads();
+  if (ordered) __syncthreads(); else if (Gate::leave(a, gate_word, Xs)) return;   // the gradient block is in LDS (Zs' rows; Xs is free); nothing has been stored yet
   f32x4 gv = *reinterpret_cast<const f32x4*>(Gs + er * DWS_GLD + ec);
   if (flat) {   // this thread's lane of the contiguous run: elements 4 tid .. + 3 = (row e / Kvalid, column e % Kvalid) of the block
     const unsigned mk = fastdiv_magic(Kvalid);

@@ -798,7 +798,8 @@ __global__ __launch_bounds__(256) void k_gt_dw32(GtDw a) {
   DwArgs d = {};
   d.params = a.P; d.grads = a.G; d.opt = a.opt; d.grads_only = a.grads_only; d.batch = a.Bp;
   const int64_t base = net * a.p_ns;
-  dw_block32<false>(d, L.dZT + net * L.dz_ns, L.N, L.XT + net * L.x_ns, L.K, (b / nbk) * DWS, (b % nbk) * DWS, base + L.oW, base + L.ob, L.PF ? L.PF + net * a.pk_ns : nullptr,
+  // (the constants stay behind the products here - dw_block32's LATE_CONSTS: with them in flight beside the operand lanes this kernel is one register over four waves per SIMD)
+  dw_block32<false, DwNoGate, true>(d, L.dZT + net * L.dz_ns, L.N, L.XT + net * L.x_ns, L.K, (b / nbk) * DWS, (b % nbk) * DWS, base + L.oW, base + L.ob, L.PF ? L.PF + net * a.pk_ns : nullptr,
                     L.PB ? L.PB + net * a.pk_ns : nullptr, smem);
 }
 // lane-ordered copies of the H x H layers: blockIdx.y = slot; slot s copies W (src[s]) into PF[s] / PB[s] (PB NULL: forward copy only)

@@ -320,7 +320,10 @@ __device__ __forceinline__ void sync_timed_out(long long* sync) {   // one threa
   const long long host = sync[IL_SYNC_HOST_FLAG];
   if (host) __hip_atomic_store((__attribute__((address_space(1))) long long*)host, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // typed global: a FLAT store would make every later wait of the kernel conservative
 }
-// wave-uniform: has a bounded wait of this learner expired (now or in an earlier launch)? Read by the optimiser epilogues right before their stores.
+// wave-uniform: has a bounded wait of this learner expired (now or in an earlier launch)? A load and a wait for it: a trip to memory of its own (below the caches) wherever it
+// stands. The overlapped optimiser launches and k_gail_reduce read it like this, behind their waits; the in-order block jobs and tail blocks of k_dw_adam do not call it -
+// they REQUEST the same word with their operands (sync_read(sync, IL_SYNC_POISON); sac.hip DwOvGate, dw_tail_alpha, dw_tail_polyak) and look at it between the arrival
+// of those operands and their first store.
 __device__ __forceinline__ bool sync_poisoned(const long long* sync) {
   return sync && __hip_atomic_load(sync + IL_SYNC_POISON, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
 }

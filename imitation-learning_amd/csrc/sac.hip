@@ -1764,9 +1764,21 @@ __device__ __forceinline__ void dw_bias(const DwArgs& a, const adam_consts& ac, 
   if (g == 0 && n0 + j < Nvalid) adam_store(a, ac, poff + n0 + j, s);
 }
 
-template <bool PEER>
-__device__ __forceinline__ void dw_tail_alpha(const DwArgs& a, const DwPeer* pp, bool poisoned = false) {   // tail block 0: Adam(log alpha), the Philox counter, the end-of-update signal (one thread); poisoned: no store to log alpha or its moments
+// tail block 0: Adam(log alpha), the Philox counter, the end-of-update signal (one thread). One thread's dependent chain: everything it reads - the first sixteen
+// partials, log alpha, its moments, the optimiser's constants (alpha_opt is ticked by an EARLIER launch: the policy / critic launch), the noise counter (last written by
+// the previous update's tail) and, with FLAGGED (in-order launches of k_dw_adam with il_sync counters: `sync` is not NULL), the learner's [IL_SYNC_POISON] word - is
+// requested together, ahead of the first wait. poisoned, or a raised word: no store to log alpha or its moments. (FLAGGED is a template parameter so that the word is
+// a load on every path: as `sync ? load : 0` its compare with zero is moved up to the load by the compiler, and the wait with it, in front of the other requests.)
+template <bool PEER, bool FLAGGED = false>
+__device__ __forceinline__ void dw_tail_alpha(const DwArgs& a, const DwPeer* pp, bool poisoned = false, const long long* sync = nullptr) {
   if (a.log_alpha && threadIdx.x == 0) {
+    long long poison = 0;
+    if (FLAGGED) poison = sync_read(sync, IL_SYNC_POISON);
+    const float la = gload(a.log_alpha);
+    float mm = 0.f, vv = 0.f; f32x4 c_lo = zero4(), c_hi = zero4();
+    if (!a.grads_only) { mm = gload(a.alpha_opt.m); vv = gload(a.alpha_opt.v); const float* f = reinterpret_cast<const float*>(a.alpha_opt.step) + 4; c_lo = gload4(f); c_hi = gload4(f + 4); }
+    // (without a counter: log alpha's word once more, not looked at - a load on every path, like the flag)
+    const uint32_t nc = gload(a.noise_counter ? a.noise_counter : reinterpret_cast<const uint32_t*>(a.log_alpha));
     float s = 0.f;
     int i0 = 0;
     for (; i0 + 16 <= a.n_alpha_part; i0 += 16) {   // one thread, B / 16 partials: requested together, added in index order (as a plain loop: one dependent round trip per partial)
@@ -1778,24 +1790,25 @@ __device__ __forceinline__ void dw_tail_alpha(const DwArgs& a, const DwPeer* pp,
       for (int u = 0; u < 16; ++u) s += t[u];
     }
     for (int i = i0; i < a.n_alpha_part; ++i) s += a.alpha_part[i];
-    const float alpha = expf(a.log_alpha[0]);
+    const float alpha = expf(la);
     float gr = -(alpha) * (s / (float)a.batch);
     if (PEER) gr = peer_thread_allreduce1(pp->x, a.n_big_blocks, pp->alpha_at, gr);   // data-parallel: the mean over the ranks (its own arrival line behind the block jobs')
     if (a.grads_only) a.alpha_grad[0] = gr;
-    else if (!poisoned) {
-      const adam_consts ac = load_adam_consts(a.alpha_opt);
-      float pp = a.log_alpha[0], mm = a.alpha_opt.m[0], vv = a.alpha_opt.v[0];
-      adam_update(pp, gr, mm, vv, ac);
+    else if (!poisoned && poison == 0) {
+      float pp = la;
+      adam_update(pp, gr, mm, vv, adam_consts_of(c_lo, c_hi));
       a.log_alpha[0] = pp; a.alpha_opt.m[0] = mm; a.alpha_opt.v[0] = vv;
     }
     // (with il_sync counters the bumped counter is read by the NEXT update's discriminator launch, resident on the other stream: written through and drained like every
     // other in-launch hand-off, profiles/r06_soak_under_load.md)
-    if (a.noise_counter) { if (a.sync) { wstore1(reinterpret_cast<float*>(a.noise_counter), 0, __uint_as_float(a.noise_counter[0] + 1u)); sync_drain_stores(); } else a.noise_counter[0] += 1; }
+    if (a.noise_counter) { if (a.sync) { wstore1(reinterpret_cast<float*>(a.noise_counter), 0, __uint_as_float(nc + 1u)); sync_drain_stores(); } else a.noise_counter[0] = nc + 1u; }
     // this update's SAC half is done. Release: the resident sampler and, behind it, the discriminator kernels of the NEXT update start from this signal and read the noise counter bumped above
     if (a.sync) __hip_atomic_fetch_add(reinterpret_cast<long long*>(a.sync) + IL_SYNC_MAIN_EPOCH, 1LL, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
-__device__ __forceinline__ void dw_tail_polyak(const DwArgs& a, const int tb, const int ntb) {   // every tail block: target <- tau target + (1 - tau) critic
+// every tail block: target <- tau target + (1 - tau) critic. poison_at (in-order launches of k_dw_adam): the learner's [IL_SYNC_POISON] word is requested behind each
+// trip's lanes and looked at between their arrival and their stores - a raised word: nothing is stored. (No barrier in here: a wave decides for itself.)
+__device__ __forceinline__ void dw_tail_polyak(const DwArgs& a, const int tb, const int ntb, const long long* poison_at = nullptr) {
   if (a.target && !a.grads_only) {
     const float omt = (float)(1.0 - a.tau), tau = (float)a.tau;
     // (round 3) target <- tau target + (1 - tau) critic over the parameter arena AND its lane-ordered copies as ONE index space of 16-byte lanes, four lanes per thread
@@ -1812,12 +1825,13 @@ __device__ __forceinline__ void dw_tail_polyak(const DwArgs& a, const int tb, co
           dst[u] = reinterpret_cast<f32x4*>(second ? a.pk_target : a.target) + (second ? qc - n1 : qc);
           t[u] = *dst[u]; p[u] = *(reinterpret_cast<const f32x4*>(second ? a.pk_critic : a.polyak_src) + (second ? qc - n1 : qc));
         }
+        const long long poison = poison_at ? sync_read(poison_at, IL_SYNC_POISON) : 0LL;
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
 #pragma unroll
           for (int q = 0; q < 4; ++q) t[u][q] = __fadd_rn(__fmul_rn(t[u][q], tau), __fmul_rn(omt, p[u][q]));
-          if (i + u * stride < n1 + n2) {
+          if (i + u * stride < n1 + n2 && poison == 0) {
             const int64_t q2 = i + u * stride;   // written through like p / m / v: the target network is not read again before the next update's forward
             if (q2 >= n1) wstore4(a.pk_target, (q2 - n1) * 4, t[u]); else wstore4(a.target, q2 * 4, t[u]);
           }
@@ -1825,6 +1839,7 @@ __device__ __forceinline__ void dw_tail_polyak(const DwArgs& a, const int tb, co
       }
       return;
     }
+    if (sync_poisoned(poison_at)) return;
     for (int64_t i = ((int64_t)tb * blockDim.x + threadIdx.x) * 4; i < a.polyak_n; i += (int64_t)ntb * blockDim.x * 4) {
       if (a.polyak_fused) {   // the H x H layers were stepped by the critic launch's blocks: whole lanes inside them are skipped, lanes at their edges go element by element
         // (the twin critic's layout from what the tail knows: polyak_n = 2 strides, stride = H IN + H | H H | H | H | 1 rounded up to a multiple of 4 floats)
@@ -2060,12 +2075,26 @@ static inline int dw_block64_count(int H, int nets) { return (H / DWB) * (H / DW
 // One network's optimiser step as uniform block jobs: [0, nbh^2) the H x H layer (bias 2 with the k0 = 0 blocks), then nbh x kin blocks of layer 1 (bias 1), then
 // nout x nbh blocks of layer 3 (bias 3). Returns false when `job` is past the network's list.
 __host__ __device__ static inline int dw_block_jobs(int IN, int H, int OUT) { const int nbh = H / DWS; return nbh * nbh + nbh * ((IN + DWS - 1) / DWS) + ((OUT + DWS - 1) / DWS) * nbh; }
-// the gate of the single-learner kernel's block jobs (dw_block.hpp): overlapped launches wait for the launch that produces dZ / the activations while p / m / v are on
-// their way; an update whose hand-off expired - in an earlier launch of this update, or in that wait - never reaches the weights ([IL_SYNC_POISON])
+// the gate of the single-learner kernel's block jobs (dw_block.hpp): an update whose hand-off expired - in an earlier launch of this update, or in the overlapped schedule's
+// own wait - never reaches the weights ([IL_SYNC_POISON]). In-order launches (ov_stage == 0) request the flag behind their operands and look at it in the epilogue's barrier;
+// overlapped launches (`ordered`) wait for the launch that produces dZ / the activations while p / m / v are on their way, and read the flag behind that wait.
 struct DwOvGate {
-  __device__ __forceinline__ bool operator()(const DwArgs& a) const { dw_ov_wait<true>(a); return a.sync && __syncthreads_or(sync_poisoned(reinterpret_cast<const long long*>(a.sync)) ? 1 : 0); }
+  typedef long long word;
+  static __device__ __forceinline__ bool ordered(const DwArgs& a) { return a.ov_stage != 0; }
+  static __device__ __forceinline__ bool wait(const DwArgs& a) { dw_ov_wait<true>(a); return a.sync && __syncthreads_or(sync_poisoned(reinterpret_cast<const long long*>(a.sync)) ? 1 : 0); }
+  static __device__ __forceinline__ word request(const DwArgs& a) { return a.sync ? sync_read(reinterpret_cast<const long long*>(a.sync), IL_SYNC_POISON) : 0LL; }
+  // ONE thread's word decides for the workgroup (the waves may have read it at different times, and barriers follow): it crosses the epilogue's own barrier through LDS,
+  // as it arrived - no barrier is added, and no arithmetic touches the word in front of the barrier (a compare the compiler could move up to the load, and the wait
+  // for the load with it, in front of the products)
+  static __device__ __forceinline__ bool leave(const DwArgs& a, word w, float* lds) {
+    if (!a.sync) { __syncthreads(); return false; }
+    long long* slot = reinterpret_cast<long long*>(lds);
+    if (threadIdx.x == 0) *slot = w;
+    __syncthreads();
+    return *slot != 0;
+  }
 };
-template <bool PEER = false, class Gate = DwNoGate>
+template <bool PEER = false, class Gate = DwNoGate, bool LATE_CONSTS = false>
 __device__ __forceinline__ void dw_block_job(const DwArgs& a, int net, int job, float* smem, const DwPeer* pp = nullptr, int pjob = -1) {
   const int IN = a.in_dim, H = a.hidden, OUT = a.out_dim, nbh = H / DWS, kin = (IN + DWS - 1) / DWS;
   const int64_t pbase = (int64_t)net * a.net_stride;
@@ -2081,13 +2110,13 @@ __device__ __forceinline__ void dw_block_job(const DwArgs& a, int net, int job, 
       const int x = job & 7, slot = job >> 3;
       nb = 2 * (x >> 1) + (slot >> 2); kb = 4 * (x & 1) + (slot & 3);
     }
-    dw_block32<PEER, Gate>(a, dz2, H, h1, H, nb * DWS, kb * DWS, oW2, ob2, a.pk_f ? a.pk_f + (size_t)net * H * H : nullptr, a.pk_b ? a.pk_b + (size_t)net * H * H : nullptr, smem, pp, pjob);
+    dw_block32<PEER, Gate, LATE_CONSTS>(a, dz2, H, h1, H, nb * DWS, kb * DWS, oW2, ob2, a.pk_f ? a.pk_f + (size_t)net * H * H : nullptr, a.pk_b ? a.pk_b + (size_t)net * H * H : nullptr, smem, pp, pjob);
     return;
   }
   job -= nbh * nbh;
-  if (job < nbh * kin) { dw_block32<PEER, Gate>(a, dz1, H, a.x0 + net * a.x0_net_stride, IN, (job / kin) * DWS, (job % kin) * DWS, oW1, ob1, nullptr, nullptr, smem, pp, pjob); return; }
+  if (job < nbh * kin) { dw_block32<PEER, Gate, LATE_CONSTS>(a, dz1, H, a.x0 + net * a.x0_net_stride, IN, (job / kin) * DWS, (job % kin) * DWS, oW1, ob1, nullptr, nullptr, smem, pp, pjob); return; }
   job -= nbh * kin;
-  dw_block32<PEER, Gate>(a, a.dz3 + net * a.dz3_net_stride, OUT, h2, H, (job / nbh) * DWS, (job % nbh) * DWS, oW3, ob3, nullptr, nullptr, smem, pp, pjob);
+  dw_block32<PEER, Gate, LATE_CONSTS>(a, a.dz3 + net * a.dz3_net_stride, OUT, h2, H, (job / nbh) * DWS, (job % nbh) * DWS, oW3, ob3, nullptr, nullptr, smem, pp, pjob);
 }
 static inline int dw_block32_count(int H, int nets) { return (H / DWS) * (H / DWS) * nets; }
 static inline bool dw_block32_fits(int H, int B) { return H % DWS == 0 && B % DWS_ROWS == 0; }
@@ -2132,15 +2161,18 @@ __global__ __launch_bounds__(256) void k_dw_adam(DwArgs a) {   // a.n_big_blocks
     dw_block_job<false, DwOvGate>(a, bx / per_net, bx % per_net, smem, nullptr, bx);
   } else {
     const int tb = bx - a.n_big_blocks, ntb = (int)gridDim.x - a.n_big_blocks;
-    // overlapped launches: the target step needs nothing of the launch this one waits for (the critics were stepped by this stream's previous launch, the targets' last
-    // readers are gone) - it runs while that launch is still busy; block 0 then waits and closes the update (Adam(log alpha), Philox counter, [IL_SYNC_MAIN_EPOCH])
-    const bool poisoned = a.sync && __syncthreads_or(sync_poisoned(reinterpret_cast<const long long*>(a.sync)) ? 1 : 0);   // (the tail still closes the update: counters and signals keep the pipeline moving until the host has seen the flag)
+    // (the tail still closes the update whatever the flag says: counters and signals keep the pipeline moving until the host has seen it)
     if (a.ov_stage) {
+      // overlapped launches: the target step needs nothing of the launch this one waits for (the critics were stepped by this stream's previous launch, the targets' last
+      // readers are gone) - it runs while that launch is still busy; block 0 then waits and closes the update (Adam(log alpha), Philox counter, [IL_SYNC_MAIN_EPOCH])
+      const bool poisoned = a.sync && __syncthreads_or(sync_poisoned(reinterpret_cast<const long long*>(a.sync)) ? 1 : 0);
       if (!poisoned) dw_tail_polyak(a, tb, ntb);
       if (tb == 0) { dw_ov_wait<true>(a); dw_tail_alpha<false>(a, nullptr, poisoned || sync_poisoned(reinterpret_cast<const long long*>(a.sync))); }
     } else {
-      if (tb == 0) dw_tail_alpha<false>(a, nullptr, poisoned);
-      if (!poisoned) dw_tail_polyak(a, tb, ntb);
+      // in-order launches: the flag rides with the requests of the two bodies instead of being a trip of its own in front of them
+      const long long* poison_at = reinterpret_cast<const long long*>(a.sync);
+      if (tb == 0) { if (poison_at) dw_tail_alpha<false, true>(a, nullptr, false, poison_at); else dw_tail_alpha<false>(a, nullptr); IL_TL(2, 3); }   // (slot 3: block 0's log-alpha step and end-of-update signal are out)
+      dw_tail_polyak(a, tb, ntb, poison_at);
     }
   }
   IL_TL_END(a.log_alpha ? 2 : 1);
@@ -2570,7 +2602,7 @@ __global__ __launch_bounds__(256) IL_POP_DW_ATTR void k_dw_adam_pop(const il_sac
       // (round 3) layers 1 and 3 with their biases as 32 x 32 LDS block jobs (dw_block32: whole-line staging instead of the wave-per-tile jobs' half-line gathers, which were
       // 72 % of this launch's line requests), bias 2 as wave jobs (dw_block64 does not fold it), then the tail. Grid: pop_dw_grid().
       const int nb32 = H / DWS, small = dw_block_jobs(a.in_dim, H, a.out_dim) - nb32 * nb32, sb = bx - nb64;
-      if (sb < small * a.n_nets) { dw_block_job(a, sb / small, nb32 * nb32 + sb % small, smem); IL_TLC(kind ? 11 : 10, 5); IL_TL_END(kind ? 11 : 10); return; }
+      if (sb < small * a.n_nets) { dw_block_job<false, DwNoGate, true>(a, sb / small, nb32 * nb32 + sb % small, smem); IL_TLC(kind ? 11 : 10, 5); IL_TL_END(kind ? 11 : 10); return; }
       const int bias_blocks = (H / 16 * a.n_nets + 3) / 4, bb = sb - small * a.n_nets;
       if (bb < bias_blocks) {
         const int job = bb * 4 + (int)(threadIdx.x >> 6);

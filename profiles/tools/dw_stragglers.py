@@ -22,6 +22,12 @@ for kid, name, per_net, nets_ in ((1, 'critic', 80, 2), (2, 'actor', 80, 1)):
   for k in ('HxH', 'W1', 'W3+b'):
     m = kind == k
     print(f'  {k:5s} n={m.sum():3d} start {np.median(start[m]):5.2f}  products done {np.median(prod[m]):5.2f}  done median {np.median(done[m]):5.2f} max {done[m].max():5.2f}')
+  tail = live & (np.arange(W) >= n)   # actor launch: the tail workgroups behind the block jobs (target step; block 0: the log-alpha step and the end-of-update signal)
+  if tail.any():
+    ts, td = (a[tail, 0] - t0) / 100.0, (a[tail, 7] - t0) / 100.0
+    alpha = f'{(a[n, 3] - t0) / 100.0:5.2f}' if a[n, 3] > 0 else '  n/a'   # slot 3: stamped by builds that have it
+    print(f'  tail  n={tail.sum():3d} start {np.median(ts):5.2f}  block 0: log alpha + signal out {alpha}, done {(a[n, 7] - t0) / 100.0:5.2f}  tail block done median {np.median(td):5.2f} max {td.max():5.2f}')
+    print(f'  launch ends on: {"a tail block" if td.max() > done.max() else "a block job"} (block jobs max {done.max():5.2f}, tail max {td.max():5.2f})')
   order = np.argsort(-done)[:10]
   print('  slowest:', [(int(j), kind[j], round(float(done[j]), 2), 'xcd %d' % (j % 8)) for j in order])
   for x in range(8):
