@@ -106,6 +106,10 @@ class GmmilLearner(C.Structure):   # il_gmmil_learner: one learner of il_gmmil_r
   _fields_ = [('policy', Batch), ('expert', Batch), ('gamma_1', C.c_float), ('gamma_2', C.c_float), ('workspace', C.c_void_p), ('out_rewards', C.c_void_p)]
 
 
+class PwilLearner(C.Structure):   # il_pwil_learner: one learner of il_pwil_act_reward_population (a device array of these)
+  _fields_ = [('d', Pwil), ('mailbox', C.c_void_p), ('carry', C.c_void_p)]
+
+
 class SampleArgs(C.Structure):
   _fields_ = [('state', C.c_void_p),
               ('ring_state_a', C.c_void_p), ('ring_a', C.c_void_p), ('capacity_a', C.c_int64), ('row_floats_a', C.c_int32), ('idx_a', C.c_void_p), ('rows_a', C.c_void_p),
@@ -237,6 +241,7 @@ _SIGNATURES = {
     'il_pwil_reward': (C.c_int, [C.POINTER(Pwil), _P, _P, _P, _P]),
     'il_pwil_couple_supported': (C.c_int32, [C.c_int32, C.c_double]),
     'il_pwil_act_reward': (C.c_int, [C.POINTER(Pwil), _P, _P, _P]),
+    'il_pwil_act_reward_population': (C.c_int, [_P, C.c_int32, C.POINTER(Pwil), _P]),
     'il_pwil_relabel_rows': (C.c_int, [C.POINTER(Pwil), _P, C.c_int64, C.c_int64, C.c_int64, _P]),
     'il_dril_numel': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'il_dril_workspace_floats': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),

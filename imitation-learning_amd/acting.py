@@ -20,7 +20,8 @@ Schedules:
 
 Population (`PopulationActingWorker`): L learners of one fused actor shape (a seed sweep in one process) step in lockstep through `il_act_step_population` - ONE launch
 of L workgroups and one wait for L echoes per act / append / step, instead of L launches and L turn-arounds. Every learner keeps its own mailbox, carry, ring, cursor,
-Philox seed and offset; a learner with nothing to do in a launch idles (it gets its echo, nothing else of it is touched).
+Philox seed and offset; a learner with nothing to do in a launch idles (it gets its echo, nothing else of it is touched). With `reward_models` (one PWILDiscriminator
+per learner) every launch that appends is preceded by ONE `il_pwil_act_reward_population` launch - the learner is a grid axis, so the L merges run side by side.
 
 PWIL (`ActingWorker(..., reward_model=PWILDiscriminator)`): the reward of a transition is the greedy coupling of its (state, action) against the expert atoms
 (models.py:216-249), which the per-function loop computes with a launch and a `.item()` per step. Here every launch that appends is preceded, on the same stream, by ONE
@@ -331,13 +332,21 @@ class PopulationActingWorker:
   (`il_act_step_population`: workgroup l = learner l's `il_act_step`). `act` / `append` / `step` are `ActingWorker`'s exact and fused schedules over lists (entry l belongs to
   learner l); a `None` entry makes that learner idle in the launch. Every learner's `actor._act_calls`, `memory.idx / full / num_trajectories`, ring and cursor end up
   where its own `ActingWorker(actor, memory, noise_seed=noise_seeds[l])` would have left them. Fused actor shapes only (depth 2, ReLU, hidden 64..256 in multiples of 64);
-  no mirror / overlap schedule and no PWIL reward model."""
+  no mirror / overlap schedule. `reward_models`: None, or one PWILDiscriminator per learner (each on its own atoms: the learners of a sweep subsample their expert data
+  under their own seeds) - `append` and `step` then post IL_ACT_REWARD_ON_DEVICE for every pending learner and enqueue `il_pwil_act_reward_population` directly ahead of
+  the acting launch; the `reward` argument never reaches the ring, and no `reset()` is issued at episode ends (the kernel does it), as in `ActingWorker(reward_model=...)`."""
 
   def __init__(self, actors, memories, noise_seeds, reward_models=None):
     actors, memories, noise_seeds = list(actors), list(memories), [int(s) for s in noise_seeds]
-    if reward_models is not None and any(r is not None for r in (reward_models if isinstance(reward_models, (list, tuple)) else [reward_models])):
-      raise NotImplementedError('PopulationActingWorker: no PWIL reward model (IL_ACT_REWARD_ON_DEVICE needs a coupling launch per learner in front of the append: one ActingWorker per learner)')
     L = len(actors)
+    if reward_models is not None:
+      reward_models = list(reward_models) if isinstance(reward_models, (list, tuple)) else [reward_models]
+      if all(r is None for r in reward_models): reward_models = None
+    if reward_models is not None:
+      if any(r is None for r in reward_models) or len(reward_models) != L:
+        raise ValueError(f'PopulationActingWorker(reward_models=...): None, or one PWILDiscriminator per learner ({L}) - a list that mixes None with discriminators, or of another length, is refused')
+      if not all(hasattr(r, 'require_device_coupling') for r in reward_models):
+        raise NotImplementedError('PopulationActingWorker(reward_models=...): a PWIL reward model (PWILDiscriminator: the one reward computed per environment step, by il_pwil_act_reward_population) per learner')
     assert L >= 1 and len(memories) == L and len(noise_seeds) == L, 'PopulationActingWorker: one memory and one noise seed per actor'
     a0, m0 = actors[0], memories[0]
     if any(getattr(a, 'general', False) for a in actors):
@@ -358,6 +367,18 @@ class PopulationActingWorker:
     self._descs = {id(box): self._descriptors(box, carry) for box, carry in ((self._act_box, self.carry), (self._append_box, self.carry), (self._eval_box, self.eval_carry))}
     self._absorbing = np.array([bool(m.absorbing) for m in memories])
     self._all = list(range(L))
+    self.reward_models = reward_models   # kept alive: the il_pwil_learner arrays below point into their atoms, weights and scratch
+    self._reward_flag = REWARD_ON_DEVICE if reward_models is not None else 0
+    if reward_models is not None:
+      r0 = reward_models[0]
+      for r in reward_models:
+        assert (r.state_size, r.action_size) == (self.S, self.A) and _lib.on_device(r.expert_atoms), 'PopulationActingWorker(reward_models=...): the discriminators live on the GPU and have the rings\' dims'
+        if (r.state_size, r.action_size, r.state_only, r.time_horizon) != (r0.state_size, r0.action_size, r0.state_only, r0.time_horizon):
+          raise ValueError('PopulationActingWorker(reward_models=...): one state_size, action_size, state_only and time_horizon for all learners (they differ in their seed, i.e. in their atoms, alone)')
+        r.require_device_coupling('PopulationActingWorker(reward_models=...)')   # NotImplementedError outside the one-launch coupling's sizes
+      self._pwil_shape = max(reward_models, key=lambda r: r.expert_atoms.size(0))._desc   # the largest learner's descriptor: checked on the host, sizes the grid
+      # one il_pwil_learner array per role; the act and the append mailboxes share the training carries. The evaluation mailboxes never post PENDING: no coupling
+      self._pwil_descs = {id(box): self._pwil_descriptors(box) for box in (self._act_box, self._append_box)}
 
   def _descriptors(self, box: _MailboxBlock, carry: torch.Tensor) -> torch.Tensor:
     """The il_act_learner array of one role, uploaded once (every pointer is stable for the life of the worker)."""
@@ -366,7 +387,17 @@ class PopulationActingWorker:
     return _device_array([_lib.ActLearner(a.flat.data_ptr(), base + l * stride, carry[l].data_ptr(), m.ring.data_ptr(), m._ring_state.data_ptr(), s & (2**64 - 1))
                           for l, (a, m, s) in enumerate(zip(self.actors, self.memories, self._seeds))], self.device)
 
-  def _launch(self, box: _MailboxBlock):
+  def _pwil_descriptors(self, box: _MailboxBlock) -> torch.Tensor:
+    """The il_pwil_learner array of one role: every learner's own coupling descriptor with its mailbox of `box` and its training carry."""
+    from .training import _device_array
+    base, stride = box.tensor.data_ptr(), box.floats * 4
+    return _device_array([_lib.PwilLearner(r._desc, base + l * stride, self.carry[l].data_ptr()) for l, r in enumerate(self.reward_models)], self.device)
+
+  def _launch(self, box: _MailboxBlock, appends: bool = False):
+    """`appends`: the launch may find pending transitions in `box` - with reward models their coupling launch goes first, on the same stream."""
+    if appends and self.reward_models is not None:
+      rc = _lib.lib().il_pwil_act_reward_population(_lib.ptr(self._pwil_descs[id(box)]), self.L, C.byref(self._pwil_shape), torch.cuda.current_stream().cuda_stream)
+      if rc: _lib.check(rc)
     rc = _lib.lib().il_act_step_population(_lib.ptr(self._descs[id(box)]), self.L, self.S, self.A, self.H, torch.cuda.current_stream().cuda_stream)
     if rc: _lib.check(rc)
 
@@ -411,7 +442,7 @@ class PopulationActingWorker:
     for l in rows:
       wrap[l] = self._absorbing[l] and bool(terminal[l]) and not bool(timeout[l])
     flags = np.zeros(self.L, dtype=np.int64)
-    flags[rows] = PENDING
+    flags[rows] = PENDING | self._reward_flag
     flags[wrap] |= WRAP_ABSORBING
     return rows, wrap, flags
 
@@ -429,14 +460,15 @@ class PopulationActingWorker:
 
   def append(self, step, next_obs, reward, terminal, timeout):
     """`memory_l.append(...)` of the (state, action) of learner l's last `act`, plus its absorbing wrap at a true termination. Asynchronous: nothing is waited for.
-    `step`: one int for all learners or a list; `next_obs[l] is None`: learner l idles."""
+    `step`: one int for all learners or a list; `next_obs[l] is None`: learner l idles. With reward models the ring's reward is the device's (`reward` is the caller's,
+    e.g. for its train_return), here and in `step`."""
     box = self._append_box
     if box.words is not None: box.wait('il_act_step_population(append)')   # normally already echoed: the act in between ran after it on the same stream
     rows, wrap, flags = self._transition_flags(next_obs, terminal, timeout)
     flags |= NO_ACTION
     self._post_transition(box, rows, step, next_obs, reward, terminal, timeout)
     box.commit(self._next_seq(), flags)
-    self._launch(box)
+    self._launch(box, appends=True)
     self._append_launched = True
     self._mirror_appends(rows, terminal, timeout, wrap)
 
@@ -455,7 +487,7 @@ class PopulationActingWorker:
     self._post_transition(box, rows, step, next_obs, reward, terminal, timeout)
     self._post_act(box, [None if next_obs[l] is None else (next_obs[l] if obs is None or obs[l] is None else obs[l]) for l in self._all], flags)
     box.commit(self._next_seq(), flags)
-    self._launch(box)
+    self._launch(box, appends=True)
     self._mirror_appends(rows, terminal, timeout, wrap)
     return self._collect(box)
 

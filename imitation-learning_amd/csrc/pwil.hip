@@ -396,13 +396,14 @@ __global__ __launch_bounds__(256) void k_pwil_merge(il_pwil d, int G, int K, con
 // The arrival hand-off of the one-launch kernels below: every workgroup calls it behind its candidate stores; true in the LAST workgroup to arrive, which may then read
 // every list. The candidates left with write-through stores: once every wave has drained its own (acknowledged by the memory side) and the workgroup has met, a RELAXED
 // ticket is enough - no release, i.e. no write-back of the XCD's L2 per workgroup; only the last arriver pays an acquire (an invalidate) before it reads the lists.
-__device__ __forceinline__ bool pwil_arrive_last(unsigned* __restrict__ ticket) {
+// `arrivals`: the workgroups that take this ticket - the whole grid of the one-learner kernels, one learner's row of chunks in k_pwil_couple_population.
+__device__ __forceinline__ bool pwil_arrive_last(unsigned* __restrict__ ticket, unsigned arrivals) {
   __shared__ unsigned last;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (threadIdx.x == 0) {
     const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last = t == gridDim.x - 1 ? 1u : 0u;
+    last = t == arrivals - 1 ? 1u : 0u;
     if (last) {
       __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch (stream-ordered behind this one), whatever the last arriver goes on to do
     }
@@ -418,7 +419,7 @@ __device__ __forceinline__ bool pwil_arrive_last(unsigned* __restrict__ ticket) 
 __global__ __launch_bounds__(PW_CHUNK) void k_pwil_step(il_pwil d, const float* __restrict__ state, const float* __restrict__ action, int K, PwCand* __restrict__ cand,
                                                         unsigned* __restrict__ ticket, float* __restrict__ out) {
   pwil_select_block<true>(d, state, action, K, cand);
-  if (!pwil_arrive_last(ticket)) return;
+  if (!pwil_arrive_last(ticket, gridDim.x)) return;
   pwil_merge_block(d, (int)gridDim.x, K, cand, out);
   IL_TL(1, 7);
 }
@@ -438,8 +439,18 @@ __global__ __launch_bounds__(PW_CHUNK) void k_pwil_step(il_pwil d, const float* 
 // one coupled it whole, else by the pair the host enqueues behind the post. After the merge of an episode's last transition the same workgroup sets every atom weight back
 // to 1 / N (k_pwil_reset's value): a reset() issued by the host at the episode end would run AHEAD of a coupling that rides in the update's graph. The arrival ticket ends
 // at zero whatever the gate says.
+//   population form (k_pwil_couple_population): the acting form for L learners in one launch, blockIdx.y = learner, blockIdx.x = chunk. Learner l's row of G_l =
+//                ceil(N_l / 256) workgroups runs pwil_couple_block on learner l's descriptor, lists, ticket, mailbox and carry - nothing is shared between rows, so every
+//                sentence above holds per row with G_l in place of the grid's width: G_l workgroups take the ticket, the last of THEM merges, and it compares G_l head stamps.
+//                The grid is as wide as the largest learner's row; a workgroup past its learner's last chunk returns before it touches anything of that learner, the ticket
+//                included, so the count the last arriver waits for is exactly G_l. An idle learner (IL_ACT_NO_ACTION without IL_ACT_PENDING, as il_act_step_population
+//                defines it) is no special case: its workgroups select for the word they read and stamp it like any other - idempotent, the lists mean nothing beyond the
+//                launch that wrote them -, take the ticket, and the gate fails in the last arriver because the word is not pending (or, had the host posted a pending word
+//                meanwhile, because the stamps differ): no weight, no carry word changes, and the ticket ends at zero. (Skipping the select for such a word would leave
+//                head stamps of an EARLIER launch under the gate's comparison; it is not done: no learner idles in a sweep's training loop.)
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(PW_CHUNK) void k_pwil_couple(il_pwil d, int K, PwCand* __restrict__ cand, unsigned* __restrict__ ticket, const float* mail, float* carry, float* row) {
+// G: the workgroups of this coupling (the chunks of d.n_atoms), all of which call this function; blockIdx.x is the chunk.
+__device__ __forceinline__ void pwil_couple_block(const il_pwil& d, int K, int G, PwCand* __restrict__ cand, unsigned* __restrict__ ticket, const float* mail, float* carry, float* row) {
   __shared__ unsigned go;
   const int tid = threadIdx.x, S = d.state_dim, A = d.action_dim;
   const float* state; const float* action; float* out; const float* ends;   // ends[0 .. 1]: terminal, timeout
@@ -456,21 +467,47 @@ __global__ __launch_bounds__(PW_CHUNK) void k_pwil_couple(il_pwil d, int K, PwCa
     state = row; action = row + S; out = row + 2 * S + A; ends = out + 1;
   }
   pwil_select_block<true>(d, state, action, K, cand, commit);
-  if (!pwil_arrive_last(ticket)) return;
+  if (!pwil_arrive_last(ticket, (unsigned)G)) return;
   if (mail) {
     if (tid == 0) go = act_pending(word, carry, S, A) ? 1u : 0u;
     __syncthreads();
-    for (int g = tid; g < (int)gridDim.x; g += PW_CHUNK) if (cand[(size_t)g * K].pad != commit) go = 0u;   // (rank 0 of every chunk is always written)
+    for (int g = tid; g < G; g += PW_CHUNK) if (cand[(size_t)g * K].pad != commit) go = 0u;   // (rank 0 of every chunk is always written)
     __syncthreads();
     if (!go) return;   // workgroup-uniform
   }
   const bool episode_end = ends[0] != 0.f || ends[1] != 0.f;   // (requested ahead of the merge: the acting form reads it from host memory)
-  pwil_merge_block(d, (int)gridDim.x, K, cand, out);   // ends behind a barrier: wave 0's weight stores precede the reset below
+  pwil_merge_block(d, G, K, cand, out);   // ends behind a barrier: wave 0's weight stores precede the reset below
   if (episode_end) {
     const float w = (float)(1.0 / (double)d.n_atoms);
     for (int i = tid; i < d.n_atoms; i += PW_CHUNK) d.weights[i] = w;
   }
   if (mail && tid == 0) carry[act_carry_coupled(S, A)] = __uint_as_float(word);   // what the reward slot holds the reward of: the append stores it for this post only
+}
+__global__ __launch_bounds__(PW_CHUNK) void k_pwil_couple(il_pwil d, int K, PwCand* __restrict__ cand, unsigned* __restrict__ ticket, const float* mail, float* carry, float* row) {
+  pwil_couple_block(d, K, (int)gridDim.x, cand, ticket, mail, carry, row);
+}
+
+// il_pwil_scratch_floats and the places of a learner's candidate lists and ticket inside its scratch, for the host's entry points and for k_pwil_couple_population, which
+// derives them from each learner's own descriptor (the learners of a sweep subsample their expert data under their own seeds: their atom counts differ)
+__host__ __device__ inline int pwil_take_of(int n_atoms, double agent_weight) { return (int)ceil(agent_weight * (double)n_atoms) + 2; }   // most atoms one step can consume
+__host__ __device__ inline int pwil_chunks_of(int n_atoms) { return (int)(((long long)n_atoms + PW_CHUNK - 1) / PW_CHUNK); }
+__host__ __device__ inline long long pwil_scratch_floats_of(int n_atoms, double agent_weight) {
+  const int m = pwil_take_of(n_atoms, agent_weight), K = m < PW_CHUNK ? m : PW_CHUNK;
+  const long long lists = (long long)pwil_chunks_of(n_atoms) * K * 4;
+  return (lists > n_atoms ? lists : n_atoms) + 4;   // + one 16-byte slot behind everything: k_pwil_step's arrival counter
+}
+__host__ __device__ inline unsigned* pwil_ticket_of(const il_pwil& d) { return reinterpret_cast<unsigned*>(d.dists + pwil_scratch_floats_of(d.n_atoms, d.agent_weight) - 4); }
+
+// The acting form for a population (include/il_hip.h il_pwil_act_reward_population): grid (chunks of the largest learner, learners). See the comment above
+// pwil_couple_block; nobody waits, and a row narrower than the grid leaves its surplus workgroups with nothing to do.
+__global__ __launch_bounds__(PW_CHUNK) void k_pwil_couple_population(const il_pwil_learner* __restrict__ learners) {
+  const il_pwil_learner& ln = learners[blockIdx.y];
+  const il_pwil d = ln.d;
+  const int G = pwil_chunks_of(d.n_atoms);
+  // workgroup-uniform, ahead of every access to this learner's memory: its ticket counts G arrivals. A learner wider than the grid (more atoms than shape_host: the caller's
+  // error) is not coupled at all rather than left with a ticket that never completes: its post stays uncoupled, and the appending launch leaves such a post alone
+  if ((int)blockIdx.x >= G || G > (int)gridDim.x) return;
+  pwil_couple_block(d, pwil_take_of(d.n_atoms, d.agent_weight), G, reinterpret_cast<PwCand*>(d.dists), pwil_ticket_of(d), ln.mailbox, ln.carry, nullptr);
 }
 
 __global__ __launch_bounds__(256) void k_pwil_merge_serial(il_pwil d, int G, int K, const PwCand* __restrict__ cand, float* __restrict__ out) {
@@ -484,16 +521,9 @@ __global__ __launch_bounds__(256) void k_pwil_merge_serial(il_pwil d, int G, int
   else pwil_merge_wave(d, G, K, cand, out);
 }
 
-static int pwil_take(const il_pwil* d) { return (int)ceil(d->agent_weight * (double)d->n_atoms) + 2; }   // most atoms one step can consume
-extern "C" int64_t il_pwil_scratch_floats(int32_t n_atoms, double agent_weight) {
-  const int m = (int)ceil(agent_weight * (double)n_atoms) + 2, K = m < PW_CHUNK ? m : PW_CHUNK;
-  const int64_t lists = ((int64_t)n_atoms + PW_CHUNK - 1) / PW_CHUNK * K * 4;
-  return (lists > n_atoms ? lists : n_atoms) + 4;   // + one 16-byte slot behind everything: k_pwil_step's arrival counter
-}
-static unsigned* pwil_ticket(const il_pwil* d) {
-  const int64_t n = il_pwil_scratch_floats(d->n_atoms, d->agent_weight);
-  return reinterpret_cast<unsigned*>(d->dists + n - 4);
-}
+static int pwil_take(const il_pwil* d) { return pwil_take_of(d->n_atoms, d->agent_weight); }
+extern "C" int64_t il_pwil_scratch_floats(int32_t n_atoms, double agent_weight) { return (int64_t)pwil_scratch_floats_of(n_atoms, agent_weight); }
+static unsigned* pwil_ticket(const il_pwil* d) { return pwil_ticket_of(*d); }
 
 extern "C" int il_pwil_reset(const il_pwil* d, il_stream_t stream_) {
   IL_CHECK_ARG(d && d->weights && d->n_atoms > 0, "il_pwil_reset: bad arguments");
@@ -550,6 +580,16 @@ extern "C" int il_pwil_act_reward(const il_pwil* d, const float* mailbox, float*
   { IL_TRACE("k_pwil_couple", (hipStream_t)stream_);
     k_pwil_couple<<<ceil_div(d->n_atoms, PW_CHUNK), PW_CHUNK, 0, (hipStream_t)stream_>>>(*d, pwil_take(d), reinterpret_cast<PwCand*>(d->dists), pwil_ticket(d), mailbox, carry, nullptr); }
   IL_CHECK_LAUNCH("il_pwil_act_reward");
+  return IL_OK;
+}
+
+extern "C" int il_pwil_act_reward_population(const il_pwil_learner* learners, int32_t n_learners, const il_pwil* shape_host, il_stream_t stream_) {
+  IL_CHECK_ARG(learners && shape_host, "il_pwil_act_reward_population: null learners / shape_host");
+  IL_CHECK_ARG(n_learners >= 1 && n_learners <= 65535, "il_pwil_act_reward_population: n_learners=%d outside [1, 65535] (the learner is the grid's y axis)", n_learners);
+  if (int rc = pwil_couple_check(shape_host, "il_pwil_act_reward_population")) return rc;   // m and the chunk count grow with n_atoms: the largest learner's check covers the others
+  { IL_TRACE("k_pwil_couple_population", (hipStream_t)stream_);
+    k_pwil_couple_population<<<dim3((unsigned)ceil_div(shape_host->n_atoms, PW_CHUNK), (unsigned)n_learners), PW_CHUNK, 0, (hipStream_t)stream_>>>(learners); }
+  IL_CHECK_LAUNCH("il_pwil_act_reward_population");
   return IL_OK;
 }
 

@@ -396,8 +396,10 @@ class UpdatePlan:
   def __init__(self, algorithm: str, actor, critic, log_alpha, target_critic, memory: ReplayMemory, actor_optimiser, critic_optimiser, temperature_optimiser,
                batch_size: int, discount: float, entropy_target: float, polyak_factor: float, expert_memory: Optional[ReplayMemory] = None, discriminator=None,
                discriminator_optimiser=None, imitation_cfg=None, device_index_draw: bool = True, overlap: bool = True, learner_id=None, mix_expert: bool = False,
-               bc_aux: bool = False):
+               bc_aux: bool = False, noise_seed_offset: Optional[int] = None):
     """`learner_id`: give this plan private scratch / noise / index-stream state so that several plans can run concurrently (`PopulationPlan`).
+    `noise_seed_offset`: what is added to the process seed for this plan's Philox key (default: 0 without a learner_id, else 7919 * (learner_id + 1), which keeps learners
+    built under ONE seed apart; a sweep's PWIL learners are built under their own seeds and pass 0: the key `train()` gives that seed).
     `mix_expert`: imitation.mix_expert_data == 'mixed_batch' (DRIL / GMMIL / RED); `bc_aux`: imitation.bc_aux_loss (train.py:201)."""
     assert algorithm in self.ALGORITHMS, f'UpdatePlan: unknown algorithm {algorithm}'
     # reinforcement.actor / critic outside the fused kernels' shape (models._mlp_shape: any depth 1-8, relu / tanh / sigmoid, hidden <= 2048, wide action spaces): the same plan
@@ -420,6 +422,7 @@ class UpdatePlan:
     self.transitions = batch_views(self.rows, memory.state_size, memory.action_size, memory.absorbing)
     self.logp, self.q = torch.empty(batch_size, device=dev), torch.empty(batch_size, device=dev)
     tag, off = learner_id, (0 if learner_id is None else 7919 * (int(learner_id) + 1))
+    if noise_seed_offset is not None: off = int(noise_seed_offset)
     self.sac = sac_descriptor(actor, critic, log_alpha, target_critic, batch_size, actor_optimiser, critic_optimiser, temperature_optimiser, discount, entropy_target, polyak_factor,
                               tag=tag, seed_offset=off)
     self.sac.out_logp, self.sac.out_q = self.logp.data_ptr(), self.q.data_ptr()
@@ -1436,7 +1439,8 @@ class BatchedPopulationPlan:
   networks, optimiser state, scratch and Philox counter (build the `UpdatePlan`s with distinct `learner_id`s).  SAC, GAIL (`il_gail_step_population`: discriminator step +
   relabel), DRIL (`il_dril_reward_population`: every learner's Monte-Carlo-dropout reward under its own ensemble, threshold, Philox key and counter; with `bc_aux` also
   `il_bc_step_population`, the behavioural-cloning auxiliary step of every actor on its own expert batch, in front of the forward kernels), RED (`il_red_reward_population`: every learner's eval-mode reward under its own predictor, target and sigma_1) and GMMIL (`il_gmmil_reward_population`: every
-  learner's kernel-mean-embedding reward on its own batches, under its own frozen bandwidths, with its own workspace) learners; GAIL's, DRIL's, RED's and GMMIL's reward launches run
+  learner's kernel-mean-embedding reward on its own batches, under its own frozen bandwidths, with its own workspace) learners, and PWIL learners, whose update is SAC's (no
+  reward step: the acting side stores the coupling reward with every transition); GAIL's, DRIL's, RED's and GMMIL's reward launches run
   on a second stream beside the reward-independent forward kernels (IL_POP_OVERLAP=0: in stream order).  GMMIL: the FIRST run() is eager - every learner fixes its
   bandwidths from its first batch on the host (models.py:193-195), one read per learner, once - and cannot be captured; from the second on an update is the same launches
   as for the others."""
@@ -1458,7 +1462,9 @@ class BatchedPopulationPlan:
     for p in self.plans:
       p._set_device_sync(False)   # one stream, one set of launches for all learners: plain stream order
     p0 = self.plans[0]
-    assert all(p.algorithm == p0.algorithm and p.B == p0.B for p in self.plans) and p0.algorithm in ('SAC', 'GAIL', 'RED', 'GMMIL', 'DRIL'), 'the population launches exist for SAC, GAIL, RED, GMMIL and DRIL learners of one batch size'
+    assert all(p.algorithm == p0.algorithm and p.B == p0.B for p in self.plans) and p0.algorithm in ('SAC', 'GAIL', 'RED', 'GMMIL', 'DRIL', 'PWIL'), 'the population launches exist for SAC, GAIL, RED, GMMIL, DRIL and PWIL learners of one batch size'
+    if p0.algorithm == 'PWIL':   # a SAC update: PWIL's reward is stored with every transition, by the acting side (PopulationActingWorker(reward_models=...): il_pwil_act_reward_population)
+      assert not any(p.mix_expert or p.bc_aux for p in self.plans), 'BatchedPopulationPlan(PWIL): mixed batches / the BC auxiliary step have no population launches'
     if p0.algorithm == 'RED':
       shape = lambda r: (r.state_dim, r.action_dim, r.hidden, r.depth, r.activation, r.state_only, r.batch)   # what sizes il_red_reward_population's tile and grid
       assert all(shape(p.red) == shape(p0.red) for p in self.plans), 'BatchedPopulationPlan(RED): the discriminators of one population share dims, hidden, depth, activation, state_only and batch'

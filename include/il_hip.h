@@ -416,8 +416,9 @@ int il_act_step(const float* actor, int32_t state_dim, int32_t action_dim, int32
 /* il_act_step for n_learners learners of one shape in ONE launch (a seed sweep in one process): workgroup l runs il_act_step's contract for learners[l] (a DEVICE array).
  * Every learner has its own mailbox (pinned host memory), carry, ring, cursor and Philox seed; its Philox offset travels in word [6] of its mailbox, because the
  * learners' offsets drift apart (evaluation episodes of different lengths share the counter). A learner whose post carries IL_ACT_NO_ACTION and no IL_ACT_PENDING is
- * idle in this launch: it gets its echo and nothing else of it is written. Shape limits: il_act_step's. No mirror form; IL_ACT_REWARD_ON_DEVICE posts are
- * the caller's to refuse (no coupling launch precedes this one). */
+ * idle in this launch: it gets its echo and nothing else of it is written. Shape limits: il_act_step's. No mirror form. An IL_ACT_REWARD_ON_DEVICE post is
+ * valid when il_pwil_act_reward_population for the same mailboxes and carries precedes this launch on the stream (a pending post with that flag that no coupling has
+ * coupled is left alone, as in il_act_step: no row, no action, no echo). */
 typedef struct il_act_learner {
   const float* actor; float* mailbox; float* carry; float* ring; int64_t* ring_state; uint64_t noise_seed;
 } il_act_learner;
@@ -665,6 +666,17 @@ int32_t il_pwil_couple_supported(int32_t n_atoms, double agent_weight);
  * what hands the mailbox back to the host, so the mailbox words read here cannot change under a launch that was enqueued for them; and it is the launch that moves
  * carry[S + A], so this one always sees the post as pending. */
 int il_pwil_act_reward(const il_pwil* d, const float* mailbox, float* carry, il_stream_t stream);
+/* il_pwil_act_reward for n_learners learners in ONE launch (a seed sweep in one process: the coupling in front of il_act_step_population). Grid (chunk, learner): row l
+ * runs il_pwil_act_reward's contract - the same select, arrival ticket, gate, merge and episode-end reset, hence the same reward, atom weights and carry words bit for
+ * bit - for learners[l] (a DEVICE array), whose descriptor is its own: the learners of a sweep subsample their expert data under their own seeds, so n_atoms, atoms,
+ * weights, scale, offset and the scratch (>= il_pwil_scratch_floats(d.n_atoms, d.agent_weight) floats, zeroed ticket in its last 16 bytes: il_pwil_reset) differ, and
+ * the chunk count and the candidates per chunk are derived on the device from each descriptor. shape_host: a complete descriptor on the HOST with the LARGEST n_atoms of
+ * the population (the largest learner's own), checked like il_pwil_act_reward's - its limits grow with n_atoms, so it covers the others - and sizing the grid; dim,
+ * state_dim, action_dim and agent_weight are the population's. No learner's n_atoms may exceed shape_host's (a learner with more chunks than the grid is wide is not coupled at all: its post stays uncoupled, which the appending launch leaves alone). A learner that idles in il_act_step_population's sense
+ * (IL_ACT_NO_ACTION without IL_ACT_PENDING) keeps its weights and carry, and every learner's ticket ends at zero. 1 <= n_learners <= 65535. Ordering contract:
+ * il_pwil_act_reward's, with il_act_step_population as the appending launch. */
+typedef struct il_pwil_learner { il_pwil d; const float* mailbox; float* carry; } il_pwil_learner;
+int il_pwil_act_reward_population(const il_pwil_learner* learners /* device */, int32_t n_learners, const il_pwil* shape_host, il_stream_t stream);
 /* train.py:135-141 as one call: `count` coupling launches on `stream`, launch i reading state | action from ring row first + i (rows of
  * il_ring_row_floats(state_dim, action_dim) floats), writing the reward into that row's reward column and - when the row's terminals or timeouts column is non-zero -
  * setting the weights back to 1 / N after its merge. No host read and no synchronisation between rows. 0 <= first, first + count <= capacity; count = 0 launches nothing. */
@@ -871,7 +883,7 @@ int il_red_epoch_steps(const il_red* d, const il_batch* ring, const float* mask_
                        uint32_t flags, const il_epoch* epoch, int32_t steps, il_stream_t stream);
 
 /* sizeof() of the descriptor structs in this build (0 il_batch, 1 il_adam, 2 il_sac, 3 il_disc, 4 il_pwil, 5 il_sample_args, 6 il_red,
- * 7 il_dril, 8 il_disc_shaped, 9 il_disc_deep, 10 il_peer_bucket, 11 il_disc_shaped_deep, 12 il_epoch, 13 il_act_learner, 14 il_gmmil_learner; -1 otherwise): lets a binding verify its own struct definitions. */
+ * 7 il_dril, 8 il_disc_shaped, 9 il_disc_deep, 10 il_peer_bucket, 11 il_disc_shaped_deep, 12 il_epoch, 13 il_act_learner, 14 il_gmmil_learner, 15 il_pwil_learner; -1 otherwise): lets a binding verify its own struct definitions. */
 int32_t il_struct_size(int32_t which);
 
 #ifdef __cplusplus

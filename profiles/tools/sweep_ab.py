@@ -9,7 +9,9 @@
   python profiles/tools/sweep_ab.py [--steps 4000] [--repeats 5] [--learners 4 16] [--algorithms GAIL SAC] [--out profiles/sweep_ab.txt]
 (--algorithms RED: the same three forms with the predictor's pretraining cut to 100 iterations per learner; --algorithms GMMIL: at batch 128, the batch of every shipped GMMIL
 configuration, where one reward launch is 16 workgroups; --algorithms DRIL: the shipped configuration, i.e. with imitation.bc_aux_loss - il_dril_reward_population and
-il_bc_step_population per update - and the ensemble's pretraining cut to 100 iterations per learner)"""
+il_bc_step_population per update - and the ensemble's pretraining cut to 100 iterations per learner; --algorithms PWIL: with the opt-in key +sweep.pwil_population=true,
+every learner on its own 6,006 atoms - six trajectories of 1,000 steps and their absorbing rows - at horizon 1,000: 24 chunks of 8 candidates per learner, one
+il_pwil_act_reward_population launch per lockstep step under (c) against one il_pwil_act_reward launch per learner under (b); (a) couples per step as train() does)"""
 import argparse
 import os
 import sys
@@ -39,6 +41,7 @@ def say(text):
 
 def overrides(algorithm, steps, start):
   extra = ['imitation.pretraining.iterations=100'] if algorithm in ('RED', 'DRIL') else []   # (the predictor's / ensemble's pretraining sits in front of the clock: kept short, the job measures the loop)
+  if algorithm == 'PWIL': extra = [train.PWIL_POPULATION_KEY]   # PWIL sweeps form a population on opt-in only; train() ignores the key
   batch = 128 if algorithm == 'GMMIL' else 256
   return [f'algorithm={algorithm}', 'env=halfcheetah', f'steps={steps}', f'training.start={start}', f'training.batch_size={batch}', 'check_time_usage=true', 'logging.interval=1000',
           '+synthetic_env.dataset_trajectories=6'] + extra

@@ -11,7 +11,8 @@ the row-by-row loop.
 
 Sweeps:  python train.py -m seed=1,2,3 algorithm=GAIL env=halfcheetah  (Hydra's multirun: comma lists, Cartesian product, outputs/<algorithm>_<env>_sweeper/<time>/<job>/).
 Jobs that differ only in their seed train as ONE population in lockstep (`train_sweep`: `il.BatchedPopulationPlan` for the update, `il.PopulationActingWorker` or one
-`il.ActingWorker` per learner for acting: `+sweep.schedule=population|per_learner`, the same bits either way; GMMIL and DRIL sweeps only when that key is given); every other sweep runs its jobs one after another, and says so.
+`il.ActingWorker` per learner for acting: `+sweep.schedule=population|per_learner`, the same bits either way; GMMIL and DRIL sweeps only when that key is given, PWIL sweeps only under `+sweep.pwil_population=true`:
+one `il_pwil_act_reward_population` coupling launch per lockstep step in front of the population acting launch); every other sweep runs its jobs one after another, and says so.
 """
 import os
 import sys
@@ -405,6 +406,25 @@ def sweep_schedule(cfg) -> str:
   return schedule
 
 
+PWIL_POPULATION_KEY = '+sweep.pwil_population=true'   # the opt-in of PWIL sweeps (`+sweep.schedule` alone keeps them job after job)
+
+
+def pwil_population(cfg) -> bool:
+  return bool((cfg.get('sweep', {}) or {}).get('pwil_population', False))
+
+
+def pwil_atoms_upper_bound(cfg) -> tuple:
+  """(most atoms a learner of this configuration can hold, horizon): kept trajectories x ceil(horizon / subsample) rows, plus - with absorbing states - the appended
+  absorbing row and the two rows the subsampling always keeps (environments.dataset_to_memory). imitation.trajectories=0 keeps the whole dataset: counted as the synthetic
+  stand-in's (+synthetic_env.dataset_trajectories, default 30); a larger real dataset is refused by the worker when it is built."""
+  env_kw = dict(cfg.get('synthetic_env', {}) or {})
+  horizon = int(env_kw.get('max_episode_steps', 1000))
+  kept = int(cfg.imitation.trajectories) or int(env_kw.get('dataset_trajectories', 30))
+  sub, absorbing = int(cfg.imitation.subsample), bool(cfg.imitation.absorbing)
+  per_trajectory = -(-(horizon + int(absorbing)) // sub) + (2 if absorbing and sub > 1 else 0)
+  return kept * per_trajectory, horizon
+
+
 def _fused_shape(model_cfg) -> bool:
   return int(model_cfg.depth) == 2 and str(model_cfg.activation) == 'relu' and int(model_cfg.hidden_size) % 64 == 0 and 64 <= int(model_cfg.hidden_size) <= 256
 
@@ -413,10 +433,12 @@ def sweep_fallback_reason(cfg):
   """None when a seed sweep of this configuration can train as one population (what il.BatchedPopulationPlan and il.PopulationActingWorker take); otherwise the reason
   its jobs run one after another through train()."""
   explicit = (cfg.get('sweep', {}) or {}).get('schedule') is not None
-  if cfg.algorithm not in ('SAC', 'GAIL', 'RED', 'GMMIL') and not (cfg.algorithm == 'DRIL' and explicit):
+  if cfg.algorithm not in ('SAC', 'GAIL', 'RED', 'GMMIL') and not (cfg.algorithm == 'DRIL' and explicit) and not (cfg.algorithm == 'PWIL' and pwil_population(cfg)):
     reason = f'algorithm={cfg.algorithm} has no population launches (SAC, GAIL and RED have), and GMMIL under an explicit +sweep.schedule'
     if cfg.algorithm == 'DRIL':   # opt-in, as for GMMIL: a DRIL sweep without the key runs as it always has
       reason += f'; DRIL trains as one population (il_dril_reward_population, il_bc_step_population) only when +sweep.schedule={"|".join(SWEEP_SCHEDULES)} is given'
+    if cfg.algorithm == 'PWIL':   # opt-in by a key of its own: a PWIL sweep without it, with or without +sweep.schedule, runs as it always has
+      reason += f'; PWIL trains as one population (il_pwil_act_reward_population: one coupling launch per lockstep step) only when {PWIL_POPULATION_KEY} is given'
     return reason
   if cfg.algorithm == 'GMMIL' and (cfg.get('sweep', {}) or {}).get('schedule') is None:
     # opt-in: a GMMIL sweep without the key runs as it always has; with it, its first update is eager (every learner's bandwidths) and the rest are population launches
@@ -428,7 +450,8 @@ def sweep_fallback_reason(cfg):
   if cfg.training.batch_size % 16 != 0:
     return f'training.batch_size={cfg.training.batch_size} is not a multiple of 16'
   # RED, GMMIL and DRIL with prefill_memory: the expert rows are moved into the agent ring once, in front of the loop (train.py:134, 192); nothing is edited between the launches
-  if cfg.imitation.mix_expert_data != 'none' and not (cfg.algorithm in ('RED', 'GMMIL', 'DRIL') and cfg.imitation.mix_expert_data == 'prefill_memory'):
+  # PWIL with prefill_memory: each learner relabels its expert memory on the device and moves it into its ring, once, in front of the loop (train.py:135-141, 192)
+  if cfg.imitation.mix_expert_data != 'none' and not (cfg.algorithm in ('RED', 'GMMIL', 'DRIL', 'PWIL') and cfg.imitation.mix_expert_data == 'prefill_memory'):
     return f'imitation.mix_expert_data={cfg.imitation.mix_expert_data} edits the batches between the launches'
   if cfg.imitation.bc_aux_loss and cfg.algorithm != 'DRIL':   # DRIL (every shipped configuration sets it): il_bc_step_population in front of the forward launches
     return 'imitation.bc_aux_loss adds an actor step per update that the population launches do not have'
@@ -437,6 +460,12 @@ def sweep_fallback_reason(cfg):
   acting = (cfg.get('acting', {}) or {}).get('schedule', 'exact')
   if acting not in ('exact', 'fused'):
     return f'+acting.schedule={acting}: the population acting launch has the exact and the fused schedule'
+  if cfg.algorithm == 'PWIL':
+    n, horizon = pwil_atoms_upper_bound(cfg)
+    m, chunks = int(np.ceil((1 / horizon - 1e-6) * n)) + 2, -(-n // 256)
+    if m > 256 or chunks * m > 4096:
+      return (f'PWIL with up to {n} atoms at horizon {horizon} lies outside the one-launch coupling il_pwil_act_reward_population runs per learner: it needs m = ceil(N / T) + 2 <= 256 '
+              f'consumable atoms per step and ceil(N / 256) * m <= 4096 candidates (here m = {m}, {chunks} chunks)')
   if cfg.algorithm == 'GMMIL':
     S, A = env_dims(cfg.env, cfg.imitation.absorbing)
     D = S + (0 if cfg.imitation.state_only else A)
@@ -497,7 +526,7 @@ def train_sweep(cfgs, prefixes):
   """The loop of train() in lockstep over L learners that differ only in their seed: per lockstep step ONE population act launch, L host environment steps and ONE
   append launch (`+acting.schedule=fused`: one launch for both); on update steps ONE population update (il.BatchedPopulationPlan); on evaluation steps
   evaluate_population. Every learner has its own seeds, index stream, environments, rings, networks, optimisers and `learner_id`; job l writes what a single run writes
-  under prefixes[l] (GAIL, RED and DRIL: with a discriminator.pth; GMMIL, as in train(): without one - its bandwidths are fixed by each learner's first batch, in the first, eager,
+  under prefixes[l] (GAIL, RED and DRIL: with a discriminator.pth; PWIL and GMMIL, as in train(): without one - its bandwidths are fixed by each learner's first batch, in the first, eager,
   update, and live in no file). Returns the mean normalised score per job."""
   L = len(cfgs)
   assert L >= 1 and len(prefixes) == L
@@ -543,6 +572,8 @@ def train_sweep(cfgs, prefixes):
     elif cfg.algorithm == 'DRIL':   # the dropout policy ensemble (train.py:73)
       ln.discriminator = il.DropoutSoftActor(S, A, cfg.imitation.discriminator)
       ln.discriminator_optimiser = il.AdamW(ln.discriminator, lr=cfg.imitation.learning_rate, weight_decay=cfg.imitation.weight_decay)
+    elif cfg.algorithm == 'PWIL':   # this learner's own atoms: its expert data was subsampled under its seed
+      ln.discriminator = il.PWILDiscriminator(S, A, cfg.imitation, ln.expert_memory, ln.env.max_episode_steps)
     ln.metrics = dict(train_steps=[], train_returns=[], test_steps=[], test_returns=[], test_returns_normalized=[], update_steps=[], predicted_rewards=[], alphas=[], entropies=[], Q_values=[])
     ln.score = []
     start_time += time.time() - built
@@ -573,23 +604,35 @@ def train_sweep(cfgs, prefixes):
         start_time += ln.metrics['pre_training_time']
       if cfg.imitation.mix_expert_data == 'prefill_memory': ln.memory.transfer_transitions(ln.expert_memory)
     if cfg.algorithm == 'GMMIL' and cfg.imitation.mix_expert_data == 'prefill_memory': ln.memory.transfer_transitions(ln.expert_memory)   # train.py:192, once, in front of the loop
+    if cfg.algorithm == 'PWIL' and cfg.imitation.mix_expert_data == 'prefill_memory':   # train.py:135-141, 192 as train() runs them: the relabel on the device (or row by row), then the prefill
+      if pretraining_schedule(cfg) == 'plan':
+        ln.discriminator.relabel_memory(ln.expert_memory)   # (sweep_fallback_reason has bounded the atoms: inside the one-launch coupling)
+      else:
+        for r in range(ln.expert_memory.size):
+          tr = ln.expert_memory[r]
+          ln.expert_memory.rewards[r] = ln.discriminator.compute_reward(tr['states'].unsqueeze(0), tr['actions'].unsqueeze(0))
+          if tr['terminals'] or tr['timeouts']: ln.discriminator.reset()
+      ln.memory.transfer_transitions(ln.expert_memory)
     ln.plan = il.UpdatePlan(cfg.algorithm, ln.actor, ln.critic, ln.log_alpha, ln.target_critic, ln.memory, ln.actor_optimiser, ln.critic_optimiser, ln.temperature_optimiser, B,
                             cfg.reinforcement.discount, entropy_target, cfg.reinforcement.polyak_factor, expert_memory=ln.expert_memory, discriminator=ln.discriminator,
                             discriminator_optimiser=ln.discriminator_optimiser, imitation_cfg=cfg.imitation if cfg.algorithm == 'GAIL' else None, overlap=False, learner_id=i,
-                            bc_aux=bool(cfg.imitation.bc_aux_loss))   # (sweep_fallback_reason: set for DRIL learners only)
+                            bc_aux=bool(cfg.imitation.bc_aux_loss),   # (sweep_fallback_reason: set for DRIL learners only)
+                            noise_seed_offset=0 if cfg.algorithm == 'PWIL' else None)   # PWIL jobs train as train() trains them, bit for bit: its Philox key for this learner's seed
     ln.plan.main_feeds_ring = True
     ln.plan.watch_timeouts()
-    if ln.discriminator is not None and cfg.algorithm != 'DRIL': ln.discriminator.eval()   # train.py:147 (the DRIL ensemble keeps its dropout, i.e. train mode, on purpose)
+    if ln.discriminator is not None and cfg.algorithm not in ('DRIL', 'PWIL'): ln.discriminator.eval()   # train.py:147 (the DRIL ensemble keeps its dropout, i.e. train mode, on purpose)
     learners.append(ln)
   plans = [ln.plan for ln in learners]
 
   if how == 'population':
     pop = il.BatchedPopulationPlan(plans)
-    worker = il.PopulationActingWorker([ln.actor for ln in learners], [ln.memory for ln in learners], [ln.cfg.seed for ln in learners])
+    # PWIL: every learner's coupling in ONE launch ahead of the population acting launch; the rewards are stored from the device, and the kernel resets the atom weights at episode ends
+    worker = il.PopulationActingWorker([ln.actor for ln in learners], [ln.memory for ln in learners], [ln.cfg.seed for ln in learners],
+                                       reward_models=[ln.discriminator for ln in learners] if cfg0.algorithm == 'PWIL' else None)
     update = pop.run
   else:
     pop, worker = None, None
-    workers = [il.ActingWorker(ln.actor, ln.memory, noise_seed=ln.cfg.seed) for ln in learners]
+    workers = [il.ActingWorker(ln.actor, ln.memory, noise_seed=ln.cfg.seed, reward_model=ln.discriminator if cfg0.algorithm == 'PWIL' else None) for ln in learners]
     def update():
       for p in plans: p.run()
 
