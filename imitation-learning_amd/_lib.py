@@ -110,6 +110,10 @@ class PwilLearner(C.Structure):   # il_pwil_learner: one learner of il_pwil_act_
   _fields_ = [('d', Pwil), ('mailbox', C.c_void_p), ('carry', C.c_void_p)]
 
 
+class MixLearner(C.Structure):   # il_mix_learner: one learner of il_batch_mix_relabel_population (a device array of these; 32 bytes)
+  _fields_ = [('rows', C.c_void_p), ('expert_rows', C.c_void_p), ('dyn', C.c_void_p), ('reward_expert', C.c_float)]
+
+
 class SampleArgs(C.Structure):
   _fields_ = [('state', C.c_void_p),
               ('ring_state_a', C.c_void_p), ('ring_a', C.c_void_p), ('capacity_a', C.c_int64), ('row_floats_a', C.c_int32), ('idx_a', C.c_void_p), ('rows_a', C.c_void_p),
@@ -196,6 +200,7 @@ _SIGNATURES = {
     'il_actor_act': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_uint64, C.c_uint32, C.c_int32, _P, _P, _P]),
     'il_batch_mix_relabel': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_float, C.c_int64, _P]),
     'il_batch_mix_relabel_dyn': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P]),
+    'il_batch_mix_relabel_population': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     'il_act_mailbox_floats': (C.c_int32, [C.c_int32, C.c_int32]),
     'il_act_step': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, C.c_int64, _P]),
     'il_act_step_population': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),

@@ -117,6 +117,76 @@ extern "C" int il_batch_mix_relabel_dyn(float* rows, const float* expert_rows, i
   return IL_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The same step for the L learners of a seed sweep in ONE launch, grid (strip, learner): il_batch_mix_relabel_dyn's effect per learner, bit for bit. The learner's
+// descriptor and its three dyn words are read once per workgroup, in front of the loops, and made wave-uniform, so "expert or policy" is a decision per row range and a
+// scalar branch: rows [0, n_expert) are copied as whole lanes (16 bytes each when both row buffers lie on the 16-byte grid, as torch's do; one float each otherwise: the
+// same bits), the reward column patched inside the lane that carries it; rows [n_expert, n) get ONE store each, to their reward column, and none under label 0. A
+// balanced learner's policy turn (n_expert = 0) is therefore n stores. The two ranges share no row, and a learner's workgroups see only its own descriptor.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ void mix_put(f32x4& v, int k, float x) { if (k == 0) v[0] = x; else if (k == 1) v[1] = x; else if (k == 2) v[2] = x; else v[3] = x; }
+__device__ __forceinline__ void mix_put(float& v, int, float x) { v = x; }
+
+// rows [0, n_expert) <- expert rows, lane by lane (V: f32x4 or float; lpr lanes per row); with a label the expert's constant reward goes into component k_rew of lane c_rew
+template <class V>
+__device__ __forceinline__ void mix_copy_expert(float* __restrict__ rows, const float* __restrict__ expert, int n_expert, int lpr, int c_rew, int k_rew, bool relabel, float v_expert) {
+  const V* src = reinterpret_cast<const V*>(expert);
+  V* dst = reinterpret_cast<V*>(rows);
+  const int total = n_expert * lpr, stride = gridDim.x * blockDim.x;
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  int c = i % lpr;                                     // one division per thread: the strides below are uniform
+  const int dc = stride % lpr;
+  for (; i < total; i += stride) {
+    V v = src[i];
+    if (relabel && c == c_rew) mix_put(v, k_rew, v_expert);
+    dst[i] = v;
+    c += dc; if (c >= lpr) c -= lpr;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_mix_relabel_population(const il_mix_learner* __restrict__ learners, int n, int row, int o_rew, int label, float update_freq) {
+  const il_mix_learner a = learners[blockIdx.y];       // uniform address: one descriptor per workgroup
+  float* rows = as_global(a.rows);
+  const float* expert = as_global(a.expert_rows);
+  const long long* dyn = as_global((const long long*)a.dyn);
+  const long long d0 = dyn[0], d1 = dyn[1], d2 = dyn[2];   // the conversions of k_mix_relabel
+  const int n_expert = __builtin_amdgcn_readfirstlane((int)(d0 < 0 ? 0 : (d0 > n ? n : d0)));
+  const float round_num = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)d1)));
+  const float policy_trajectories = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)(d2 > 1 ? d2 : 1))));
+  const float v_expert = (label == 1) ? 1.f : a.reward_expert;
+  if (n_expert > 0) {
+    if ((((uintptr_t)rows | (uintptr_t)expert) & 15) == 0) mix_copy_expert<f32x4>(rows, expert, n_expert, row >> 2, o_rew >> 2, o_rew & 3, label != 0, v_expert);
+    else mix_copy_expert<float>(rows, expert, n_expert, row, o_rew, 0, label != 0, v_expert);
+  }
+  if (label == 0) return;
+  for (int r = n_expert + blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x) {   // policy rows: the reward column alone
+    float* p = rows + (size_t)r * row + o_rew;
+    float v = 0.f;
+    if (label == 2) {
+      const float stamped = ceilf(__fdiv_rn(p[4], update_freq));                              // round in which the row was collected
+      v = __fdiv_rn(-1.f * ((round_num > stamped) ? 1.f : 0.f), policy_trajectories);         // -0.0 for the current round, like torch
+    }
+    *p = v;
+  }
+}
+
+extern "C" int il_batch_mix_relabel_population(const il_mix_learner* learners, int32_t n_learners, int32_t n, int32_t S, int32_t A, int32_t label, int32_t update_freq, il_stream_t stream) {
+  IL_CHECK_ARG(learners, "il_batch_mix_relabel_population: null learner array");
+  IL_CHECK_ARG(((uintptr_t)learners & 7) == 0, "il_batch_mix_relabel_population: the learner array must be 8-byte aligned");
+  IL_CHECK_ARG(n_learners >= 1 && n_learners <= 65535, "il_batch_mix_relabel_population: n_learners=%d outside 1..65535", n_learners);
+  IL_CHECK_ARG(n > 0 && S > 0 && A > 0, "il_batch_mix_relabel_population: n=%d state_dim=%d action_dim=%d must be positive", n, S, A);
+  IL_CHECK_ARG(label >= 0 && label <= 2 && (label != 2 || update_freq > 0), "il_batch_mix_relabel_population: label=%d update_freq=%d", label, update_freq);
+  const int row = il_ring_row_floats(S, A);            // a whole number of 16-byte lanes
+  IL_CHECK_ARG((int64_t)n * row <= 0x7FFFFFFFll, "il_batch_mix_relabel_population: n=%d rows of %d floats exceed the 32-bit element index", n, row);
+  const int lanes = n * (row / 4);                     // sized from n x row like the single-learner launch, one 16-byte lane per thread
+  const int blocks = (lanes + 255) / 256 < 512 ? (lanes + 255) / 256 : 512;
+  { IL_TRACE("k_mix_relabel_population", (hipStream_t)stream);
+    k_mix_relabel_population<<<dim3(blocks, n_learners), 256, 0, (hipStream_t)stream>>>(learners, n, row, 2 * S + A, label, (float)update_freq); }
+  IL_CHECK_LAUNCH("il_batch_mix_relabel_population");
+  return IL_OK;
+}
+
 extern "C" int il_replay_wrap_absorbing(float* ring, int64_t capacity, int32_t S, int32_t A, int64_t last, int64_t cursor, il_stream_t stream) {
   IL_CHECK_ARG(ring && last >= 0 && last < capacity && cursor >= 0 && cursor < capacity && last != cursor, "il_replay_wrap_absorbing: bad arguments");
   { IL_TRACE("k_wrap_absorbing", (hipStream_t)stream); k_wrap_absorbing<<<1, 64, 0, (hipStream_t)stream>>>(ring, il_ring_row_floats(S, A), S, A, last, cursor); }

@@ -1440,7 +1440,10 @@ class BatchedPopulationPlan:
   relabel), DRIL (`il_dril_reward_population`: every learner's Monte-Carlo-dropout reward under its own ensemble, threshold, Philox key and counter; with `bc_aux` also
   `il_bc_step_population`, the behavioural-cloning auxiliary step of every actor on its own expert batch, in front of the forward kernels), RED (`il_red_reward_population`: every learner's eval-mode reward under its own predictor, target and sigma_1) and GMMIL (`il_gmmil_reward_population`: every
   learner's kernel-mean-embedding reward on its own batches, under its own frozen bandwidths, with its own workspace) learners, and PWIL learners, whose update is SAC's (no
-  reward step: the acting side stores the coupling reward with every transition); GAIL's, DRIL's, RED's and GMMIL's reward launches run
+  reward step: the acting side stores the coupling reward with every transition), and AdRIL / SQIL learners (`il_batch_mix_relabel_population`: every learner's expert
+  rows mixed in and its rewards relabelled under its own {n_expert, round, policy trajectories} and 1 / |expert trajectories|, ONE launch between the gathers and the SAC
+  launches, on the one stream - it edits the rows the forward kernels read; `relabel_args(step, [num_trajectories ...])` stages the 3 L words of the next update with one
+  stream-ordered copy and is due before every run() / replay(), like `UpdatePlan.relabel_args`); GAIL's, DRIL's, RED's and GMMIL's reward launches run
   on a second stream beside the reward-independent forward kernels (IL_POP_OVERLAP=0: in stream order).  GMMIL: the FIRST run() is eager - every learner fixes its
   bandwidths from its first batch on the host (models.py:193-195), one read per learner, once - and cannot be captured; from the second on an update is the same launches
   as for the others."""
@@ -1462,7 +1465,11 @@ class BatchedPopulationPlan:
     for p in self.plans:
       p._set_device_sync(False)   # one stream, one set of launches for all learners: plain stream order
     p0 = self.plans[0]
-    assert all(p.algorithm == p0.algorithm and p.B == p0.B for p in self.plans) and p0.algorithm in ('SAC', 'GAIL', 'RED', 'GMMIL', 'DRIL', 'PWIL'), 'the population launches exist for SAC, GAIL, RED, GMMIL, DRIL and PWIL learners of one batch size'
+    assert all(p.algorithm == p0.algorithm and p.B == p0.B for p in self.plans) and p0.algorithm in ('SAC', 'GAIL', 'RED', 'GMMIL', 'DRIL', 'PWIL', 'AdRIL'), 'the population launches exist for SAC, GAIL, RED, GMMIL, DRIL, PWIL and AdRIL learners of one batch size'
+    if p0.algorithm == 'AdRIL':   # il_batch_mix_relabel_population: label, update_freq, n and the row are the launch's, everything else is the learner's
+      shape = lambda p: (p.B, p.discriminator.update_freq, p.discriminator.balanced, p.memory.row, p.expert_memory.row, p.memory.state_size, p.memory.action_size)
+      assert all(shape(p) == shape(p0) for p in self.plans) and p0.memory.row == p0.expert_memory.row, 'BatchedPopulationPlan(AdRIL): the relabellers of one population share batch, update_freq, balanced and the ring row'
+      assert not any(p.mix_expert or p.bc_aux for p in self.plans), 'BatchedPopulationPlan(AdRIL): mixed batches / the BC auxiliary step have no population launches'
     if p0.algorithm == 'PWIL':   # a SAC update: PWIL's reward is stored with every transition, by the acting side (PopulationActingWorker(reward_models=...): il_pwil_act_reward_population)
       assert not any(p.mix_expert or p.bc_aux for p in self.plans), 'BatchedPopulationPlan(PWIL): mixed batches / the BC auxiliary step have no population launches'
     if p0.algorithm == 'RED':
@@ -1506,10 +1513,42 @@ class BatchedPopulationPlan:
       self.reward_ptrs = torch.tensor([p.rewards.data_ptr() for p in self.plans], dtype=torch.int64, device=dev)
       self.bc_aux = bool(p0.bc_aux)
       if self.bc_aux: self.expert_batches = _device_array([p.eb for p in self.plans], dev)
+    if self.algorithm == 'AdRIL':   # one (L, 3) device tensor for the per-update scalars: learner l's il_mix_learner.dyn points at row l (8-byte words, so every row is aligned)
+      import numpy as np
+      r0 = p0.discriminator
+      self.dyn = torch.zeros((self.L, 3), dtype=torch.int64, device=dev)
+      self._dyn_set = False
+      assert all(p.rows.data_ptr() % 16 == 0 and p.erows.data_ptr() % 16 == 0 for p in self.plans), 'BatchedPopulationPlan(AdRIL): row buffers off the 16-byte grid'
+      self.mix_learners = _device_array([_lib.MixLearner(p.rows.data_ptr(), p.erows.data_ptr(), self.dyn[l].data_ptr(),
+                                                         float(np.float32(1 / p.expert_memory.num_trajectories)) if r0.update_freq > 0 else 0.0)
+                                         for l, p in enumerate(self.plans)], dev)
+      self.mix_label = 2 if r0.update_freq > 0 else 1
     self.gmmil_learners = None   # GMMIL: the il_gmmil_learner array, built once every learner's bandwidths are frozen (after the first run())
     self.graph = None
     self._prepared = False
     self.side = torch.cuda.Stream() if self.algorithm in ('GAIL', 'RED', 'GMMIL', 'DRIL') and os.environ.get('IL_POP_OVERLAP', '1') != '0' else None
+
+  def relabel_args(self, step: int, num_trajectories):
+    """AdRIL / SQIL: `UpdatePlan.relabel_args` for every learner of the population (`num_trajectories`: one count per learner, in plan order) - each learner's balanced
+    alternation, flipping its own `discriminator.sample_expert`, the round of `step` and its policy trajectory count - staged for the NEXT update with ONE stream-ordered
+    copy of all 3 L words into the device tensor the (captured) relabel launch reads. Call once before every run() / replay()."""
+    assert self.algorithm == 'AdRIL' and len(num_trajectories) == self.L, 'BatchedPopulationPlan.relabel_args: AdRIL learners, one trajectory count per learner'
+    if self.subs is not None:
+      at = 0
+      for sub in self.subs:
+        sub.relabel_args(step, num_trajectories[at:at + sub.L]); at += sub.L
+      return
+    words = []
+    for p, count in zip(self.plans, num_trajectories):
+      r = p.discriminator
+      if r.balanced:
+        n_expert = self.B if r.sample_expert else 0
+        r.sample_expert = not r.sample_expert
+      else:
+        n_expert = self.B // 2
+      words.append([n_expert, -(-int(step) // r.update_freq) if r.update_freq > 0 else 0, int(count)])
+    self.dyn.copy_(torch.tensor(words, dtype=torch.int64))   # pageable source: staged synchronously, ordered on the current stream
+    self._dyn_set = True
 
   def run(self):
     if self.subs is not None:
@@ -1523,7 +1562,14 @@ class BatchedPopulationPlan:
       return
     L, st, p0 = _lib.lib(), _lib.stream_ptr(), self.plans[0]
     prepared = _lib.IL_FLAG_SAC_PREPARED if (self._prepared and not self.bc_aux) else 0   # the BC auxiliary step moves the actor every update: its lane-ordered copies are re-derived (UpdatePlan.run: flag = 0)
+    if self.algorithm == 'AdRIL':   # asked in front of the first launch: a refused update draws no indices
+      capturing = torch.cuda.is_current_stream_capturing()   # a captured launch reads whatever relabel_args() stored before it is replayed
+      assert capturing or self._dyn_set, 'BatchedPopulationPlan(AdRIL): call relabel_args(step, [memory.num_trajectories ...]) before every update'
     _lib.check(L.il_replay_sample_population(_lib.ptr(self.sample_args), self.L, self.B, self.max_row, st))
+    if self.algorithm == 'AdRIL':   # models.py:293-318 for every learner, in stream order between the gathers and the forward kernels that read the rows it edits
+      m = p0.memory
+      _lib.check(L.il_batch_mix_relabel_population(_lib.ptr(self.mix_learners), self.L, self.B, m.state_size, m.action_size, self.mix_label, p0.discriminator.update_freq, st))
+      if not capturing: self._dyn_set = False
     if self.algorithm == 'RED':
       assert not any(p.discriminator.training for p in self.plans), 'BatchedPopulationPlan(RED): discriminator.eval() first (train.py:147)'
     if self.algorithm == 'GMMIL':

@@ -132,6 +132,25 @@ int il_batch_mix_relabel(float* rows, const float* expert_rows, int32_t n, int32
  * all-expert / all-policy batches), round_num = ceil(step / update_freq), policy_trajectories}; the caller refreshes it with a stream-ordered copy before each replay. */
 int il_batch_mix_relabel_dyn(float* rows, const float* expert_rows, int32_t n, int32_t state_dim, int32_t action_dim, int32_t label, int32_t update_freq, float reward_expert,
                              const int64_t* dyn, il_stream_t stream);
+/* il_batch_mix_relabel_dyn for n_learners learners in ONE launch (an AdRIL / SQIL seed sweep in one process: the step between il_replay_sample_population and
+ * il_sac_update_population). Grid (strip, learner): for learners[l] (a DEVICE array) the call has exactly the effect of il_batch_mix_relabel_dyn(rows, expert_rows, n,
+ * state_dim, action_dim, label, update_freq, reward_expert, dyn, stream), bit for bit: the same clamps (n_expert into [0, n], policy trajectories to at least 1), the same
+ * ceil(step / update_freq) round stamp and the same -[round > stamp] / trajectories, i.e. -0.0 for a row of the current round. n, the dims, label and update_freq are the
+ * population's; rows, expert rows, the three dyn words and reward_expert are each learner's own (with imitation.balanced one learner's n_expert may be n while
+ * another's is 0; the learners subsample their expert data under their own seeds, so 1 / |expert trajectories| differs). Rows [0, n_expert) are copied as whole 16-byte
+ * lanes - rows and expert_rows are expected on the 16-byte grid (torch's allocator puts them there; the builder of the array checks, since the entry point cannot read a
+ * device array: a buffer off the grid is still served, one float per lane, with the same result) -; rows [n_expert, n) get one store each, to their reward column, and none
+ * under label 0. A learner's workgroups touch no other learner's memory. dyn: int64[3] on the device, 8-byte aligned, refreshed by the caller with a stream-ordered copy
+ * before each launch or replay. Refused (IL_ERR_ARG, nothing launched): a null or misaligned array, n_learners outside 1..65535, n <= 0, a label outside 0..2, label 2
+ * with update_freq <= 0. */
+typedef struct il_mix_learner {
+  float* rows;               /* [n][row] packed batch of this learner, edited in place */
+  const float* expert_rows;  /* [n][row] its expert batch */
+  const int64_t* dyn;        /* {n_expert, round, policy trajectories} of this update, as il_batch_mix_relabel_dyn reads them */
+  float reward_expert;       /* AdRIL: float32(1 / this learner's expert trajectories); unused for labels 0 and 1 */
+} il_mix_learner;            /* 32 bytes */
+int il_batch_mix_relabel_population(const il_mix_learner* learners /* device */, int32_t n_learners, int32_t n, int32_t state_dim, int32_t action_dim,
+                                    int32_t label, int32_t update_freq, il_stream_t stream);
 /* memory.py:58-63 `sample` gather step: out[i] = ring[idx[i]] for i < n (packed rows, coalesced 16-B lanes). */
 int il_replay_gather(const float* ring, int64_t capacity, int32_t row_floats, const int32_t* idx, int32_t n, float* out_rows,
                      il_stream_t stream);

@@ -11,7 +11,9 @@
 configuration, where one reward launch is 16 workgroups; --algorithms DRIL: the shipped configuration, i.e. with imitation.bc_aux_loss - il_dril_reward_population and
 il_bc_step_population per update - and the ensemble's pretraining cut to 100 iterations per learner; --algorithms PWIL: with the opt-in key +sweep.pwil_population=true,
 every learner on its own 6,006 atoms - six trajectories of 1,000 steps and their absorbing rows - at horizon 1,000: 24 chunks of 8 candidates per learner, one
-il_pwil_act_reward_population launch per lockstep step under (c) against one il_pwil_act_reward launch per learner under (b); (a) couples per step as train() does)"""
+il_pwil_act_reward_population launch per lockstep step under (c) against one il_pwil_act_reward launch per learner under (b); (a) couples per step as train() does;
+--algorithms AdRIL: the shipped configuration - balanced, update_freq 1250 - with the opt-in key +sweep.adril_population=true: one il_batch_mix_relabel_population launch
+and one copy of 3 L words per update under (c) against one il_batch_mix_relabel_dyn launch and one three-word copy per learner under (b))"""
 import argparse
 import os
 import sys
@@ -42,6 +44,7 @@ def say(text):
 def overrides(algorithm, steps, start):
   extra = ['imitation.pretraining.iterations=100'] if algorithm in ('RED', 'DRIL') else []   # (the predictor's / ensemble's pretraining sits in front of the clock: kept short, the job measures the loop)
   if algorithm == 'PWIL': extra = [train.PWIL_POPULATION_KEY]   # PWIL sweeps form a population on opt-in only; train() ignores the key
+  if algorithm == 'AdRIL': extra = [train.ADRIL_POPULATION_KEY]   # likewise
   batch = 128 if algorithm == 'GMMIL' else 256
   return [f'algorithm={algorithm}', 'env=halfcheetah', f'steps={steps}', f'training.start={start}', f'training.batch_size={batch}', 'check_time_usage=true', 'logging.interval=1000',
           '+synthetic_env.dataset_trajectories=6'] + extra

@@ -12,7 +12,8 @@ the row-by-row loop.
 Sweeps:  python train.py -m seed=1,2,3 algorithm=GAIL env=halfcheetah  (Hydra's multirun: comma lists, Cartesian product, outputs/<algorithm>_<env>_sweeper/<time>/<job>/).
 Jobs that differ only in their seed train as ONE population in lockstep (`train_sweep`: `il.BatchedPopulationPlan` for the update, `il.PopulationActingWorker` or one
 `il.ActingWorker` per learner for acting: `+sweep.schedule=population|per_learner`, the same bits either way; GMMIL and DRIL sweeps only when that key is given, PWIL sweeps only under `+sweep.pwil_population=true`:
-one `il_pwil_act_reward_population` coupling launch per lockstep step in front of the population acting launch); every other sweep runs its jobs one after another, and says so.
+one `il_pwil_act_reward_population` coupling launch per lockstep step in front of the population acting launch, AdRIL / SQIL sweeps only under `+sweep.adril_population=true`:
+one `il_batch_mix_relabel_population` launch per update between the gathers and the SAC launches); every other sweep runs its jobs one after another, and says so.
 """
 import os
 import sys
@@ -413,6 +414,13 @@ def pwil_population(cfg) -> bool:
   return bool((cfg.get('sweep', {}) or {}).get('pwil_population', False))
 
 
+ADRIL_POPULATION_KEY = '+sweep.adril_population=true'   # the opt-in of AdRIL / SQIL sweeps (`+sweep.schedule` alone keeps them job after job)
+
+
+def adril_population(cfg) -> bool:
+  return bool((cfg.get('sweep', {}) or {}).get('adril_population', False))
+
+
 def pwil_atoms_upper_bound(cfg) -> tuple:
   """(most atoms a learner of this configuration can hold, horizon): kept trajectories x ceil(horizon / subsample) rows, plus - with absorbing states - the appended
   absorbing row and the two rows the subsampling always keeps (environments.dataset_to_memory). imitation.trajectories=0 keeps the whole dataset: counted as the synthetic
@@ -433,12 +441,15 @@ def sweep_fallback_reason(cfg):
   """None when a seed sweep of this configuration can train as one population (what il.BatchedPopulationPlan and il.PopulationActingWorker take); otherwise the reason
   its jobs run one after another through train()."""
   explicit = (cfg.get('sweep', {}) or {}).get('schedule') is not None
-  if cfg.algorithm not in ('SAC', 'GAIL', 'RED', 'GMMIL') and not (cfg.algorithm == 'DRIL' and explicit) and not (cfg.algorithm == 'PWIL' and pwil_population(cfg)):
+  if cfg.algorithm not in ('SAC', 'GAIL', 'RED', 'GMMIL') and not (cfg.algorithm == 'DRIL' and explicit) and not (cfg.algorithm == 'PWIL' and pwil_population(cfg)) \
+      and not (cfg.algorithm == 'AdRIL' and adril_population(cfg)):
     reason = f'algorithm={cfg.algorithm} has no population launches (SAC, GAIL and RED have), and GMMIL under an explicit +sweep.schedule'
     if cfg.algorithm == 'DRIL':   # opt-in, as for GMMIL: a DRIL sweep without the key runs as it always has
       reason += f'; DRIL trains as one population (il_dril_reward_population, il_bc_step_population) only when +sweep.schedule={"|".join(SWEEP_SCHEDULES)} is given'
     if cfg.algorithm == 'PWIL':   # opt-in by a key of its own: a PWIL sweep without it, with or without +sweep.schedule, runs as it always has
       reason += f'; PWIL trains as one population (il_pwil_act_reward_population: one coupling launch per lockstep step) only when {PWIL_POPULATION_KEY} is given'
+    if cfg.algorithm == 'AdRIL':   # opt-in by a key of its own, as for PWIL: an AdRIL / SQIL sweep without it, with or without +sweep.schedule, runs as it always has
+      reason += f'; AdRIL trains as one population (il_batch_mix_relabel_population: one relabel launch per update) only when {ADRIL_POPULATION_KEY} is given'
     return reason
   if cfg.algorithm == 'GMMIL' and (cfg.get('sweep', {}) or {}).get('schedule') is None:
     # opt-in: a GMMIL sweep without the key runs as it always has; with it, its first update is eager (every learner's bandwidths) and the rest are population launches
@@ -451,7 +462,9 @@ def sweep_fallback_reason(cfg):
     return f'training.batch_size={cfg.training.batch_size} is not a multiple of 16'
   # RED, GMMIL and DRIL with prefill_memory: the expert rows are moved into the agent ring once, in front of the loop (train.py:134, 192); nothing is edited between the launches
   # PWIL with prefill_memory: each learner relabels its expert memory on the device and moves it into its ring, once, in front of the loop (train.py:135-141, 192)
-  if cfg.imitation.mix_expert_data != 'none' and not (cfg.algorithm in ('RED', 'GMMIL', 'DRIL', 'PWIL') and cfg.imitation.mix_expert_data == 'prefill_memory'):
+  # AdRIL's mixed_batch (config.validate demands it) is its relabel launch itself: il_batch_mix_relabel_population edits every learner's rows in ONE launch between the launches
+  if cfg.imitation.mix_expert_data != 'none' and not (cfg.algorithm in ('RED', 'GMMIL', 'DRIL', 'PWIL') and cfg.imitation.mix_expert_data == 'prefill_memory') \
+      and not (cfg.algorithm == 'AdRIL' and cfg.imitation.mix_expert_data == 'mixed_batch'):
     return f'imitation.mix_expert_data={cfg.imitation.mix_expert_data} edits the batches between the launches'
   if cfg.imitation.bc_aux_loss and cfg.algorithm != 'DRIL':   # DRIL (every shipped configuration sets it): il_bc_step_population in front of the forward launches
     return 'imitation.bc_aux_loss adds an actor step per update that the population launches do not have'
@@ -526,7 +539,7 @@ def train_sweep(cfgs, prefixes):
   """The loop of train() in lockstep over L learners that differ only in their seed: per lockstep step ONE population act launch, L host environment steps and ONE
   append launch (`+acting.schedule=fused`: one launch for both); on update steps ONE population update (il.BatchedPopulationPlan); on evaluation steps
   evaluate_population. Every learner has its own seeds, index stream, environments, rings, networks, optimisers and `learner_id`; job l writes what a single run writes
-  under prefixes[l] (GAIL, RED and DRIL: with a discriminator.pth; PWIL and GMMIL, as in train(): without one - its bandwidths are fixed by each learner's first batch, in the first, eager,
+  under prefixes[l] (GAIL, RED and DRIL: with a discriminator.pth; PWIL, AdRIL and GMMIL, as in train(): without one - its bandwidths are fixed by each learner's first batch, in the first, eager,
   update, and live in no file). Returns the mean normalised score per job."""
   L = len(cfgs)
   assert L >= 1 and len(prefixes) == L
@@ -574,6 +587,8 @@ def train_sweep(cfgs, prefixes):
       ln.discriminator_optimiser = il.AdamW(ln.discriminator, lr=cfg.imitation.learning_rate, weight_decay=cfg.imitation.weight_decay)
     elif cfg.algorithm == 'PWIL':   # this learner's own atoms: its expert data was subsampled under its seed
       ln.discriminator = il.PWILDiscriminator(S, A, cfg.imitation, ln.expert_memory, ln.env.max_episode_steps)
+    elif cfg.algorithm == 'AdRIL':   # no parameters: its state is the balanced alternation (update_freq=0: SQIL)
+      ln.discriminator = il.RewardRelabeller(cfg.imitation.update_freq, cfg.imitation.balanced)
     ln.metrics = dict(train_steps=[], train_returns=[], test_steps=[], test_returns=[], test_returns_normalized=[], update_steps=[], predicted_rewards=[], alphas=[], entropies=[], Q_values=[])
     ln.score = []
     start_time += time.time() - built
@@ -620,7 +635,7 @@ def train_sweep(cfgs, prefixes):
                             noise_seed_offset=0 if cfg.algorithm == 'PWIL' else None)   # PWIL jobs train as train() trains them, bit for bit: its Philox key for this learner's seed
     ln.plan.main_feeds_ring = True
     ln.plan.watch_timeouts()
-    if ln.discriminator is not None and cfg.algorithm not in ('DRIL', 'PWIL'): ln.discriminator.eval()   # train.py:147 (the DRIL ensemble keeps its dropout, i.e. train mode, on purpose)
+    if ln.discriminator is not None and cfg.algorithm not in ('DRIL', 'PWIL', 'AdRIL'): ln.discriminator.eval()   # train.py:147 (the DRIL ensemble keeps its dropout, i.e. train mode, on purpose)
     learners.append(ln)
   plans = [ln.plan for ln in learners]
 
@@ -668,6 +683,10 @@ def train_sweep(cfgs, prefixes):
       state[l] = following[l]
 
     if step >= cfg0.training.start and step % cfg0.training.interval == 0:
+      if cfg0.algorithm == 'AdRIL':   # models.py:300-318: every learner's {n_expert, round, policy trajectories} of this update, in front of its run or replay
+        if pop is not None: pop.relabel_args(step, [ln.memory.num_trajectories for ln in learners])   # one stream-ordered copy of the 3 L words
+        else:
+          for ln in learners: ln.plan.relabel_args(step, ln.memory.num_trajectories)
       if pop is not None and captured:
         pop.replay()
       else:
