@@ -203,7 +203,15 @@ class ReplayMemory(torch.utils.data.Dataset):
     return batch_views(rows, self.state_size, self.action_size, self.absorbing)
 
   def sample_device(self, n: int, idx_out: Tensor, rows_out: Tensor) -> Dict[str, Tensor]:
-    """Graph-capturable sample: MT19937 draw + rejection on the device (same stream), then the gather; no host involvement."""
+    """Graph-capturable sample: MT19937 draw + rejection on the device (same stream), then the gather; no host involvement.
+    A ring with no slot to draw from (not full with idx in {0, 1}: memory.py:54 raises there; or a full ring of one row, whose only slot is the excluded one) is refused
+    here, in the words of the host draw (il_mt19937_sample_indices): the device draw reads the cursor from device memory and would write zeros. A captured plan,
+    whose cursor moves on the device, is not covered."""
+    high = self.size if self.full else self.idx - 1
+    if high < 1 or high > 0x7FFFFFFF:
+      raise RuntimeError(f'il_mt19937_sample_indices_device: empty or oversized range (high={high})')
+    if high == 1 and (self.idx - 1) % self.size == 0:
+      raise RuntimeError('il_mt19937_sample_indices_device: the only candidate slot is the excluded one')
     st = self.stream().device_state(self.device)
     _lib.check(_lib.lib().il_mt19937_sample_indices_device(_lib.ptr(st), _lib.ptr(self._ring_state), n, _lib.ptr(idx_out), _lib.stream_ptr()))
     _lib.check(_lib.lib().il_replay_gather(_lib.ptr(self.ring), self.size, self.row, _lib.ptr(idx_out), n, _lib.ptr(rows_out), _lib.stream_ptr()))
