@@ -252,24 +252,32 @@ __device__ __forceinline__ void gail_grad_body(il_disc d, il_batch pol, il_batch
     if (tid < 64 && d.spectral_norm) sn_chain(L.W1s, L.W2s, L.Ms, D, H, L.u1(0), L.v1(0), L.v2(0), L.tmp, pass + 1, L.sc(0));
     long long* sy = reinterpret_cast<long long*>(d.sync);
     IL_TL(0, 1);
+    // (round 5) With the in-launch sampler the draw may be AHEAD of the previous update's end. The one thing this step reads that the previous update's last launch
+    // writes is the Philox counter its actor step advances, and only the mixing calls (gradient penalty, Mixup) read it: those wait for [IL_SYNC_MAIN_EPOCH] (= the number
+    // of discriminator steps closed so far) as well, but only once their rows are on their way into registers (epoch_late, below). The policy and the expert call do
+    // not wait for the epoch at all. Why nothing else needs it: the ring rows an update may draw are stream-ordered ahead of this launch (appends enqueued on the caller's
+    // stream since the last update: this stream waits for that one before the launch, UpdatePlan main_feeds_ring); the expert ring is static; k_gail_reduce of the previous update - the
+    // reader of the slabs and writer of the parameters - precedes this launch in its own stream; and this launch writes nothing but its slabs.
+    bool epoch_late = false;
+    long long side_epoch = 0;
     if (pol.gather && exp.gather) {
-      // rows come straight from the rings: only the draw has to be done (with the in-launch sampler a second wait follows, and the acquire - by every wave - sits behind that one)
-      if (has_sampler) sync_wait_only(sy, IL_SYNC_INDICES, sync_read(sy, IL_SYNC_SIDE_EPOCH) + 1);
-      else sync_wait(sy, IL_SYNC_INDICES, sync_read(sy, IL_SYNC_SIDE_EPOCH) + 1);
-      // (round 5) the draw may now be AHEAD of the previous update's end: this step reads the Philox counter that update's actor step advances (below), so it still starts
-      // behind [IL_SYNC_MAIN_EPOCH] (= the number of discriminator steps closed so far) - 4 us earlier than when the draw itself waited for it
-      if (has_sampler) sync_wait(sy, IL_SYNC_MAIN_EPOCH, sync_read(sy, IL_SYNC_SIDE_EPOCH));
+      // rows come straight from the rings: only the draw has to be done. Every wave acquires here: the index arrays are read with ordinary loads right behind this wait
+      side_epoch = sync_read(sy, IL_SYNC_SIDE_EPOCH);   // (closed by k_gail_reduce of the previous update, which precedes this launch in its stream: constant here)
+      sync_wait(sy, IL_SYNC_INDICES, side_epoch + 1);
+      epoch_late = has_sampler && kind >= 2;
     } else {
       sync_wait(sy, IL_SYNC_ROWS, (sync_read(sy, IL_SYNC_SIDE_EPOCH) + 1) * sy[IL_SYNC_GATHER_WGS]);   // gathered batches: every gather workgroup of this update has signalled
     }
-    IL_TL(0, 2);
-    ctr = d.noise_counter ? *d.noise_counter : 0u;   // after the wait: the previous update's actor step (which bumps it) precedes this update's gather
+    if (!epoch_late) {
+      IL_TL(0, 2);
+      if (kind >= 2) ctr = d.noise_counter ? *d.noise_counter : 0u;   // after the wait: the previous update's actor step (which bumps it) precedes this update's gather (the policy and the expert call do not read it)
+    }
     // (round 4) The rows of this call with every load of a round in flight: stage_rows' element loop makes, per element, an index load and then a dependent row load -
     // four serialised fabric / HBM round trips for the two elements a thread owns at HalfCheetah dims - and draws the mixing coefficient of a row once per ELEMENT
     // (a Philox call each). Here: the coefficients once per row (16 threads, into zs, which nothing reads before the loss), the indices of up to four elements per thread
     // requested together, then their rows. Same values, same X: same bits.
     float* eps_s = L.zs;
-    if (kind >= 2 && tid < IL_TILE_R) eps_s[tid] = tid < nrows ? mix_eps(row0 + tid) : 0.f;
+    if (!epoch_late && kind >= 2 && tid < IL_TILE_R) eps_s[tid] = tid < nrows ? mix_eps(row0 + tid) : 0.f;
     const unsigned mdp = fastdiv_magic(Dp);
     for (int base = 0; base < IL_TILE_R * Dp; base += 4 * (int)blockDim.x) {
       int64_t pr[4], er[4]; int rr[4], kk[4]; bool ok[4];
@@ -299,6 +307,14 @@ __device__ __forceinline__ void gail_grad_body(il_disc d, il_batch pol, il_batch
         if (exp.gather) wer = wer < 0 ? 0 : (wer >= exp.gather_capacity ? exp.gather_capacity - 1 : wer);
         if (kind != 1) wp = gload(pol.weights + (size_t)wpr * pol.ld_weights);
         if (kind != 0) we = gload(exp.weights + (size_t)wer * exp.ld_weights);
+      }
+      if (base == 0 && epoch_late) {
+        // the mixing calls behind the in-launch sampler: the first round's indices, elements and row weights are requested (they usually sit in registers long before the
+        // previous update ends); now the epoch, then the counter and the coefficients - one trip behind the epoch instead of index -> row behind it
+        sync_wait(sy, IL_SYNC_MAIN_EPOCH, side_epoch);
+        IL_TL(0, 2);
+        ctr = d.noise_counter ? *d.noise_counter : 0u;
+        if (tid < IL_TILE_R) eps_s[tid] = tid < nrows ? mix_eps(row0 + tid) : 0.f;
       }
       if (base == 0) __syncthreads();   // the rows' mixing coefficients are in LDS
 #pragma unroll

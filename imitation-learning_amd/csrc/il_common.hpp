@@ -357,6 +357,32 @@ __device__ __forceinline__ void sync_wait(long long* sync, int which, long long 
 }
 __device__ __forceinline__ void sync_wait_only(long long* sync, int which, long long target) { sync_wait<false, true>(sync, which, target); }
 __device__ __forceinline__ void sync_wait_leader(long long* sync, int which, long long target) { sync_wait<true>(sync, which, target); }
+// The split form: the first poll was REQUESTED by the caller - sync_read(sync, which) by every thread with no branch around it, in one batch with the word the target is
+// derived from (and, for the waves that do not poll, ahead of loads that do not depend on the wait) - and `seen` is what it returned. A target that is derived from
+// another counter then costs one trip to memory instead of two dependent ones. Polls go on from `seen`; same bound, same poison path, same acquire forms as above.
+template <bool LEADER_ACQUIRE = false, bool NO_ACQUIRE = false>
+__device__ __forceinline__ void sync_wait(long long* sync, int which, long long target, long long seen, int limit) {   // all threads of the workgroup
+  if (threadIdx.x == 0) {
+    int spins = 0;
+    while (seen < target) {
+      __builtin_amdgcn_s_sleep(8);
+      if (limit == 0) { const long long own = sync[IL_SYNC_SPIN]; limit = own > 0 ? (int)(own > 0x7fffffffLL ? 0x7fffffffLL : own) : IL_SYNC_SPIN_LIMIT; }
+      if (++spins > limit) { sync_timed_out(sync); break; }
+      seen = __hip_atomic_load(sync + which, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (LEADER_ACQUIRE && !NO_ACQUIRE) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  }
+  __syncthreads();
+  if (!LEADER_ACQUIRE && !NO_ACQUIRE) sync_acquire_all();
+}
+// The words of such a wait whose target is [IL_SYNC_MAIN_EPOCH] + 1 (the hand-offs of the update that follows the ones counted there): both requested at once
+struct SyncEpochWords { long long epoch, seen; };
+__device__ __forceinline__ SyncEpochWords sync_request_epoch(const long long* sync, int which) {   // every thread, no branch around the call
+  SyncEpochWords w;
+  w.epoch = sync_read(sync, IL_SYNC_MAIN_EPOCH); w.seen = sync_read(sync, which);
+  return w;
+}
+__device__ __forceinline__ void sync_wait_leader(long long* sync, int which, const SyncEpochWords& w) { sync_wait<true>(sync, which, w.epoch + 1, w.seen, 0); }
 
 // ---------------------------------------------------------------------------------------------
 // Stage hand-offs of the overlapped SAC branch (il_sac_update_gather_overlap; include/il_hip.h [IL_SYNC_OV_EPOCH] / [IL_SYNC_OV_TICKET]). The four launches of an update alternate

@@ -551,7 +551,7 @@ __device__ __forceinline__ void sac_chain_body(il_sac& d, il_batch& b, const flo
   int gw = -1, G = 0;   // row-copy workgroup index / count
   if (bid >= 6 * nt) { gw = bid - 6 * nt; G = (int)gridDim.x - 6 * nt; }
   IL_TL(0, 0);
-  if (rl.wait_indices) { long long* sy = reinterpret_cast<long long*>(d.sync); sync_wait_leader(sy, IL_SYNC_INDICES, sync_read(sy, IL_SYNC_MAIN_EPOCH) + 1); }   // (leader: see k_sac_chain_pair)
+  if (rl.wait_indices) { long long* sy = reinterpret_cast<long long*>(d.sync); sync_wait_leader(sy, IL_SYNC_INDICES, sync_request_epoch(sy, IL_SYNC_INDICES)); }   // (both words in one trip; leader: see k_sac_chain_pair)
   IL_TL(0, 1);
   if (gw >= 0) {
     const int row4 = b.ld_states / 4, lanes = d.batch * row4;
@@ -648,7 +648,14 @@ __device__ __forceinline__ float* pair_w1s(float* smem, int in_pad, int H) { ret
 // actor(s') of one tile as a pair (reference models.py:90-94 on next_states; training.py:21): the arithmetic of actor_fwd_tile(is_cur = false)
 // ov >= 0 (overlapped launches): the previous update's actor optimiser launch may still be running. The row indices and the rows are requested first; everything that launch
 // writes (the actor's parameters and lane-ordered copy, the Philox counter) is requested behind the wait for its epoch.
-__device__ __forceinline__ void actor_next_pair(const il_sac& d, const il_batch& b, const float* __restrict__ eps_next, int tile, int half, float* smem, float* slab, unsigned* flag, long long ov = -1, int ov_grid = 0) {
+// wait_sy != NULL (in-order launches behind the resident sampler, ov < 0): this role does the launch's wait for [IL_SYNC_INDICES] itself. Nothing it reads but the index
+// arrays depends on that wait - its weights, biases and the Philox counter were written by the previous launches of this stream - and those are what the role really
+// waits for: the two sync words go out first, in one batch, every wave's W1 lanes, biases, counter and head lanes right behind them, and the compare looks at the words
+// as they arrive; only the row indices, the rows and the head threads' `absorbing` stay behind the wait. The polling wave requests its weights ahead of the wait like
+// the others: its acquire waits for them (a fence waits for every load of its wave), but they travel with the words; requested behind the acquire from a second site
+// in the code, the compiler parked them in other registers and waited for them in front of the row indices - a trip more, not less.
+__device__ __forceinline__ void actor_next_pair(const il_sac& d, const il_batch& b, const float* __restrict__ eps_next, int tile, int half, float* smem, float* slab, unsigned* flag, long long ov = -1, int ov_grid = 0,
+                                                long long* wait_sy = nullptr) {
   const int S = d.state_dim, A = d.action_dim, H = d.hidden, B = d.batch;
   const int row0 = tile * IL_TILE_R;
   const int Sp = round_up16(S), ldx = Sp + 4, ldh = H + 4, ldw1 = Sp + 4;
@@ -659,33 +666,62 @@ __device__ __forceinline__ void actor_next_pair(const il_sac& d, const il_batch&
   const MlpView net = mlp_view(d.actor, S, H, 2 * A);
   const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4, wave = threadIdx.x >> 6, nw = blockDim.x >> 6, tid = threadIdx.x;
   const int t2 = 8 * half + wave;   // this wave's output tile of the hidden layer
+  const bool split = wait_sy != nullptr;
+  // (every thread, and NO branch around the request: behind one the compiler waits for the words where the branch ends, ahead of every later request. A role without
+  // this wait reads - and ignores - the same two offsets of the workspace's head, which pair mode's activations make far larger. The announce below is younger: the
+  // compare does not wait for it.)
+  const SyncEpochWords sw = sync_request_epoch(split ? wait_sy : reinterpret_cast<const long long*>(W), IL_SYNC_INDICES);
   if (half == 0) pair_announce(flag);
   // requests, smallest first: row indices, W1, biases, the rows, then the hidden layer's panel
-  RowsPre rp; rows_idx(rp, Sp, row0, b.gather);
+  RowsPre rp;
   const bool head_thread = half == 0 && tid < IL_TILE_R * A;
   const int hr = tid / A, hc = tid - hr * A;
-  int64_t hidx = row0 + min(hr, IL_TILE_R - 1);
-  if (head_thread && b.gather) hidx = gload(b.gather + row0 + hr);
   float absorb_pre = 0.f;
-  if (ov >= 0) {   // rows first, then the wait; the weights behind it
-    rows_issue(rp, Sp, b.next_states, b.ld_next_states, S, nullptr, 0, 0, row0, b.gather != nullptr, b.gather_capacity, false);
-    if (head_thread) { if (b.gather) hidx = hidx < 0 ? 0 : (hidx >= b.gather_capacity ? b.gather_capacity - 1 : hidx); absorb_pre = gload(b.absorbing + (size_t)hidx * b.ld_absorbing); }
-    ov_wait(reinterpret_cast<long long*>(d.sync), IL_OV_DWA, ov, ov_grid);
-    IL_ST_GATE(IL_ST_CHAIN);
-  }
   const int w1_lanes = H * S / 4;
   const bool w1_regs = l1_rows_aligned(net.W1, S);
   W1Pre w1; L1Pre w1r;
-  if (w1_regs) l1_prefetch(w1r, net.W1, S, Sp, H); else w1_issue(w1, net.W1, w1_lanes);
-  const float pb1a = gload(net.b1 + wave * 16 + j), pb1b = gload(net.b1 + min((wave + nw) * 16 + j, H - 1)), pb2 = gload(net.b2 + t2 * 16 + j);
-  const uint32_t nctr = (half == 0 && d.noise_counter) ? gload(d.noise_counter) : 0u;
-  __builtin_amdgcn_sched_barrier(0);
-  if (ov < 0) {
-    rows_issue(rp, Sp, b.next_states, b.ld_next_states, S, nullptr, 0, 0, row0, b.gather != nullptr, b.gather_capacity, false);
-    if (head_thread) { if (b.gather) hidx = hidx < 0 ? 0 : (hidx >= b.gather_capacity ? b.gather_capacity - 1 : hidx); absorb_pre = gload(b.absorbing + (size_t)hidx * b.ld_absorbing); }
-  }
+  float pb1a = 0.f, pb1b = 0.f, pb2 = 0.f;
+  uint32_t nctr = 0u;
   SmallPre w3pre = {};
-  if (half == 0) w3pre = tile_fwd_small_prefetch(net.W3, H, 2 * A, H);
+  auto request_weights = [&] {
+    if (w1_regs) l1_prefetch(w1r, net.W1, S, Sp, H); else w1_issue(w1, net.W1, w1_lanes);
+    pb1a = gload(net.b1 + wave * 16 + j); pb1b = gload(net.b1 + min((wave + nw) * 16 + j, H - 1)); pb2 = gload(net.b2 + t2 * 16 + j);
+    nctr = (half == 0 && d.noise_counter) ? gload(d.noise_counter) : 0u;
+  };
+  auto request_head_row = [&](int64_t hidx) {
+    if (head_thread) { if (b.gather) hidx = hidx < 0 ? 0 : (hidx >= b.gather_capacity ? b.gather_capacity - 1 : hidx); absorb_pre = gload(b.absorbing + (size_t)hidx * b.ld_absorbing); }
+  };
+  // (the two forms share no control flow between the sync words and the panel: a join in between made the compiler wait for the words where the paths met)
+  if (split) {
+    request_weights();
+    if (half == 0) w3pre = tile_fwd_small_prefetch(net.W3, H, 2 * A, H);
+    __builtin_amdgcn_sched_barrier(0);
+    // (leader acquire: the index arrays are read by no kernel between this launch's start and the draw, see sac_chain_pair_body)
+    sync_wait_leader(wait_sy, IL_SYNC_INDICES, sw);
+    rows_idx(rp, Sp, row0, b.gather);
+    int64_t hidx = row0 + min(hr, IL_TILE_R - 1);
+    if (head_thread && b.gather) hidx = gload(b.gather + row0 + hr);
+    __builtin_amdgcn_sched_barrier(0);
+    rows_issue(rp, Sp, b.next_states, b.ld_next_states, S, nullptr, 0, 0, row0, b.gather != nullptr, b.gather_capacity, false);
+    request_head_row(hidx);
+  } else {
+    rows_idx(rp, Sp, row0, b.gather);
+    int64_t hidx = row0 + min(hr, IL_TILE_R - 1);
+    if (head_thread && b.gather) hidx = gload(b.gather + row0 + hr);
+    if (ov >= 0) {   // rows first, then the wait; the weights behind it
+      rows_issue(rp, Sp, b.next_states, b.ld_next_states, S, nullptr, 0, 0, row0, b.gather != nullptr, b.gather_capacity, false);
+      request_head_row(hidx);
+      ov_wait(reinterpret_cast<long long*>(d.sync), IL_OV_DWA, ov, ov_grid);
+      IL_ST_GATE(IL_ST_CHAIN);
+    }
+    request_weights();
+    __builtin_amdgcn_sched_barrier(0);
+    if (ov < 0) {
+      rows_issue(rp, Sp, b.next_states, b.ld_next_states, S, nullptr, 0, 0, row0, b.gather != nullptr, b.gather_capacity, false);
+      request_head_row(hidx);
+    }
+    if (half == 0) w3pre = tile_fwd_small_prefetch(net.W3, H, 2 * A, H);
+  }
   // Only the FIRST HALF of the hidden layer's panel is requested here (panel_prefetch_lo), behind every wave's small loads (issue_fence): a wave that issues 16 KB of
   // loads is held at the issue stage until the CU's memory pipeline has taken them - with eight waves doing so ~0.85 us per panel, during which it cannot commit its rows
   // (two whole panels parked in the prologue of the first pair-mode k_policy_critic: a 4.8 us prologue). The second half goes out right before the MFMAs and streams in
@@ -882,7 +918,13 @@ __device__ __forceinline__ void sac_chain_pair_body(il_sac& d, il_batch& b, cons
   const long long ov = rl.overlap ? rl.ov_n : -1;   // >= 0: [IL_SYNC_MAIN_EPOCH] may not count the previous update yet (its last launch is still running on the other stream)
   // (leader acquire: the index arrays are read by no kernel between this launch's start and the draw - the discriminator step that shares them waits for the same counter -
   // so no L2 can hold a pre-draw copy fetched during this launch; 163 workgroups x 8 waves of invalidates here cost the launch 7 us: profiles/r06_soak_under_load.md)
-  if (rl.wait_indices) sync_wait_leader(sy, IL_SYNC_INDICES, (ov >= 0 ? ov : sync_read(sy, IL_SYNC_MAIN_EPOCH)) + 1);
+  // In-order launches: the target is [IL_SYNC_MAIN_EPOCH] + 1, and both words are requested in one batch (one trip to memory, not two dependent ones). actor(s') - the
+  // head of the launch's critical leg - waits inside its role (actor_next_pair), behind the requests of everything that does not depend on the indices.
+  const bool wait_in_role = rl.wait_indices && ov < 0 && id.role == 0;
+  if (rl.wait_indices && !wait_in_role) {
+    if (ov >= 0) sync_wait_leader(sy, IL_SYNC_INDICES, ov + 1);
+    else sync_wait_leader(sy, IL_SYNC_INDICES, sync_request_epoch(sy, IL_SYNC_INDICES));
+  }
   if (id.role == 5) {
     const int G = (int)gridDim.x - chain_pair_workgroups(nt, rl.on, 0), gw = id.tile;
     const int row4 = b.ld_states / 4, lanes = d.batch * row4;
@@ -902,7 +944,7 @@ __device__ __forceinline__ void sac_chain_pair_body(il_sac& d, il_batch& b, cons
   float* slab = d.workspace + ws.x_slab + (size_t)slot * IL_TILE_R * (H / 2);
   unsigned* flag = reinterpret_cast<unsigned*>(d.workspace + ws.x_flag) + slot * IL_CTR_STRIDE;
   if (id.role == 0) {
-    actor_next_pair(d, b, eps_next, id.tile, id.half, smem, slab, flag, ov, rl.overlap);
+    actor_next_pair(d, b, eps_next, id.tile, id.half, smem, slab, flag, ov, rl.overlap, wait_in_role ? sy : nullptr);
     if (id.half == 0) { tile_arrive_through(ctr, 1u); IL_TL(10, 7); }
   } else if (id.role == 1) {
     target_pair(d, b, id.net, id.tile, id.half, smem, slab, flag, ctr, ov, rl.overlap);

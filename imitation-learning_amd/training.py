@@ -780,10 +780,12 @@ class UpdatePlan:
   def staged_rows(self) -> bool:
     """GAIL with the resident sampler on one GPU: the sampler workgroup also copies the drawn agent rows into a dense slab (`stage`) before it signals
     (il_gail_disc_step_draw_staged) - with the early draw that is ~30 us before the update starts - and the forward / critic-loss launch reads them from there
-    (IL_FLAG_SAC_STAGED_ROWS): one global trip in its prologues instead of index -> row. The discriminator step keeps reading through the indices. Measured NEUTRAL on an
+    (IL_FLAG_SAC_STAGED_ROWS): one global trip in its prologues instead of index -> row. The discriminator step keeps reading through the indices. First measured NEUTRAL on an
     interleaved A/B (17.55-17.63k against 17.47-17.64k updates/s, k_sac_chain_pair 22.1-22.3 us either way, profiles/r05_stage_rows_ab.txt): with the indices drawn ~30 us
-    ahead the index -> row trip of the prologues is not what the forward / critic-loss launch waits for. Kept bit-identical and switchable, OFF by default (IL_STAGE_ROWS=1)."""
-    return bool(self.algorithm == 'GAIL' and self.resident_sampler and self.peer_desc is None and not getattr(self, 'data_parallel', False) and os.environ.get('IL_STAGE_ROWS', '0') == '1')
+    ahead the index -> row trip of the prologues was not what the forward / critic-loss launch waited for - its weights' trip stood behind two serialised sync-word trips.
+    With actor(s') requesting its weights ahead of that wait (sac.hip actor_next_pair) the rows bind: 18.38-18.45k against 18.27-18.29k updates/s, five alternating runs
+    each, disjoint (profiles/chain_legs.txt). Bit-identical and switchable, ON by default since then (IL_STAGE_ROWS=0: rows through the indices)."""
+    return bool(self.algorithm == 'GAIL' and self.resident_sampler and self.peer_desc is None and not getattr(self, 'data_parallel', False) and os.environ.get('IL_STAGE_ROWS', '1') != '0')
 
   def _staged_batch(self):
     if getattr(self, '_stage_desc', None) is None:
