@@ -189,6 +189,7 @@ _SIGNATURES = {
     'il_sac_update': (C.c_int, [C.POINTER(Sac), C.POINTER(Batch), _P, _P, _P, _P, C.c_uint32, _P]),
     'il_sac_update_gather': (C.c_int, [C.POINTER(Sac), C.POINTER(Batch), C.POINTER(Batch), _P, C.POINTER(Disc), _P, _P, _P, _P, _P, C.c_uint32, _P]),
     'il_sac_update_gather_overlap': (C.c_int, [C.POINTER(Sac), C.POINTER(Batch), C.POINTER(Batch), _P, C.POINTER(Disc), _P, _P, _P, _P, _P, C.c_uint32, _P, _P]),
+    'il_sac_update_gather_spec': (C.c_int, [C.POINTER(Sac), C.POINTER(Batch), C.POINTER(Batch), _P, C.POINTER(Disc), _P, _P, _P, _P, _P, _P, C.c_uint32, _P]),
     'il_sac_overlap_enter': (C.c_int, [C.POINTER(Sac), _P]),
     'il_sync_clear_poison': (C.c_int, [_P, _P]),
     'il_sync_layout_ex': (None, [C.POINTER(C.c_int32), C.c_int32]),
@@ -234,6 +235,8 @@ _SIGNATURES = {
     'il_bc_step_general': (C.c_int, [_P, _P, C.POINTER(Adam), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Batch), _P, C.c_int64, _P, C.c_uint32, _P]),
     'il_gail_disc_step_draw': (C.c_int, [C.POINTER(Disc), C.POINTER(Batch), C.POINTER(Batch), _P, _P, _P, _P, _P, C.c_uint32, _P]),
     'il_gail_disc_step_draw_staged': (C.c_int, [C.POINTER(Disc), C.POINTER(Batch), C.POINTER(Batch), _P, _P, _P, _P, _P, _P, C.c_uint32, _P]),
+    'il_gail_disc_step_draw_staged2': (C.c_int, [C.POINTER(Disc), C.POINTER(Batch), C.POINTER(Batch), _P, _P, _P, _P, _P, _P, _P, C.c_uint32, _P]),
+    'il_stage_next_row_floats': (C.c_int32, [C.c_int32]),
     'il_gail_disc_step_draw_peer': (C.c_int, [C.POINTER(Disc), C.POINTER(Batch), C.POINTER(Batch), _P, _P, _P, _P, _P, C.c_uint32, C.POINTER(PeerBucket), _P]),
     'il_gail_apply_grads': (C.c_int, [C.POINTER(Disc), _P]),
     'il_gail_reward': (C.c_int, [C.POINTER(Disc), C.POINTER(Batch), _P, _P, _P, _P]),
@@ -304,9 +307,10 @@ def sync_layout():
 
 
 def sync_layout_ex():
-  """sync_layout() followed by (poison index, first stage-epoch index, first stage-ticket index, main-epoch index): include/il_hip.h IL_SYNC_POISON / IL_SYNC_OV_EPOCH / IL_SYNC_OV_TICKET."""
-  out = (C.c_int32 * 10)()
-  lib().il_sync_layout_ex(out, 10)
+  """sync_layout() followed by (poison index, first stage-epoch index, first stage-ticket index, main-epoch index, index-draw index, draw-seen index, vouched index):
+  include/il_hip.h IL_SYNC_POISON / IL_SYNC_OV_EPOCH / IL_SYNC_OV_TICKET / IL_SYNC_MAIN_EPOCH / IL_SYNC_INDICES / IL_SYNC_DRAW_SEEN / IL_SYNC_VOUCHED."""
+  out = (C.c_int32 * 13)()
+  lib().il_sync_layout_ex(out, 13)
   return tuple(int(v) for v in out)
 
 

@@ -179,7 +179,7 @@ __device__ __forceinline__ void gail_grad_body(il_disc d, il_batch pol, il_batch
   const int has_sampler = sa.state != nullptr;
   if (has_sampler && (int)blockIdx.x == (int)gridDim.x - 1) {
     if (blockIdx.y == 0) {
-      MtStage stg = sa.stage; stg.ring = as_global(stg.ring); stg.rows = as_global(stg.rows);
+      MtStage stg = sa.stage; stg.ring = as_global(stg.ring); stg.rows = as_global(stg.rows); stg.nxt = as_global(stg.nxt); stg.absb = as_global(stg.absb); stg.next = as_global(stg.next);
       mt_sample_update(*reinterpret_cast<MtShared*>(smem), as_global(sa.state), sa.n, as_global(sa.rs_a), as_global(sa.idx_a), as_global(sa.rs_b), as_global(sa.idx_b),
                        reinterpret_cast<long long*>(as_global(d.sync)), 1, stg);
     }
@@ -670,7 +670,7 @@ extern "C" int il_gail_disc_step(const il_disc* d, const il_batch* pol, const il
 }
 
 static int gail_disc_step_draw_impl(const il_disc* d, const il_batch* pol, const il_batch* exp, uint32_t* mt_state_dev, const int64_t* ring_state_a, int32_t* idx_a,
-                                    const int64_t* ring_state_b, int32_t* idx_b, uint32_t flags, const il_peer_bucket* peer, il_stream_t stream_, float* stage_rows = nullptr) {
+                                    const int64_t* ring_state_b, int32_t* idx_b, uint32_t flags, const il_peer_bucket* peer, il_stream_t stream_, float* stage_rows = nullptr, float* stage_next = nullptr) {
   if (int rc = check_disc(d)) return rc;
   IL_CHECK_ARG(pol && exp && pol->n == d->batch && exp->n == d->batch && pol->gather && exp->gather, "il_gail_disc_step_draw: both batches must be rings read through il_batch.gather");
   IL_CHECK_ARG(d->sync && mt_state_dev && ring_state_a && idx_a && ring_state_b && idx_b, "il_gail_disc_step_draw: the il_sync counters, the generator state and both rings' states / index arrays are required");
@@ -685,6 +685,12 @@ static int gail_disc_step_draw_impl(const il_disc* d, const il_batch* pol, const
   if (stage_rows) {   // the policy batch IS the agent ring read through idx_a: its packed rows start at `states`
     IL_CHECK_ARG(pol->ld_states % 4 == 0 && (reinterpret_cast<uintptr_t>(pol->states) & 15) == 0 && (reinterpret_cast<uintptr_t>(stage_rows) & 15) == 0, "il_gail_disc_step_draw_staged: packed rows of whole 16-byte lanes");
     sa.stage = MtStage{pol->states, stage_rows, (long long)pol->gather_capacity, pol->ld_states / 4};
+  }
+  if (stage_next) {   // actor(s')'s private slab: next_states and absorbing of the drawn agent rows, whole 128-byte lines per row
+    IL_CHECK_ARG(pol->next_states && pol->absorbing && pol->gather_capacity > 0 && (reinterpret_cast<uintptr_t>(stage_next) & 15) == 0, "il_gail_disc_step_draw_staged2: the policy ring's next_states / absorbing and a 16-byte aligned slab");
+    sa.stage.capacity = (long long)pol->gather_capacity;
+    sa.stage.nxt = pol->next_states; sa.stage.absb = pol->absorbing; sa.stage.next = stage_next;
+    sa.stage.ld_nxt = pol->ld_next_states; sa.stage.ld_absb = pol->ld_absorbing; sa.stage.S = d->state_dim; sa.stage.next_ld = stage_next_row_floats(d->state_dim);
   }
   { IL_TRACE("k_gail_grad", st); k_gail_grad<<<dim3(nt + 1, disc_calls(*d)), 256, lds, st>>>(*d, *pol, *exp, nullptr, il_gail_extra{}, nullptr, nullptr, nullptr, sa, 0); }
   const int64_t P = disc_layout(D, d->hidden, d->spectral_norm).P;
@@ -708,6 +714,12 @@ extern "C" int il_gail_disc_step_draw_staged(const il_disc* d, const il_batch* p
                                              const int64_t* ring_state_b, int32_t* idx_b, float* stage_rows, uint32_t flags, il_stream_t stream_) {
   IL_CHECK_ARG(stage_rows, "il_gail_disc_step_draw_staged: null staging slab");
   return gail_disc_step_draw_impl(d, pol, exp, mt_state_dev, ring_state_a, idx_a, ring_state_b, idx_b, flags, nullptr, stream_, stage_rows);
+}
+extern "C" int32_t il_stage_next_row_floats(int32_t state_dim) { return stage_next_row_floats(state_dim); }
+extern "C" int il_gail_disc_step_draw_staged2(const il_disc* d, const il_batch* pol, const il_batch* exp, uint32_t* mt_state_dev, const int64_t* ring_state_a, int32_t* idx_a,
+                                              const int64_t* ring_state_b, int32_t* idx_b, float* stage_rows, float* stage_next, uint32_t flags, il_stream_t stream_) {
+  IL_CHECK_ARG(stage_rows && stage_next, "il_gail_disc_step_draw_staged2: null staging slab");
+  return gail_disc_step_draw_impl(d, pol, exp, mt_state_dev, ring_state_a, idx_a, ring_state_b, idx_b, flags, nullptr, stream_, stage_rows, stage_next);
 }
 extern "C" int il_gail_disc_step_draw_peer(const il_disc* d, const il_batch* pol, const il_batch* exp, uint32_t* mt_state_dev, const int64_t* ring_state_a, int32_t* idx_a,
                                            const int64_t* ring_state_b, int32_t* idx_b, uint32_t flags, const il_peer_bucket* peer, il_stream_t stream_) {

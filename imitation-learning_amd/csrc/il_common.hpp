@@ -59,6 +59,9 @@ __device__ __forceinline__ void wstore4(float* base, int64_t off, const f32x4& v
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(il_u32x4, v), rs, (int)(off * 4), 0, 17);       // sc0 | sc1
 }
 
+// floats per row of actor(s')'s private row slab (include/il_hip.h il_stage_next_row_floats; written by mt_device.hpp MtStage.next, read by sac.hip actor_next_pair):
+// next_states[0 .. S), absorbing, zeros up to whole 128-byte lines
+__host__ __device__ static inline int stage_next_row_floats(int state_dim) { return (state_dim + 1 + 31) & ~31; }
 // One float written through / read below this CU's L1 (the fence-free hand-offs of the pair-mode kernels: a few scalars per lane next to a relaxed arrival counter)
 __device__ __forceinline__ void wstore1(float* base, int64_t off, float v) {
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7ffffff0, 0x00020000);

@@ -476,6 +476,25 @@ __device__ __forceinline__ bool l1_rows_aligned(const float* W, int Kw) { return
 __device__ __forceinline__ void l1_prefetch(L1Pre& w, const float* __restrict__ W, int Kw, int Kpad, int N) {   // l1_rows_aligned(W, Kw)
   if (Kw == Kpad) l1_prefetch_impl<0>(w, W, Kw, Kw, Kpad, N); else l1_prefetch_impl<1>(w, W, Kw, Kw, Kpad, N);
 }
+// ... and when they are only 8-byte aligned (Kw even, not a multiple of 4: the actor at HalfCheetah dims, Kw = 18): the same operand lanes as two 2-float loads each,
+// straight from the parameter matrix. Lane (j, g) of k-block u holds columns 16 u + 4 g .. + 3 of row c0 + j; a pair that starts at or beyond Kw - the second pair of
+// the k-block that straddles Kw (Kw = 4 m + 2), both pairs further right - is read from the row's last pair instead (address clamped, never past the row). What those
+// lanes hold meets the zero-padded columns of Xs: exact +0 products, as load4<1>'s clamped lanes. Operands and MFMA order are l1_compute_regs': same bits as the LDS form.
+typedef float l1_f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ bool l1_rows_aligned8(const float* W, int Kw) { return (Kw & 1) == 0 && Kw >= 2 && (reinterpret_cast<uintptr_t>(W) & 7) == 0; }
+__device__ __forceinline__ void l1_prefetch8(L1Pre& w, const float* __restrict__ W, int Kw, int Kpad, int N) {   // l1_rows_aligned8(W, Kw)
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6, j = lane & 15, g = lane >> 4;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const float* wr = W + (size_t)(min((wave + q * nw) * 16, N - 16) + j) * Kw;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) if (16 * u < Kpad) {
+      const int k0 = 16 * u + 4 * g;
+      const l1_f32x2 lo = *(const __attribute__((address_space(1))) l1_f32x2*)(wr + min(k0, Kw - 2)), hi = *(const __attribute__((address_space(1))) l1_f32x2*)(wr + min(k0 + 2, Kw - 2));
+      w.b[q][u] = f32x4{lo[0], lo[1], hi[0], hi[1]};
+    }
+  }
+}
 template <class Epi>
 __device__ __forceinline__ void l1_compute_regs(const L1Pre& w, const float* Xs, int ldx, int Kpad, int N, Epi epi) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6, j = lane & 15, g = lane >> 4;

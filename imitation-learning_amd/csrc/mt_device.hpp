@@ -103,7 +103,10 @@ __device__ __forceinline__ void mt_draw(MtShared& sh, const int64_t* __restrict_
 // `stage` (round 5, il_gail_disc_step_draw_staged): after the draw the workgroup also copies the n drawn AGENT rows (row4 16-byte lanes each, ring rows at `stage_ring`,
 // indices clamped like il_replay_gather) into the dense slab `stage` BEFORE it signals: with the early draw (IL_SYNC_CHAIN_DONE) this happens tens of microseconds ahead
 // of the next update, whose forward / critic-loss launch then reads dense rows - one global trip in its prologues instead of index -> row.
-struct MtStage { const float* ring; float* rows; long long capacity; int row4; };
+// `next` (il_gail_disc_step_draw_staged2): per drawn agent row also next_states[0 .. S) followed by `absorbing`, zero-padded to next_ld floats (whole 128-byte lines),
+// into the slab that only actor(s') of the next forward / critic-loss launch reads (sac.hip actor_next_pair requests it AHEAD of its wait for the draw: lines that no
+// other role touches, read below the caches). Written through; sync_signal drains every wave before the arrival.
+struct MtStage { const float* ring; float* rows; long long capacity; int row4; const float* nxt; const float* absb; float* next; int ld_nxt, ld_absb, S, next_ld; };
 __device__ __forceinline__ void mt_sample_update(MtShared& sh, uint32_t* __restrict__ state, int n, const int64_t* __restrict__ rs_a, int32_t* __restrict__ idx_a,
                                                  const int64_t* __restrict__ rs_b, int32_t* __restrict__ idx_b, long long* __restrict__ sync, int resident, MtStage stage = MtStage{}) {
   const int tid = threadIdx.x;
@@ -128,9 +131,9 @@ __device__ __forceinline__ void mt_sample_update(MtShared& sh, uint32_t* __restr
   mt_draw(sh, rs_a, n, idx_a);
   if (rs_b) { __syncthreads(); mt_draw(sh, rs_b, n, idx_b); }
   IL_TL(0, 3);
+  typedef float st_f32x4 __attribute__((ext_vector_type(4)));
   if (stage.rows) {
     __syncthreads();   // idx_a as written by this workgroup's threads above
-    typedef float st_f32x4 __attribute__((ext_vector_type(4)));
     const st_f32x4* src = reinterpret_cast<const st_f32x4*>(stage.ring);
     st_f32x4* dst = reinterpret_cast<st_f32x4*>(stage.rows);
     const int lanes = n * stage.row4;
@@ -142,6 +145,26 @@ __device__ __forceinline__ void mt_sample_update(MtShared& sh, uint32_t* __restr
       for (int u = 0; u < 4; ++u) { const int i = min(i0 + u * 256, lanes - 1); v[u] = src[sr[u] * stage.row4 + i % stage.row4]; }
 #pragma unroll
       for (int u = 0; u < 4; ++u) { const int i = i0 + u * 256; if (i < lanes) dst[i] = v[u]; }
+    }
+  }
+  if (stage.next) {
+    if (!stage.rows) __syncthreads();   // idx_a as written above
+    const int S = stage.S, l4 = stage.next_ld / 4, lanes = n * l4;
+    for (int i0 = tid; i0 < lanes; i0 += 2 * 256) {   // two 16-byte lanes per thread and trip: indices, then their eight elements, requested together
+      long long sr[2]; float v[2][4];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) { const int i = min(i0 + u * 256, lanes - 1); const long long s_ = idx_a[i / l4]; sr[u] = s_ < 0 ? 0 : (s_ >= stage.capacity ? stage.capacity - 1 : s_); }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int i = min(i0 + u * 256, lanes - 1), k0 = 4 * (i % l4);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { const int k = k0 + c; v[u][c] = k < S ? stage.nxt[sr[u] * stage.ld_nxt + k] : stage.absb[sr[u] * stage.ld_absb]; }   // (k > S: loaded, not used)
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int i = i0 + u * 256, k0 = 4 * (i % l4);
+        if (i < lanes) { st_f32x4 o; for (int c = 0; c < 4; ++c) o[c] = k0 + c <= S ? v[u][c] : 0.f; wstore4<true>(stage.next, 4 * (int64_t)i, o); }
+      }
     }
   }
   if (sync) sync_signal(sync + IL_SYNC_INDICES);   // both index arrays (and the staged rows) are in place (a consumer that gathers its own rows need not wait for k_gather2)

@@ -440,7 +440,7 @@ __device__ __forceinline__ void critic_bwd_resident_gemm(const il_sac& d, int k,
 }
 // relabel: the rewards of this tile are the discriminator `dd`'s prediction on (s, a) - the rows still sit in Xs - computed here once its AdamW step of
 // this update is complete ([IL_SYNC_PARAMS], n_reduce workgroups per step); otherwise dense `rewards` or the batch's own reward field.
-struct ChainRelabel { il_disc dd; int on, n_reduce; float* out; int fwd_only; int wait_indices; int local_rewards; int reserved_[2]; int early_draw; int overlap; long long ov_n; };   // overlap: 0 = off, else the grid size of the actor optimiser launch this launch waits for   // overlap (k_sac_chain_pair, il_sac_update_gather_overlap): the previous update's actor optimiser launch may still be running on the other stream - ov_n = this stage's own epoch (ov_own, set by the kernel) stands in for [IL_SYNC_MAIN_EPOCH] and the roles wait for [IL_SYNC_OV_EPOCH + IL_OV_DWA] >= ov_n where they first need what that launch writes   // early_draw: publish [IL_SYNC_CHAIN_WGS] (IL_EARLY_DRAW=0: the resident sampler waits for the previous update's end, as in round 4)   // reserved_: unused padding, kept so that the size and the field offsets stay as they were: k_sac_chain_pair takes this struct by value and its register allocation depends on the argument offsets (8 bytes shorter, it compiled with 20 bytes of scratch instead of none)   // wait_indices: IL_FLAG_SAC_WAIT_INDICES; local_rewards: il_sac_update_gather without `rewards` / `relabel` (the ring's reward field: nothing to wait for)   // fwd_only: the forward kernels only (IL_FLAG_SAC_FORWARD_ONLY / data-parallel phase 0): no critic backward
+struct ChainRelabel { il_disc dd; int on, n_reduce; float* out; int fwd_only; int wait_indices; int local_rewards; unsigned spec_lo, spec_hi; int early_draw; int overlap; long long ov_n; };   // overlap: 0 = off, else the grid size of the actor optimiser launch this launch waits for   // overlap (k_sac_chain_pair, il_sac_update_gather_overlap): the previous update's actor optimiser launch may still be running on the other stream - ov_n = this stage's own epoch (ov_own, set by the kernel) stands in for [IL_SYNC_MAIN_EPOCH] and the roles wait for [IL_SYNC_OV_EPOCH + IL_OV_DWA] >= ov_n where they first need what that launch writes   // early_draw: publish [IL_SYNC_CHAIN_WGS] (IL_EARLY_DRAW=0: the resident sampler waits for the previous update's end, as in round 4)   // spec_lo / spec_hi: the address of actor(s')'s private row slab (il_sac_update_gather_spec; 0 = none), as two words in what used to be padding - the size and the field offsets stay as they were: k_sac_chain_pair takes this struct by value and its register allocation depends on the argument offsets (8 bytes shorter, it compiled with 20 bytes of scratch instead of none)   // wait_indices: IL_FLAG_SAC_WAIT_INDICES; local_rewards: il_sac_update_gather without `rewards` / `relabel` (the ring's reward field: nothing to wait for)   // fwd_only: the forward kernels only (IL_FLAG_SAC_FORWARD_ONLY / data-parallel phase 0): no critic backward
 // Runs between the critic's own work and its wait for the targets: the discriminator's step usually lands while the targets are still being computed,
 // so the relabel stays off the critical path. Leaves the tile's rewards in LDS (rew16) for critic_bwd_resident_scale.
 __device__ __forceinline__ void critic_relabel_tile(const il_sac& d, const ChainRelabel& rl, int k, int tile, float* smem) {
@@ -654,8 +654,19 @@ __device__ __forceinline__ float* pair_w1s(float* smem, int in_pad, int H) { ret
 // as they arrive; only the row indices, the rows and the head threads' `absorbing` stay behind the wait. The polling wave requests its weights ahead of the wait like
 // the others: its acquire waits for them (a fence waits for every load of its wave), but they travel with the words; requested behind the acquire from a second site
 // in the code, the compiler parked them in other registers and waited for them in front of the row indices - a trip more, not less.
+// spec != NULL (il_sac_update_gather_spec; wait_sy != NULL, staged rows): the tile's rows and the head threads' `absorbing` come from the private slab the sampler staged
+// beside the dense one (mt_device.hpp MtStage.next: [row][next_ld] = s', absorbing, zeros) and are requested in the FIRST batch, with [IL_SYNC_DRAW_SEEN] next to the two
+// sync words. That word says what the previous update's tail - which precedes this launch in stream order - saw of [IL_SYNC_INDICES]: at or beyond this launch's target,
+// the draw (slab included, written through and drained ahead of its signal) was in memory before this launch began, the wait falls through on its first look and the
+// rows requested ahead of it are the rows. Otherwise the wait runs as it always did and the same loads go out again behind it; the first ones are dropped. The slab is
+// read with sc0 sc1 buffer loads only, the form profiles/r06_l2_stale_probe.txt never saw return an earlier value, and no other role reads its lines: neither path
+// rests on what a cache holds.
+// W1F, the form of the first layer's weights, is a TEMPLATE parameter (0: through LDS, 1: 16-byte register lanes, 2: 8-byte register lanes; chosen once per launch from
+// the state width and W1's address, actor_next_pair_w1f): as a run-time branch inside request_weights the three forms' destination registers overlapped, and where they
+// joined the compiler waited for everything outstanding (vmcnt(0)) - the sync words and the first W1 lanes - before it issued the biases, the head lanes and the rows.
+template <int W1F>
 __device__ __forceinline__ void actor_next_pair(const il_sac& d, const il_batch& b, const float* __restrict__ eps_next, int tile, int half, float* smem, float* slab, unsigned* flag, long long ov = -1, int ov_grid = 0,
-                                                long long* wait_sy = nullptr) {
+                                                long long* wait_sy = nullptr, const float* spec = nullptr) {
   const int S = d.state_dim, A = d.action_dim, H = d.hidden, B = d.batch;
   const int row0 = tile * IL_TILE_R;
   const int Sp = round_up16(S), ldx = Sp + 4, ldh = H + 4, ldw1 = Sp + 4;
@@ -671,28 +682,51 @@ __device__ __forceinline__ void actor_next_pair(const il_sac& d, const il_batch&
   // this wait reads - and ignores - the same two offsets of the workspace's head, which pair mode's activations make far larger. The announce below is younger: the
   // compare does not wait for it.)
   const SyncEpochWords sw = sync_request_epoch(split ? wait_sy : reinterpret_cast<const long long*>(W), IL_SYNC_INDICES);
+  const long long draw_seen = sync_read(split ? wait_sy : reinterpret_cast<const long long*>(W), IL_SYNC_DRAW_SEEN);   // (the epoch's line; like the two above: every thread, no branch)
   if (half == 0) pair_announce(flag);
   // requests, smallest first: row indices, W1, biases, the rows, then the hidden layer's panel
   RowsPre rp;
   const bool head_thread = half == 0 && tid < IL_TILE_R * A;
   const int hr = tid / A, hc = tid - hr * A;
   float absorb_pre = 0.f;
+  bool count_vouched = false;
   const int w1_lanes = H * S / 4;
-  const bool w1_regs = l1_rows_aligned(net.W1, S);
+  constexpr bool w1_regs = W1F != 0;
   W1Pre w1; L1Pre w1r;
   float pb1a = 0.f, pb1b = 0.f, pb2 = 0.f;
   uint32_t nctr = 0u;
   SmallPre w3pre = {};
   auto request_weights = [&] {
-    if (w1_regs) l1_prefetch(w1r, net.W1, S, Sp, H); else w1_issue(w1, net.W1, w1_lanes);
+    if (W1F == 1) l1_prefetch(w1r, net.W1, S, Sp, H); else if (W1F == 2) l1_prefetch8(w1r, net.W1, S, Sp, H); else w1_issue(w1, net.W1, w1_lanes);
     pb1a = gload(net.b1 + wave * 16 + j); pb1b = gload(net.b1 + min((wave + nw) * 16 + j, H - 1)); pb2 = gload(net.b2 + t2 * 16 + j);
     nctr = (half == 0 && d.noise_counter) ? gload(d.noise_counter) : 0u;
   };
   auto request_head_row = [&](int64_t hidx) {
     if (head_thread) { if (b.gather) hidx = hidx < 0 ? 0 : (hidx >= b.gather_capacity ? b.gather_capacity - 1 : hidx); absorb_pre = gload(b.absorbing + (size_t)hidx * b.ld_absorbing); }
   };
-  // (the two forms share no control flow between the sync words and the panel: a join in between made the compiler wait for the words where the paths met)
-  if (split) {
+  // the private slab's loads (spec): element (r, k) of the tile -> rp.v, the head threads' absorbing; same lanes, same clamps as rows_issue on a dense batch
+  const int next_ld = stage_next_row_floats(S);   // (the sampler's MtStage.next_ld: one helper, il_common.hpp)
+  auto request_spec_rows = [&] {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int i = min(q * (int)blockDim.x + tid, IL_TILE_R * Sp - 1), r = fastdiv(i, fastdiv_magic(Sp)), k = i - r * Sp;
+      rp.v[q] = sload1(spec, (int64_t)(row0 + r) * next_ld + min(k, S - 1));
+    }
+    if (head_thread) absorb_pre = sload1(spec, (int64_t)(row0 + hr) * next_ld + S);
+  };
+  // (the forms share no control flow between the sync words and the panel: a join in between made the compiler wait for the words where the paths met)
+  if (split && spec) {
+    request_weights();
+    if (half == 0) w3pre = tile_fwd_small_prefetch(net.W3, H, 2 * A, H);
+    request_spec_rows();
+    __builtin_amdgcn_sched_barrier(0);
+    // (workgroup-uniform, and the same in every workgroup of the launch: neither word can change while this launch runs - the epoch is bumped by the update's last
+    // launch, [IL_SYNC_DRAW_SEEN] by that same thread just ahead of it)
+    const bool vouched = draw_seen >= sw.epoch + 1;
+    sync_wait_leader(wait_sy, IL_SYNC_INDICES, sw);   // (vouched: [IL_SYNC_INDICES] >= [IL_SYNC_DRAW_SEEN] was requested with it - falls through on its first look)
+    if (!vouched) request_spec_rows();
+    count_vouched = vouched && tile == 0 && half == 0 && tid == 0;   // ([IL_SYNC_VOUCHED] is bumped further down: here, the branch around the add ended in a vmcnt(0) in front of the panel)
+  } else if (split) {
     request_weights();
     if (half == 0) w3pre = tile_fwd_small_prefetch(net.W3, H, 2 * A, H);
     __builtin_amdgcn_sched_barrier(0);
@@ -757,6 +791,7 @@ __device__ __forceinline__ void actor_next_pair(const il_sac& d, const il_batch&
   });
   IL_TL(10, 4);
   if (half == 1) { pair_publish(flag); IL_TL(10, 7); return; }
+  if (count_vouched) __hip_atomic_fetch_add(wait_sy + IL_SYNC_VOUCHED, 1LL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (one thread of tile 0's consumer half; no returned value: fire and forget)
   // the noise of the head (Philox + Box-Muller: ~1 us of dependent ALU work) is drawn while the partner's half is on its way
   float e_pre = 0.f;
   if (head_thread) e_pre = eps_next ? eps_next[(size_t)(row0 + hr) * A + hc] : philox_normal(d.noise_seed, nctr, IL_STREAM_EPS_NEXT, (uint32_t)((row0 + hr) * A + hc));
@@ -944,7 +979,12 @@ __device__ __forceinline__ void sac_chain_pair_body(il_sac& d, il_batch& b, cons
   float* slab = d.workspace + ws.x_slab + (size_t)slot * IL_TILE_R * (H / 2);
   unsigned* flag = reinterpret_cast<unsigned*>(d.workspace + ws.x_flag) + slot * IL_CTR_STRIDE;
   if (id.role == 0) {
-    actor_next_pair(d, b, eps_next, id.tile, id.half, smem, slab, flag, ov, rl.overlap, wait_in_role ? sy : nullptr);
+    const float* spec = as_global(reinterpret_cast<const float*>(((unsigned long long)rl.spec_hi << 32) | rl.spec_lo));
+    // (kernel arguments only: a scalar branch ahead of every request, each form straight-line from its sync words to its panel)
+    const float* aw1 = mlp_view(d.actor, d.state_dim, H, 2 * d.action_dim).W1;
+    if (l1_rows_aligned(aw1, d.state_dim)) actor_next_pair<1>(d, b, eps_next, id.tile, id.half, smem, slab, flag, ov, rl.overlap, wait_in_role ? sy : nullptr, wait_in_role ? spec : nullptr);
+    else if (l1_rows_aligned8(aw1, d.state_dim)) actor_next_pair<2>(d, b, eps_next, id.tile, id.half, smem, slab, flag, ov, rl.overlap, wait_in_role ? sy : nullptr, wait_in_role ? spec : nullptr);
+    else actor_next_pair<0>(d, b, eps_next, id.tile, id.half, smem, slab, flag, ov, rl.overlap, wait_in_role ? sy : nullptr, wait_in_role ? spec : nullptr);
     if (id.half == 0) { tile_arrive_through(ctr, 1u); IL_TL(10, 7); }
   } else if (id.role == 1) {
     target_pair(d, b, id.net, id.tile, id.half, smem, slab, flag, ctr, ov, rl.overlap);
@@ -1814,8 +1854,9 @@ __device__ __forceinline__ void dw_bias(const DwArgs& a, const adam_consts& ac, 
 template <bool PEER, bool FLAGGED = false>
 __device__ __forceinline__ void dw_tail_alpha(const DwArgs& a, const DwPeer* pp, bool poisoned = false, const long long* sync = nullptr) {
   if (a.log_alpha && threadIdx.x == 0) {
-    long long poison = 0;
-    if (FLAGGED) poison = sync_read(sync, IL_SYNC_POISON);
+    long long poison = 0, drawn = 0;
+    // (FLAGGED: [IL_SYNC_INDICES] rides in the same batch - what this thread saw of the NEXT update's draw goes into [IL_SYNC_DRAW_SEEN] below, ahead of the epoch's release)
+    if (FLAGGED) { poison = sync_read(sync, IL_SYNC_POISON); drawn = sync_read(sync, IL_SYNC_INDICES); }
     const float la = gload(a.log_alpha);
     float mm = 0.f, vv = 0.f; f32x4 c_lo = zero4(), c_hi = zero4();
     if (!a.grads_only) { mm = gload(a.alpha_opt.m); vv = gload(a.alpha_opt.v); const float* f = reinterpret_cast<const float*>(a.alpha_opt.step) + 4; c_lo = gload4(f); c_hi = gload4(f + 4); }
@@ -1844,6 +1885,9 @@ __device__ __forceinline__ void dw_tail_alpha(const DwArgs& a, const DwPeer* pp,
     // (with il_sync counters the bumped counter is read by the NEXT update's discriminator launch, resident on the other stream: written through and drained like every
     // other in-launch hand-off, profiles/r06_soak_under_load.md)
     if (a.noise_counter) { if (a.sync) { wstore1(reinterpret_cast<float*>(a.noise_counter), 0, __uint_as_float(nc + 1u)); sync_drain_stores(); } else a.noise_counter[0] = nc + 1u; }
+    // [IL_SYNC_DRAW_SEEN] (include/il_hip.h): this thread precedes the next forward / critic-loss launch in stream order and has observed `drawn` draws - with the early draw
+    // that already counts the next update's, whose actor(s') then uses the rows it requested ahead of its wait (actor_next_pair). Same line as the epoch, ahead of its release.
+    if (FLAGGED) __hip_atomic_store(const_cast<long long*>(sync) + IL_SYNC_DRAW_SEEN, drawn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // this update's SAC half is done. Release: the resident sampler and, behind it, the discriminator kernels of the NEXT update start from this signal and read the noise counter bumped above
     if (a.sync) __hip_atomic_fetch_add(reinterpret_cast<long long*>(a.sync) + IL_SYNC_MAIN_EPOCH, 1LL, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
   }
@@ -2492,7 +2536,7 @@ static int check_peer_jobs(const il_peer_bucket* x, int64_t n, int32_t jobs, con
 }
 static int sac_update_gather_impl(const il_sac* d, const il_batch* rows, const il_batch* ring, const float* rewards, const il_disc* relabel, float* rewards_out,
                                   const float* eps_next, const float* eps_cur, float* out_logp, float* out_q, uint32_t flags, const il_peer_bucket* peer_critic,
-                                  const il_peer_bucket* peer_actor, il_stream_t stream_, il_stream_t stream_b_ = nullptr) {   // stream_b_: il_sac_update_gather_overlap
+                                  const il_peer_bucket* peer_actor, il_stream_t stream_, il_stream_t stream_b_ = nullptr, const float* next_rows = nullptr) {   // stream_b_: il_sac_update_gather_overlap; next_rows: il_sac_update_gather_spec
   if (int rc = check_sac(d, rows)) return rc;
   if (peer_critic || peer_actor) {
     IL_CHECK_ARG(peer_critic && peer_actor && !(flags & IL_FLAG_GRADS_ONLY), "il_sac_update_gather_peer: both buckets, and no IL_FLAG_GRADS_ONLY (the optimiser steps run inside)");
@@ -2515,8 +2559,14 @@ static int sac_update_gather_impl(const il_sac* d, const il_batch* rows, const i
   { static const int early = [] { const char* e = getenv("IL_EARLY_DRAW"); return e && e[0] == '0' ? 0 : 1; }(); rl.early_draw = early; }
   if (flags & IL_FLAG_SAC_STAGED_ROWS) {   // `ring` = the dense slab the resident sampler staged this update's rows into (il_gail_disc_step_draw_staged): no index trip
     IL_CHECK_ARG(ring && !ring->gather && ring->n == d->batch && (flags & IL_FLAG_SAC_WAIT_INDICES), "il_sac_update_gather: IL_FLAG_SAC_STAGED_ROWS takes a dense batch of %d rows and waits for [IL_SYNC_INDICES]", d->batch);
-  } else
+    if (next_rows) {
+      IL_CHECK_ARG((reinterpret_cast<uintptr_t>(next_rows) & 15) == 0 && !stream_b_ && !peer_critic && !peer_actor, "il_sac_update_gather_spec: a 16-byte aligned slab; in-order single-GPU launches only");
+      rl.spec_lo = (unsigned)(reinterpret_cast<uintptr_t>(next_rows) & 0xffffffffu); rl.spec_hi = (unsigned)(reinterpret_cast<uintptr_t>(next_rows) >> 32);
+    }
+  } else {
+  IL_CHECK_ARG(!next_rows, "il_sac_update_gather_spec: needs IL_FLAG_SAC_STAGED_ROWS");
   IL_CHECK_ARG(ring && ring->gather && ring->gather_capacity > 0 && ring->n == d->batch, "il_sac_update_gather: `ring` must carry the %d drawn indices (il_batch.gather)", d->batch);
+  }
   IL_CHECK_ARG(rows->states && ring->states && rows->ld_states == ring->ld_states && ring->ld_states % 4 == 0, "il_sac_update_gather: rows / ring must be packed rows of the same width");
   IL_CHECK_ARG(!(flags & (IL_FLAG_SAC_SKIP_FORWARD | IL_FLAG_SAC_FORWARD_ONLY)), "il_sac_update_gather: whole updates (or, with IL_FLAG_GRADS_ONLY, everything up to the critic gradients)");
   IL_CHECK_ARG(!(flags & IL_FLAG_GRADS_ONLY) || d->critic_grad, "il_sac_update_gather: IL_FLAG_GRADS_ONLY needs the critic_grad arena");
@@ -2566,6 +2616,11 @@ static int sac_update_gather_impl(const il_sac* d, const il_batch* rows, const i
 extern "C" int il_sac_update_gather(const il_sac* d, const il_batch* rows, const il_batch* ring, const float* rewards, const il_disc* relabel, float* rewards_out,
                                     const float* eps_next, const float* eps_cur, float* out_logp, float* out_q, uint32_t flags, il_stream_t stream_) {
   return sac_update_gather_impl(d, rows, ring, rewards, relabel, rewards_out, eps_next, eps_cur, out_logp, out_q, flags, nullptr, nullptr, stream_);
+}
+extern "C" int il_sac_update_gather_spec(const il_sac* d, const il_batch* rows, const il_batch* ring, const float* rewards, const il_disc* relabel, float* rewards_out,
+                                         const float* eps_next, const float* eps_cur, float* out_logp, float* out_q, const float* next_rows, uint32_t flags, il_stream_t stream_) {
+  IL_CHECK_ARG(next_rows, "il_sac_update_gather_spec: null row slab");
+  return sac_update_gather_impl(d, rows, ring, rewards, relabel, rewards_out, eps_next, eps_cur, out_logp, out_q, flags, nullptr, nullptr, stream_, nullptr, next_rows);
 }
 extern "C" int il_sac_update_gather_overlap(const il_sac* d, const il_batch* rows, const il_batch* ring, const float* rewards, const il_disc* relabel, float* rewards_out,
                                             const float* eps_next, const float* eps_cur, float* out_logp, float* out_q, uint32_t flags, il_stream_t stream_a, il_stream_t stream_b) {

@@ -475,6 +475,7 @@ class UpdatePlan:
     # dependency between the gather and the critic loss. Validated by `capture()`; IL_DEVICE_SYNC=0 keeps plain stream dependencies.
     self._sync_slots, self._sync_timeouts, self._sync_gather_wgs, _, self._sync_spin, self._sync_host_flag = _lib.sync_layout()
     self._sync_poison = _lib.sync_layout_ex()[6]
+    self._sync_indices, self._sync_draw_seen, self._sync_vouched = _lib.sync_layout_ex()[10:13]
     self.sync = torch.zeros(self._sync_slots, dtype=torch.int64, device=dev)   # IL_SYNC_SLOTS: every counter on its own 128-byte line
     self.device_sync = False
     self._chain_fits = None
@@ -648,7 +649,16 @@ class UpdatePlan:
                                                 flags, _lib.stream_ptr(), C.c_void_p(self.ov_stream.cuda_stream)))
       return
     self._ov_leave()
+    if (flags & _lib.IL_FLAG_SAC_STAGED_ROWS) and self.spec_rows:   # actor(s') reads its private slab, requested ahead of its wait for the draw
+      _lib.check(L.il_sac_update_gather_spec(C.byref(self.sac), C.byref(self.pb), C.byref(ring), rewards, relabel, rewards_out, None, None, _lib.ptr(self.logp), _lib.ptr(self.q),
+                                             _lib.ptr(self.stage_next), flags, _lib.stream_ptr()))
+      return
     _lib.check(L.il_sac_update_gather(C.byref(self.sac), C.byref(self.pb), C.byref(ring), rewards, relabel, rewards_out, None, None, _lib.ptr(self.logp), _lib.ptr(self.q), flags, _lib.stream_ptr()))
+
+  def draw_vouched(self) -> int:
+    """[IL_SYNC_VOUCHED]: forward / critic-loss launches of this learner whose draw the previous update's tail had already seen complete ([IL_SYNC_DRAW_SEEN]), so that
+    actor(s') used the rows it requested ahead of its wait. Synchronous read."""
+    return int(self.sync[self._sync_vouched].item())
 
   def poisoned(self) -> bool:
     """[IL_SYNC_POISON]: a bounded device-side wait of this learner has expired; from that launch on the optimiser launches skip their stores (the weights are those of the
@@ -787,10 +797,21 @@ class UpdatePlan:
     each, disjoint (profiles/chain_legs.txt). Bit-identical and switchable, ON by default since then (IL_STAGE_ROWS=0: rows through the indices)."""
     return bool(self.algorithm == 'GAIL' and self.resident_sampler and self.peer_desc is None and not getattr(self, 'data_parallel', False) and os.environ.get('IL_STAGE_ROWS', '1') != '0')
 
+  @property
+  def spec_rows(self) -> bool:
+    """Staged rows, in-order launches: the sampler workgroup also stages next_states and absorbing of the drawn rows into a slab of whole 128-byte lines per row that only
+    actor(s') reads (`stage_next`, il_gail_disc_step_draw_staged2), and actor(s') requests its rows from there in its first batch, ahead of its wait for the draw
+    (il_sac_update_gather_spec): when the previous update's tail has seen the draw complete ([IL_SYNC_DRAW_SEEN], the steady state with the early draw) the rows' trip no
+    longer stands behind the sync words' trip. Bit-identical and switchable (IL_SPEC_ROWS=0: rows behind the wait). draw_vouched() counts the launches that took it."""
+    return self.staged_rows and os.environ.get('IL_SPEC_ROWS', '1') != '0'
+
   def _staged_batch(self):
     if getattr(self, '_stage_desc', None) is None:
       m = self.memory
       self.stage = torch.empty(self.B, m.row, device=self.rows.device)
+      # (empty, like `stage`: the sampler writes every float of a row, pads included - and a fill kernel issued here would be CAPTURED when the first update of a plan is
+      # captured, and then clear the slab at the head of every replay of the discriminator branch, under the chain launch that still reads it)
+      self.stage_next = torch.empty(self.B, int(_lib.lib().il_stage_next_row_floats(m.state_size)), device=self.rows.device)
       t = batch_views(self.stage, m.state_size, m.action_size, True)
       if not m.absorbing:
         self._keep_zero_stage = torch.zeros(1, dtype=torch.float32, device=self.rows.device)
@@ -803,7 +824,7 @@ class UpdatePlan:
     """A ring-strided view of zeros for the `absorbing` field of a ring without absorbing states (one float per ring row would be wasteful: every
     row reads the same zero through stride 0)."""
     z = torch.zeros(1, dtype=torch.float32, device=mem.ring.device)
-    self._keep_zero = z
+    self._keep_zeros = getattr(self, '_keep_zeros', []) + [z]   # (one per ring: the agent ring's word must outlive the expert ring's call - the sampler reads it for the private slab)
     return z.expand(mem.size)
 
   @property
@@ -839,6 +860,10 @@ class UpdatePlan:
         return
       if self.staged_rows:
         self._staged_batch()
+        if self.spec_rows:
+          _lib.check(L.il_gail_disc_step_draw_staged2(C.byref(self.disc), C.byref(rp), C.byref(re_), _lib.ptr(mt), _lib.ptr(m._ring_state), _lib.ptr(self.idx), _lib.ptr(e._ring_state),
+                                                      _lib.ptr(self.eidx), _lib.ptr(self.stage), _lib.ptr(self.stage_next), flags, st))
+          return
         _lib.check(L.il_gail_disc_step_draw_staged(C.byref(self.disc), C.byref(rp), C.byref(re_), _lib.ptr(mt), _lib.ptr(m._ring_state), _lib.ptr(self.idx), _lib.ptr(e._ring_state),
                                                    _lib.ptr(self.eidx), _lib.ptr(self.stage), flags, st))
         return

@@ -231,6 +231,13 @@ int il_polyak(float* target, const float* param, int64_t n, double tau, il_strea
  *   [IL_SYNC_POISON]     != 0 once a bounded wait of this learner has given up: the optimiser epilogues (k_dw_adam, k_gail_reduce) of every later launch skip their
  *                          stores - an update whose hand-off expired never reaches the weights - until the host clears the word (il_sync_clear_poison). Same read-only line
  *                          as [IL_SYNC_SPIN].
+ *   [IL_SYNC_DRAW_SEEN]  = a value of [IL_SYNC_INDICES] that an agent which PRECEDES the next forward / critic-loss launch in stream order has observed: written by the thread
+ *                          that signals [IL_SYNC_MAIN_EPOCH] in the in-order actor optimiser launch's tail, ahead of that release (the overlapped, data-parallel and population
+ *                          tails do not write it). Monotonic; a stale read can only be too small. Shares the line of [IL_SYNC_MAIN_EPOCH], so the launch's request of the
+ *                          epoch carries it. [IL_SYNC_DRAW_SEEN] >= [IL_SYNC_MAIN_EPOCH] + 1 at a launch's start: this update's draw - index arrays and both staged slabs -
+ *                          was complete in memory before the launch began; actor(s') of il_sac_update_gather_spec then uses the rows it requested ahead of its wait.
+ *                          Whoever sets or resets [IL_SYNC_INDICES] or [IL_SYNC_MAIN_EPOCH] from the host zeroes this word too (zeroing the whole buffer does).
+ *   [IL_SYNC_VOUCHED]    += 1 (relaxed, fire and forget) per forward / critic-loss launch that found its draw vouched for. Shares the line of [IL_SYNC_TIMEOUTS].
  * With it the two branches need no stream dependency between the gather and the critic loss (fork at the start of the update, join at
  * its end). NULL everywhere = plain stream ordering (the caller serialises or uses events). */
 /* il_sync_probe: [IL_SYNC_PROBE_FLAG], [IL_SYNC_PROBE_EPOCH] of the same buffer; enqueue setter = 0 on the side stream first, then setter = 1 on the main stream. */
@@ -245,6 +252,7 @@ enum { IL_SYNC_ROWS = 0, IL_SYNC_REWARDS = 1 * IL_SYNC_STRIDE, IL_SYNC_SIDE_EPOC
        IL_SYNC_GATHER_WGS = 5 * IL_SYNC_STRIDE, IL_SYNC_PROBE_FLAG = 6 * IL_SYNC_STRIDE, IL_SYNC_PROBE_EPOCH = 7 * IL_SYNC_STRIDE, IL_SYNC_INDICES = 8 * IL_SYNC_STRIDE,
        IL_SYNC_PARAMS = 9 * IL_SYNC_STRIDE, IL_SYNC_CHAIN_DONE = 10 * IL_SYNC_STRIDE, IL_SYNC_CHAIN_WGS = 11 * IL_SYNC_STRIDE, IL_SYNC_SPIN = 5 * IL_SYNC_STRIDE + 1,
        IL_SYNC_HOST_FLAG = 5 * IL_SYNC_STRIDE + 2, IL_SYNC_POISON = 5 * IL_SYNC_STRIDE + 3,
+       IL_SYNC_DRAW_SEEN = 3 * IL_SYNC_STRIDE + 1, IL_SYNC_VOUCHED = 4 * IL_SYNC_STRIDE + 1,
        IL_SYNC_OV_EPOCH = 12 * IL_SYNC_STRIDE,  /* + stage * IL_SYNC_STRIDE, stage = IL_OV_CHAIN .. IL_OV_DWA (lines 12 .. 15) */
        IL_SYNC_OV_TICKET = 16 * IL_SYNC_STRIDE, /* + stage * IL_SYNC_STRIDE (lines 16 .. 19) */
        IL_SYNC_OV_FLAGS = 20 * IL_SYNC_STRIDE,  /* + (stage * IL_OV_MAX_GRID + workgroup) * IL_SYNC_STRIDE: one line per WAITING workgroup of the stage's consumer launch */
@@ -255,7 +263,8 @@ enum { IL_SYNC_ROWS = 0, IL_SYNC_REWARDS = 1 * IL_SYNC_STRIDE, IL_SYNC_SIDE_EPOC
 enum { IL_OV_CHAIN = 0, IL_OV_DWC = 1, IL_OV_PC = 2, IL_OV_DWA = 3 };
 /* out[0] = IL_SYNC_SLOTS (int64 elements to allocate and zero), out[1] = IL_SYNC_TIMEOUTS, out[2] = IL_SYNC_GATHER_WGS, out[3] = IL_SYNC_STRIDE, out[4] = IL_SYNC_SPIN, out[5] = IL_SYNC_HOST_FLAG */
 void il_sync_layout(int32_t* out);
-/* the same, open-ended: out[0 .. n) = il_sync_layout's six, then [6] IL_SYNC_POISON, [7] IL_SYNC_OV_EPOCH, [8] IL_SYNC_OV_TICKET, [9] IL_SYNC_MAIN_EPOCH */
+/* the same, open-ended: out[0 .. n) = il_sync_layout's six, then [6] IL_SYNC_POISON, [7] IL_SYNC_OV_EPOCH, [8] IL_SYNC_OV_TICKET, [9] IL_SYNC_MAIN_EPOCH,
+ * [10] IL_SYNC_INDICES, [11] IL_SYNC_DRAW_SEEN, [12] IL_SYNC_VOUCHED */
 void il_sync_layout_ex(int32_t* out, int32_t n);
 
 /* ------------------------------------------------------------------------------------------
@@ -340,6 +349,14 @@ int il_sac_update_gather(const il_sac* d, const il_batch* rows, const il_batch* 
  * call. Consecutive overlapped updates need neither. Bit-identical to il_sac_update_gather. */
 int il_sac_update_gather_overlap(const il_sac* d, const il_batch* rows, const il_batch* ring, const float* rewards, const struct il_disc* relabel, float* rewards_out,
                                  const float* eps_next, const float* eps_cur, float* out_logp, float* out_q, uint32_t flags, il_stream_t stream_a, il_stream_t stream_b);
+/* il_sac_update_gather(IL_FLAG_SAC_STAGED_ROWS | IL_FLAG_SAC_WAIT_INDICES) whose actor(s') reads its rows from `next_rows`, the private slab of
+ * il_gail_disc_step_draw_staged2: [batch][il_stage_next_row_floats(state_dim)] floats per row - next_states[0 .. state_dim), absorbing, zeros. actor(s') requests those rows
+ * with its sync words and weights, AHEAD of its wait for [IL_SYNC_INDICES]; if [IL_SYNC_DRAW_SEEN] vouches for the draw the wait falls through and they are used, otherwise
+ * the wait runs as in il_sac_update_gather and the rows are requested again behind it. Nobody else reads `next_rows`, and it is read below the caches only, so the
+ * early request cannot leave a pre-draw line where another reader finds it. Bit-identical to il_sac_update_gather; shapes outside pair mode (k_sac_chain) ignore next_rows. */
+int il_sac_update_gather_spec(const il_sac* d, const il_batch* rows, const il_batch* ring, const float* rewards, const struct il_disc* relabel, float* rewards_out,
+                              const float* eps_next, const float* eps_cur, float* out_logp, float* out_q, const float* next_rows, uint32_t flags, il_stream_t stream);
+int32_t il_stage_next_row_floats(int32_t state_dim); /* floats per row of that slab: state_dim + 1 rounded up to whole 128-byte lines */
 /* one tiny launch on `stream`: [IL_SYNC_OV_EPOCH + 0..3] = [IL_SYNC_MAIN_EPOCH], [IL_SYNC_OV_TICKET + 0..3] = 0 */
 int il_sac_overlap_enter(const il_sac* d, il_stream_t stream);
 /* [IL_SYNC_POISON] = 0 and [IL_SYNC_TIMEOUTS] = 0 (stream-ordered): the host has seen the expired wait and restored a consistent state (e.g. reloaded a checkpoint) */
@@ -510,6 +527,10 @@ int il_gail_disc_step_draw(const il_disc* d, const il_batch* policy, const il_ba
  * next update starts; il_sac_update_gather(IL_FLAG_SAC_STAGED_ROWS, ring = a dense il_batch over stage_rows) then reads its rows with one global trip instead of two. */
 int il_gail_disc_step_draw_staged(const il_disc* d, const il_batch* policy, const il_batch* expert, uint32_t* mt_state_dev, const int64_t* ring_state_a, int32_t* idx_a,
                                   const int64_t* ring_state_b, int32_t* idx_b, float* stage_rows, uint32_t flags, il_stream_t stream);
+/* ... and, per drawn agent row, next_states[0 .. state_dim) followed by `absorbing`, zero-padded to il_stage_next_row_floats(state_dim), into stage_next
+ * [batch][il_stage_next_row_floats]: lines that only actor(s') of il_sac_update_gather_spec reads. Written through and drained before [IL_SYNC_INDICES] is signalled. */
+int il_gail_disc_step_draw_staged2(const il_disc* d, const il_batch* policy, const il_batch* expert, uint32_t* mt_state_dev, const int64_t* ring_state_a, int32_t* idx_a,
+                                   const int64_t* ring_state_b, int32_t* idx_b, float* stage_rows, float* stage_next, uint32_t flags, il_stream_t stream);
 /* Population axis: discriminator step + AIRL/GAIL/FAIRL reward relabel for n_learners discriminators; rewards_out_dev[l] -> float[batch]. */
 int il_gail_step_population(const il_disc* descs_dev, const il_batch* policy_dev, const il_batch* expert_dev, float* const* rewards_out_dev,
                             int32_t n_learners, const il_disc* shape_host, il_stream_t stream);
