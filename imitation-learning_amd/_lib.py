@@ -175,6 +175,7 @@ _SIGNATURES = {
     'il_replay_sample_population': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P]),
     'il_sac_update_population': (C.c_int, [_P, _P, C.c_int32, C.POINTER(Sac), C.c_uint32, _P]),
     'il_gail_step_population': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(Disc), _P]),
+    'il_gail_mixup_step_population': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(Disc), _P, _P, C.c_float, _P]),   # (..., extras_dev, extras_host, mixup_alpha, stream)
     'il_adam_step': (C.c_int, [_P, _P, C.POINTER(Adam), C.c_int64, C.c_uint32, _P]),
     'il_polyak': (C.c_int, [_P, _P, C.c_int64, C.c_double, _P]),
     'il_mlp_numel': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),

@@ -221,6 +221,14 @@ __device__ __forceinline__ void gail_grad_body(il_disc d, il_batch pol, il_batch
     const float* given = kind == 2 ? eps_gp : x.eps_mix;
     return given ? given[row] : philox_uniform(d.noise_seed, ctr, kind == 2 ? IL_STREAM_GP : IL_STREAM_MIX, (uint32_t)row);
   };
+  // MULTI (k_gail_grad_pop), tiles after the workgroup's first: the 16 coefficients of the tile are drawn once, by 16 threads, into L.tmp - the power iterations'
+  // scratch, which nothing touches once they are done (ahead of the barrier in front of the tile loop) and which the loss section never writes, unlike the hand-off
+  // path's `eps_s` = L.zs - instead of once per staged ELEMENT (D Philox calls, or Marsaglia-Tsang inputs, per row) and once more in the loss. Same values: same bits.
+  bool eps_staged = false;
+  auto mix_at = [&](int row, int r) -> float {
+    if constexpr (MULTI) { if (eps_staged) return L.tmp[r]; }
+    return mix_eps(row);
+  };
   auto stage_rows = [&](int t0) {
     const int nthr = blockDim.x - t0;
     for (int i = tid - t0; i >= 0 && i < IL_TILE_R * Dp; i += nthr) {
@@ -230,7 +238,7 @@ __device__ __forceinline__ void gail_grad_body(il_disc d, il_batch pol, il_batch
         float xp = 0.f, xe = 0.f;
         if (kind != 1) { const size_t pr = brow(pol, row); xp = k < S ? pol.states[pr * pol.ld_states + k] : pol.actions[pr * pol.ld_actions + k - S]; }
         if (kind != 0) { const size_t er = brow(exp, row); xe = k < S ? exp.states[er * exp.ld_states + k] : exp.actions[er * exp.ld_actions + k - S]; }
-        if (kind >= 2) { const float e = mix_eps(row); xv = e * xe + (1.f - e) * xp; }
+        if (kind >= 2) { const float e = mix_at(row, r); xv = e * xe + (1.f - e) * xp; }
         else xv = kind == 0 ? xp : xe;
       }
       X[i] = xv;
@@ -240,7 +248,7 @@ __device__ __forceinline__ void gail_grad_body(il_disc d, il_batch pol, il_batch
       if (r < nrows) {
         const float wp = kind != 1 ? pol.weights[brow(pol, row) * pol.ld_weights] : 0.f;
         const float we = kind != 0 ? exp.weights[brow(exp, row) * exp.ld_weights] : 0.f;
-        if (kind >= 2) { const float e = mix_eps(row); w = e * we + (1.f - e) * wp; }
+        if (kind >= 2) { const float e = mix_at(row, r); w = e * we + (1.f - e) * wp; }
         else w = kind == 0 ? wp : we;
       }
       L.wt(0)[r] = w;
@@ -397,7 +405,7 @@ __device__ __forceinline__ void gail_grad_body(il_disc d, il_batch pol, il_batch
     }
     // d loss / d z = w (c_sig sigmoid(z) - c_lab) / B: BCE {1, label}; PUGAIL policy {-1, 0}, expert {2 prior, prior} (clamped away: policy {0, 0}, expert {prior, prior}); Mixup {1, eps}
     const float c_sig = pu ? (kind == 1 ? (1.f + pu_on) * d.pos_class_prior : -pu_on) : 1.f;
-    const float c_lab = kind == 3 ? mix_eps(row) : (kind == 1 ? (pu ? d.pos_class_prior : 1.f) : 0.f);
+    const float c_lab = kind == 3 ? mix_at(row, min(r, nrows - 1)) : (kind == 1 ? (pu ? d.pos_class_prior : 1.f) : 0.f);
     const float p = sigmoid_f(z);
     float dz = valid ? w * (c_sig * p - c_lab) / fB : 0.f;
     if (d.entropy_bonus > 0.f && valid) dz += d.entropy_bonus * w * z * p * (1.f - p) / fB;
@@ -476,6 +484,13 @@ __device__ __forceinline__ void gail_grad_body(il_disc d, il_batch pol, il_batch
   if (!MULTI || ti + 1 >= tpw || tile + 1 >= nt) break;
   ++tile; row0 += IL_TILE_R; nrows = min(IL_TILE_R, B - row0);
   __syncthreads();   // every reader of the previous tile's rows, activations and loss terms is done
+  if constexpr (MULTI) {
+    if (kind >= 2) {   // (workgroup-uniform)
+      if (tid < IL_TILE_R) L.tmp[tid] = tid < nrows ? mix_eps(row0 + tid) : 0.f;
+      eps_staged = true;
+      __syncthreads();
+    }
+  }
   stage_rows(0);
   __syncthreads();
   }
@@ -495,9 +510,25 @@ __global__ __launch_bounds__(256) void k_gail_grad(il_disc d, il_batch pol, il_b
   gail_grad_body<false>(d, pol, exp, eps_gp, x, dL, polL, expL, sa, pu_value_pass, 1, smem);
   IL_ST_END(IL_ST_GAIL_GRAD);
 }
-__global__ __launch_bounds__(256) void k_gail_grad_pop(il_disc d, const il_disc* __restrict__ dL, const il_batch* __restrict__ polL, const il_batch* __restrict__ expL, int tpw) {
+// xL (il_gail_mixup_step_population; may be null, like every pointer inside): learner l's optional inputs, of which only the Mixup coefficients have a population form
+__global__ __launch_bounds__(256) void k_gail_grad_pop(il_disc d, const il_disc* __restrict__ dL, const il_batch* __restrict__ polL, const il_batch* __restrict__ expL, int tpw,
+                                                       const il_gail_extra* __restrict__ xL) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  gail_grad_body<true>(d, il_batch{}, il_batch{}, nullptr, il_gail_extra{}, dL, polL, expL, GailSampler{}, 0, tpw, smem);
+  il_gail_extra x = {};
+  if (xL) x.eps_mix = xL[blockIdx.z].eps_mix;
+  gail_grad_body<true>(d, il_batch{}, il_batch{}, nullptr, x, dL, polL, expL, GailSampler{}, 0, tpw, smem);
+}
+
+// The Mixup coefficients of a population for mixup_alpha != 1, grid (row chunk, learner): learner l's Beta(alpha, alpha) draws under ITS key and update counter (read on the
+// device from its il_disc) into ITS buffer xL[l].eps_mix - il_noise_fill_beta(d_l.noise_seed, d_l.noise_counter, alpha, n, xL[l].eps_mix) for every l, in one launch.
+// The learner is blockIdx.y, as in every other (x, learner) launch of the discriminators.
+__global__ __launch_bounds__(256) void k_gail_mix_fill_pop(const il_disc* __restrict__ dL, const il_gail_extra* __restrict__ xL, int n, float alpha) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  const il_disc* d = dL + blockIdx.y;
+  const uint32_t* ctr = as_global(d->noise_counter);
+  float* out = as_global(const_cast<float*>(xL[blockIdx.y].eps_mix));
+  out[i] = philox_beta(d->noise_seed, ctr ? *ctr : 0u, IL_STREAM_MIX, (uint32_t)i, alpha);
 }
 
 // grid = ceil(P / 256): one gradient element per thread, slabs summed in tile order (deterministic)
@@ -727,15 +758,11 @@ extern "C" int il_gail_disc_step_draw_peer(const il_disc* d, const il_batch* pol
   return gail_disc_step_draw_impl(d, pol, exp, mt_state_dev, ring_state_a, idx_a, ring_state_b, idx_b, flags, peer, stream_);
 }
 
-// population axis: discriminator step + reward relabel of n_learners independent discriminators (same shapes) in three launches
-extern "C" int il_gail_step_population(const il_disc* descs_dev, const il_batch* policy_dev, const il_batch* expert_dev, float* const* rewards_out_dev, int32_t n_learners,
-                                       const il_disc* shape_host, il_stream_t stream_) {
-  if (int rc = check_disc(shape_host)) return rc;
-  IL_CHECK_ARG(descs_dev && policy_dev && expert_dev && rewards_out_dev && n_learners >= 1 && n_learners <= 65535, "il_gail_step_population: bad arguments");
-  IL_CHECK_ARG(shape_host->loss_function != IL_LOSS_MIXUP, "il_gail_step_population: loss_function Mixup is not available on the population path");
-  const il_disc* d = shape_host;
-  hipStream_t st = (hipStream_t)stream_;
-  const int D = d->state_dim + (d->state_only ? 0 : d->action_dim), nt = ceil_div(d->batch, IL_TILE_R), L = n_learners;
+// population axis: discriminator step + reward relabel of n_learners independent discriminators (same shapes) in three launches. xL: il_gail_mixup_step_population's
+// per-learner optional inputs (null otherwise).
+static int gail_population_launches(const il_disc* descs_dev, const il_batch* policy_dev, const il_batch* expert_dev, float* const* rewards_out_dev, int L, const il_disc* d,
+                                    const il_gail_extra* xL, hipStream_t st, const char* who) {
+  const int D = d->state_dim + (d->state_only ? 0 : d->action_dim), nt = ceil_div(d->batch, IL_TILE_R);
   static const int compact = [] { const char* e = getenv("IL_POP_DISC_LDS"); return e && e[0] == '0' ? 0 : 1; }();   // IL_POP_DISC_LDS=0: one workgroup per CU, as in round 3 (A/B)
   const size_t need = disc_lds_floats(D, d->hidden) * sizeof(float);
   const size_t lds = compact || need > (size_t)96 * 1024 ? need : (size_t)96 * 1024, lds_r = compact ? disc_reward_lds_floats(D, d->hidden) * sizeof(float) : lds;
@@ -746,11 +773,41 @@ extern "C" int il_gail_step_population(const il_disc* descs_dev, const il_batch*
   // tiles per workgroup of the gradient launch (k_gail_grad `tpw`): IL_POP_DISC_TPW, default 4
   static const int tpw_env = [] { const char* e = getenv("IL_POP_DISC_TPW"); const int v = e ? atoi(e) : 4; return v >= 1 && v <= 64 ? v : 4; }();
   const int tpw = tpw_env < nt ? tpw_env : nt;
-  { IL_TRACE("k_gail_grad", st); k_gail_grad_pop<<<dim3(ceil_div(nt, tpw), disc_calls(*d), L), 256, lds, st>>>(*d, descs_dev, policy_dev, expert_dev, tpw); }
+  { IL_TRACE("k_gail_grad", st); k_gail_grad_pop<<<dim3(ceil_div(nt, tpw), disc_calls(*d), L), 256, lds, st>>>(*d, descs_dev, policy_dev, expert_dev, tpw, xL); }
   { IL_TRACE("k_gail_reduce", st); k_gail_reduce<<<dim3((int)((P + 255) / 256), L), 256, 0, st>>>(*d, 1, descs_dev, 0, il_peer_bucket{}); }
   { IL_TRACE("k_gail_reward", st); k_gail_reward<<<dim3(nt, L), 256, lds_r, st>>>(*d, zb, nullptr, nullptr, nullptr, descs_dev, policy_dev, rewards_out_dev); }
-  IL_CHECK_LAUNCH("il_gail_step_population");
+  IL_CHECK_LAUNCH(who);
   return IL_OK;
+}
+extern "C" int il_gail_step_population(const il_disc* descs_dev, const il_batch* policy_dev, const il_batch* expert_dev, float* const* rewards_out_dev, int32_t n_learners,
+                                       const il_disc* shape_host, il_stream_t stream_) {
+  if (int rc = check_disc(shape_host)) return rc;
+  IL_CHECK_ARG(descs_dev && policy_dev && expert_dev && rewards_out_dev && n_learners >= 1 && n_learners <= 65535, "il_gail_step_population: bad arguments");
+  IL_CHECK_ARG(shape_host->loss_function != IL_LOSS_MIXUP, "il_gail_step_population: loss_function Mixup is not available on the population path");
+  return gail_population_launches(descs_dev, policy_dev, expert_dev, rewards_out_dev, n_learners, shape_host, nullptr, (hipStream_t)stream_, "il_gail_step_population");
+}
+// The same step for discriminators whose loss is Mixup (include/il_hip.h): for mixup_alpha != 1 one launch draws every learner's coefficients in front of the three.
+extern "C" int il_gail_mixup_step_population(const il_disc* descs_dev, const il_batch* policy_dev, const il_batch* expert_dev, float* const* rewards_out_dev, int32_t n_learners,
+                                             const il_disc* shape_host, const il_gail_extra* extras_dev, const il_gail_extra* extras_host, float mixup_alpha, il_stream_t stream_) {
+  if (int rc = check_disc(shape_host)) return rc;
+  IL_CHECK_ARG(descs_dev && policy_dev && expert_dev && rewards_out_dev, "il_gail_mixup_step_population: null descriptor / batch / reward array");
+  IL_CHECK_ARG(n_learners >= 1 && n_learners <= 65535, "il_gail_mixup_step_population: n_learners=%d must be in 1..65535 (the learner is a grid dimension)", n_learners);
+  IL_CHECK_ARG(shape_host->loss_function == IL_LOSS_MIXUP, "il_gail_mixup_step_population: loss_function=%d is not Mixup (il_gail_step_population takes BCE and PUGAIL)", shape_host->loss_function);
+  IL_CHECK_ARG(!shape_host->pu_clamped, "il_gail_mixup_step_population: pu_clamped (a finite PUGAIL margin's value pass) has no population form");
+  IL_CHECK_ARG(mixup_alpha > 0.f, "il_gail_mixup_step_population: mixup_alpha=%g must be > 0", (double)mixup_alpha);
+  IL_CHECK_ARG(!extras_dev == !extras_host, "il_gail_mixup_step_population: the il_gail_extra array comes as a device array and its host copy, or not at all");
+  IL_CHECK_ARG(mixup_alpha == 1.f || extras_dev, "il_gail_mixup_step_population: mixup_alpha=%g needs the il_gail_extra array (every learner's eps_mix buffer); only alpha = 1 draws on chip", (double)mixup_alpha);
+  for (int l = 0; extras_host && l < n_learners; ++l) {
+    const il_gail_extra& x = extras_host[l];
+    IL_CHECK_ARG(!x.logit_offset_policy && !x.logit_offset_expert && !x.logit_offset_mix, "il_gail_mixup_step_population: learner %d carries a logit offset (subtract_log_policy has no population form)", l);
+    IL_CHECK_ARG(mixup_alpha == 1.f || x.eps_mix, "il_gail_mixup_step_population: learner %d has no eps_mix buffer for the Beta(%g, %g) draws", l, (double)mixup_alpha, (double)mixup_alpha);
+  }
+  hipStream_t st = (hipStream_t)stream_;
+  if (mixup_alpha != 1.f) {
+    IL_TRACE("k_gail_mix_fill_pop", st);
+    k_gail_mix_fill_pop<<<dim3(ceil_div(shape_host->batch, 256), n_learners), 256, 0, st>>>(descs_dev, extras_dev, shape_host->batch, mixup_alpha);
+  }
+  return gail_population_launches(descs_dev, policy_dev, expert_dev, rewards_out_dev, n_learners, shape_host, extras_dev, st, "il_gail_mixup_step_population");
 }
 
 __global__ __launch_bounds__(256) void k_disc_adam(il_disc d, int64_t P) {

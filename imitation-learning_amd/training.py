@@ -1464,7 +1464,7 @@ class BatchedPopulationPlan:
   dimension, so one update of the whole population costs 11 launches instead of 11 N.  This is the route from the latency-bound
   single-learner regime towards the HBM roofline.  Every learner keeps its own replay ring, MT19937 index stream,
   networks, optimiser state, scratch and Philox counter (build the `UpdatePlan`s with distinct `learner_id`s).  SAC, GAIL (`il_gail_step_population`: discriminator step +
-  relabel), DRIL (`il_dril_reward_population`: every learner's Monte-Carlo-dropout reward under its own ensemble, threshold, Philox key and counter; with `bc_aux` also
+  relabel; learners whose loss is Mixup: `il_gail_mixup_step_population`, at any shared `mixup_alpha`), DRIL (`il_dril_reward_population`: every learner's Monte-Carlo-dropout reward under its own ensemble, threshold, Philox key and counter; with `bc_aux` also
   `il_bc_step_population`, the behavioural-cloning auxiliary step of every actor on its own expert batch, in front of the forward kernels), RED (`il_red_reward_population`: every learner's eval-mode reward under its own predictor, target and sigma_1) and GMMIL (`il_gmmil_reward_population`: every
   learner's kernel-mean-embedding reward on its own batches, under its own frozen bandwidths, with its own workspace) learners, and PWIL learners, whose update is SAC's (no
   reward step: the acting side stores the coupling reward with every transition), and AdRIL / SQIL learners (`il_batch_mix_relabel_population`: every learner's expert
@@ -1531,6 +1531,18 @@ class BatchedPopulationPlan:
       self.disc_descs = _device_array([p.disc for p in self.plans], dev)
       self.expert_batches = _device_array([p.eb for p in self.plans], dev)
       self.reward_ptrs = torch.tensor([p.rewards.data_ptr() for p in self.plans], dtype=torch.int64, device=dev)
+      # Mixup (il_gail_mixup_step_population): alpha = 1 mixes with the on-chip U(0,1) stream of every learner's key and counter; any other alpha has ONE launch draw every
+      # learner's Beta(alpha, alpha) coefficients into its own `eps_mix` (UpdatePlan allocated it) in front of the gradient launch - where plan.run() has il_noise_fill_beta
+      assert len({int(p.disc.loss_function) for p in self.plans}) == 1, 'BatchedPopulationPlan(GAIL): the discriminators of one population share loss_function'
+      self.mixup_alpha, self.extras, self._extras_host = None, None, None
+      if int(p0.disc.loss_function) == LOSS_FUNCTIONS['Mixup']:
+        alphas = {1.0 if p._beta_alpha is None else float(p._beta_alpha) for p in self.plans}
+        assert len(alphas) == 1, f'BatchedPopulationPlan(GAIL): the Mixup learners of one population share mixup_alpha (got {sorted(alphas)})'
+        self.mixup_alpha = alphas.pop()
+        if self.mixup_alpha != 1.0:
+          extras = [_lib.GailExtra(eps_mix=p.eps_mix.data_ptr()) for p in self.plans]
+          self._extras_host = (_lib.GailExtra * self.L)(*extras)   # the entry point decides its refusals on this copy
+          self.extras = _device_array(extras, dev)
     if self.algorithm == 'RED':   # every learner's own predictor / target arenas and sigma_1 (set_sigma): read on the device from its descriptor
       self.red_descs = _device_array([p.red for p in self.plans], dev)
       self.reward_ptrs = torch.tensor([p.rewards.data_ptr() for p in self.plans], dtype=torch.int64, device=dev)
@@ -1576,6 +1588,17 @@ class BatchedPopulationPlan:
       words.append([n_expert, -(-int(step) // r.update_freq) if r.update_freq > 0 else 0, int(count)])
     self.dyn.copy_(torch.tensor(words, dtype=torch.int64))   # pageable source: staged synchronously, ordered on the current stream
     self._dyn_set = True
+
+  def _gail_step(self, st):
+    """Discriminator step + relabel of every learner on stream `st`. Mixup with alpha != 1: the coefficient launch inside reads each learner's update counter on the device,
+    like the gradient launch behind it does for its gradient-penalty draws - both sit behind the previous update's actor step, which bumps it."""
+    L, p0 = _lib.lib(), self.plans[0]
+    if self.mixup_alpha is None:
+      _lib.check(L.il_gail_step_population(_lib.ptr(self.disc_descs), _lib.ptr(self.batches), _lib.ptr(self.expert_batches), _lib.ptr(self.reward_ptrs), self.L, C.byref(p0.disc), st))
+    else:
+      _lib.check(L.il_gail_mixup_step_population(_lib.ptr(self.disc_descs), _lib.ptr(self.batches), _lib.ptr(self.expert_batches), _lib.ptr(self.reward_ptrs), self.L, C.byref(p0.disc),
+                                                 _lib.ptr(self.extras) if self.extras is not None else None,
+                                                 C.cast(self._extras_host, C.c_void_p) if self._extras_host is not None else None, self.mixup_alpha, st))
 
   def run(self):
     if self.subs is not None:
@@ -1623,7 +1646,7 @@ class BatchedPopulationPlan:
       self.side.wait_stream(main)
       with torch.cuda.stream(self.side):
         if self.algorithm == 'GAIL':
-          _lib.check(L.il_gail_step_population(_lib.ptr(self.disc_descs), _lib.ptr(self.batches), _lib.ptr(self.expert_batches), _lib.ptr(self.reward_ptrs), self.L, C.byref(p0.disc), _lib.stream_ptr()))
+          self._gail_step(_lib.stream_ptr())
         elif self.algorithm == 'RED':   # the eval-mode reward of every learner (8 workgroups per learner at batch 256), the same fork and join
           _lib.check(L.il_red_reward_population(_lib.ptr(self.red_descs), _lib.ptr(self.batches), _lib.ptr(self.reward_ptrs), self.L, C.byref(p0.red), _lib.stream_ptr()))
         elif self.algorithm == 'DRIL':   # 5-member ensembles, 8 rows per workgroup (32 workgroups per learner at batch 256), the same fork and join
@@ -1637,7 +1660,7 @@ class BatchedPopulationPlan:
       _lib.check(L.il_sac_update_population(_lib.ptr(self.sac_descs), _lib.ptr(self.batches), self.L, C.byref(p0.sac), _lib.IL_FLAG_SAC_SKIP_FORWARD, st))
     else:
       if self.algorithm == 'GAIL':
-        _lib.check(L.il_gail_step_population(_lib.ptr(self.disc_descs), _lib.ptr(self.batches), _lib.ptr(self.expert_batches), _lib.ptr(self.reward_ptrs), self.L, C.byref(p0.disc), st))
+        self._gail_step(st)
       if self.algorithm == 'RED':
         _lib.check(L.il_red_reward_population(_lib.ptr(self.red_descs), _lib.ptr(self.batches), _lib.ptr(self.reward_ptrs), self.L, C.byref(p0.red), st))
       if self.algorithm == 'GMMIL':

@@ -534,6 +534,17 @@ int il_gail_disc_step_draw_staged2(const il_disc* d, const il_batch* policy, con
 /* Population axis: discriminator step + AIRL/GAIL/FAIRL reward relabel for n_learners discriminators; rewards_out_dev[l] -> float[batch]. */
 int il_gail_step_population(const il_disc* descs_dev, const il_batch* policy_dev, const il_batch* expert_dev, float* const* rewards_out_dev,
                             int32_t n_learners, const il_disc* shape_host, il_stream_t stream);
+/* The same step for discriminators whose loss is Mixup (training.py:104-113), which il_gail_step_population refuses. extras_dev: a device array of n_learners
+ * il_gail_extra, or NULL; extras_host: the same array in host memory (the refusals below are decided on the host, ahead of every launch), NULL exactly when extras_dev is.
+ * Learner l mixes with extras[l].eps_mix [batch] where that pointer is set, and otherwise with the on-chip U(0,1) stream of ITS noise_seed / *noise_counter (alpha = 1).
+ * mixup_alpha != 1: one launch in front of the three, grid (row chunk, learner), writes philox_beta(noise_seed_l, *noise_counter_l, IL_STREAM_MIX, i, alpha) to
+ * extras[l].eps_mix[i] - il_noise_fill_beta for every learner, bit for bit - so every learner then needs its buffer. Then gradient, reduce and reward in
+ * il_gail_step_population's launch shapes; per learner bit-identical to il_noise_fill_beta + il_gail_disc_step(extra) + il_gail_reward.
+ * Refused (IL_ERR_ARG, nothing launched): a shape_host whose loss is not Mixup; pu_clamped; mixup_alpha <= 0; mixup_alpha != 1 without the array or with a learner
+ * whose eps_mix is NULL; a logit offset in any extra (subtract_log_policy has no population form); one of extras_dev / extras_host without the other. */
+int il_gail_mixup_step_population(const il_disc* descs_dev, const il_batch* policy_dev, const il_batch* expert_dev, float* const* rewards_out_dev,
+                                  int32_t n_learners, const il_disc* shape_host, const il_gail_extra* extras_dev, const il_gail_extra* extras_host,
+                                  float mixup_alpha, il_stream_t stream);
 /* models.py:177-180 predict_reward (eval mode: no power iteration). out_logits may be NULL. */
 int il_gail_reward(const il_disc* d, const il_batch* batch, float* out_rewards, float* out_logits, const float* logit_offset,
                    il_stream_t stream); /* logit_offset [n] = log pi(a|s) when subtract_log_policy, else NULL */

@@ -13,7 +13,9 @@ il_bc_step_population per update - and the ensemble's pretraining cut to 100 ite
 every learner on its own 6,006 atoms - six trajectories of 1,000 steps and their absorbing rows - at horizon 1,000: 24 chunks of 8 candidates per learner, one
 il_pwil_act_reward_population launch per lockstep step under (c) against one il_pwil_act_reward launch per learner under (b); (a) couples per step as train() does;
 --algorithms AdRIL: the shipped configuration - balanced, update_freq 1250 - with the opt-in key +sweep.adril_population=true: one il_batch_mix_relabel_population launch
-and one copy of 3 L words per update under (c) against one il_batch_mix_relabel_dyn launch and one three-word copy per learner under (b))"""
+and one copy of 3 L words per update under (c) against one il_batch_mix_relabel_dyn launch and one three-word copy per learner under (b); --algorithms GAIL_Mixup: GAIL with
+imitation.loss_function=Mixup at the default mixup_alpha = 1 and the opt-in key +sweep.gail_mixup_population=true - il_gail_mixup_step_population per update under (c) against
+il_gail_disc_step + il_gail_reward per learner under (b); GAIL_Mixup_0.5: the same at imitation.mixup_alpha=0.5, one coefficient launch for all learners under (c))"""
 import argparse
 import os
 import sys
@@ -45,6 +47,9 @@ def overrides(algorithm, steps, start):
   extra = ['imitation.pretraining.iterations=100'] if algorithm in ('RED', 'DRIL') else []   # (the predictor's / ensemble's pretraining sits in front of the clock: kept short, the job measures the loop)
   if algorithm == 'PWIL': extra = [train.PWIL_POPULATION_KEY]   # PWIL sweeps form a population on opt-in only; train() ignores the key
   if algorithm == 'AdRIL': extra = [train.ADRIL_POPULATION_KEY]   # likewise
+  if algorithm.startswith('GAIL_Mixup'):   # GAIL whose loss is Mixup, under its opt-in key; GAIL_Mixup_<alpha>: at that mixup_alpha
+    extra = ['imitation.loss_function=Mixup', train.GAIL_MIXUP_POPULATION_KEY] + ([f'imitation.mixup_alpha={algorithm.split("_")[2]}'] if algorithm.count('_') == 2 else [])
+    algorithm = 'GAIL'
   batch = 128 if algorithm == 'GMMIL' else 256
   return [f'algorithm={algorithm}', 'env=halfcheetah', f'steps={steps}', f'training.start={start}', f'training.batch_size={batch}', 'check_time_usage=true', 'logging.interval=1000',
           '+synthetic_env.dataset_trajectories=6'] + extra
@@ -88,7 +93,7 @@ def main(argv=None):
   ap.add_argument('--start', type=int, default=300)
   ap.add_argument('--repeats', type=int, default=5)
   ap.add_argument('--learners', type=int, nargs='+', default=[4, 16])
-  ap.add_argument('--algorithms', nargs='+', default=['GAIL', 'SAC'])
+  ap.add_argument('--algorithms', nargs='+', default=['GAIL', 'SAC'], choices=['GAIL', 'SAC', 'RED', 'GMMIL', 'DRIL', 'PWIL', 'AdRIL', 'GAIL_Mixup', 'GAIL_Mixup_0.5'])
   ap.add_argument('--out', default=None)
   args = ap.parse_args(argv)
   global out_path

@@ -13,7 +13,9 @@ Sweeps:  python train.py -m seed=1,2,3 algorithm=GAIL env=halfcheetah  (Hydra's 
 Jobs that differ only in their seed train as ONE population in lockstep (`train_sweep`: `il.BatchedPopulationPlan` for the update, `il.PopulationActingWorker` or one
 `il.ActingWorker` per learner for acting: `+sweep.schedule=population|per_learner`, the same bits either way; GMMIL and DRIL sweeps only when that key is given, PWIL sweeps only under `+sweep.pwil_population=true`:
 one `il_pwil_act_reward_population` coupling launch per lockstep step in front of the population acting launch, AdRIL / SQIL sweeps only under `+sweep.adril_population=true`:
-one `il_batch_mix_relabel_population` launch per update between the gathers and the SAC launches); every other sweep runs its jobs one after another, and says so.
+one `il_batch_mix_relabel_population` launch per update between the gathers and the SAC launches, GAIL sweeps whose loss is Mixup (the `GAIL_5_trajectories` and
+`GAIL_10_trajectories` overlays) only under `+sweep.gail_mixup_population=true`: `il_gail_mixup_step_population`, at any `mixup_alpha`, every learner's coefficients under
+its own Philox key and update counter); every other sweep runs its jobs one after another, and says so.
 """
 import os
 import sys
@@ -421,6 +423,13 @@ def adril_population(cfg) -> bool:
   return bool((cfg.get('sweep', {}) or {}).get('adril_population', False))
 
 
+GAIL_MIXUP_POPULATION_KEY = '+sweep.gail_mixup_population=true'   # the opt-in of GAIL sweeps whose loss is Mixup (without it they run job after job, whatever +sweep.schedule says)
+
+
+def gail_mixup_population(cfg) -> bool:
+  return bool((cfg.get('sweep', {}) or {}).get('gail_mixup_population', False))
+
+
 def pwil_atoms_upper_bound(cfg) -> tuple:
   """(most atoms a learner of this configuration can hold, horizon): kept trajectories x ceil(horizon / subsample) rows, plus - with absorbing states - the appended
   absorbing row and the two rows the subsampling always keeps (environments.dataset_to_memory). imitation.trajectories=0 keeps the whole dataset: counted as the synthetic
@@ -492,8 +501,9 @@ def sweep_fallback_reason(cfg):
       return 'reward shaping / subtract_log_policy run their per-function entry points inside the plan'
     if cfg.imitation.loss_function == 'PUGAIL' and float(cfg.imitation.nonnegative_margin) != float('inf'):
       return 'a finite PUGAIL margin needs a value pass ahead of the gradients'
-    if cfg.imitation.loss_function == 'Mixup':   # whatever mixup_alpha: il_gail_step_population refuses every Mixup descriptor
-      return 'imitation.loss_function=Mixup has no population discriminator step (BCE and PUGAIL with an infinite margin have)'
+    if cfg.imitation.loss_function == 'Mixup' and not gail_mixup_population(cfg):   # opt-in by a key of its own, at any mixup_alpha: a Mixup sweep without it runs as it always has
+      return ('imitation.loss_function=Mixup has no population discriminator step (BCE and PUGAIL with an infinite margin have)'
+              f'; Mixup trains as one population (il_gail_mixup_step_population: every learner\'s coefficients under its own key and counter) only when {GAIL_MIXUP_POPULATION_KEY} is given')
   return None
 
 
@@ -552,6 +562,7 @@ def train_sweep(cfgs, prefixes):
   dev = default_device()
   assert _lib.on_device(torch.empty(0, device=dev)), 'train.py needs a GPU: the update path has no CPU fallback'
   B, env_kw = cfg0.training.batch_size, dict(cfg0.get('synthetic_env', {}) or {})
+  mixup_sweep = cfg0.algorithm == 'GAIL' and cfg0.imitation.loss_function == 'Mixup'   # (sweep_fallback_reason: under +sweep.gail_mixup_population=true only)
   start_time = time.time()   # check_time_usage: training_time is what train() reports - everything after the environments, the expert data and the networks are built
 
   learners = []
@@ -632,7 +643,7 @@ def train_sweep(cfgs, prefixes):
                             cfg.reinforcement.discount, entropy_target, cfg.reinforcement.polyak_factor, expert_memory=ln.expert_memory, discriminator=ln.discriminator,
                             discriminator_optimiser=ln.discriminator_optimiser, imitation_cfg=cfg.imitation if cfg.algorithm == 'GAIL' else None, overlap=False, learner_id=i,
                             bc_aux=bool(cfg.imitation.bc_aux_loss),   # (sweep_fallback_reason: set for DRIL learners only)
-                            noise_seed_offset=0 if cfg.algorithm == 'PWIL' else None)   # PWIL jobs train as train() trains them, bit for bit: its Philox key for this learner's seed
+                            noise_seed_offset=0 if cfg.algorithm == 'PWIL' or mixup_sweep else None)   # PWIL and Mixup jobs train as train() trains them, bit for bit: its Philox key for this learner's seed
     ln.plan.main_feeds_ring = True
     ln.plan.watch_timeouts()
     if ln.discriminator is not None and cfg.algorithm not in ('DRIL', 'PWIL', 'AdRIL'): ln.discriminator.eval()   # train.py:147 (the DRIL ensemble keeps its dropout, i.e. train mode, on purpose)
@@ -753,7 +764,9 @@ def multirun(argv, stamp=None):
   for jobs, reason in sweep_groups(cfgs):
     if reason is None:
       print(f'[train] sweep: jobs {jobs[0]}..{jobs[-1]} ({" | ".join(" ".join(overrides[j]) for j in jobs)}) train as one population of {len(jobs)} learners '
-            f'(+sweep.schedule={sweep_schedule(cfgs[jobs[0]])})', file=sys.stderr)
+            f'(+sweep.schedule={sweep_schedule(cfgs[jobs[0]])}'
+            + (f', {GAIL_MIXUP_POPULATION_KEY}: il_gail_mixup_step_population at mixup_alpha={cfgs[jobs[0]].imitation.mixup_alpha}'
+               if cfgs[jobs[0]].algorithm == 'GAIL' and cfgs[jobs[0]].imitation.loss_function == 'Mixup' else '') + ')', file=sys.stderr)
       for j, sc in zip(jobs, train_sweep([cfgs[j] for j in jobs], [prefixes[j] for j in jobs])): scores[j] = sc
     else:
       j = jobs[0]
