@@ -151,11 +151,45 @@ __device__ __forceinline__ void tile_fwd(const float* Xs, int ldx, int Kpad, con
 // dX[16 x K] = dYs[16 x Npad] . W      W: global row-major [Nvalid][ldw], rows >= Nvalid read as zero; columns kb + j >= K clamp
 // their address (the epilogue must ignore them when K % 16 != 0).  epi(kb, acc): acc[reg] = dX[row 4g+reg][col kb + j]
 // ---------------------------------------------------------------------------------------------
-template <bool FULL, class Epi>
-__device__ __forceinline__ void tile_bwd_dx_impl(const float* dYs, int ldy, int Npad, int Nvalid, const float* __restrict__ W, int ldw, int K, Epi epi) {
+// The weight operands of a narrow dY (Npad == 16: the actor head's 2A columns) depend on nothing the kernel computes: tile_bwd_dx_prefetch requests this wave's four
+// dwords of up to two kb blocks (every block of an 8-wave workgroup at K = 256) - the addresses and the min(n, Nvalid - 1) clamp of the loop below, which is the
+// identity in the FULL form - so that a caller which waits for dY first starts the product from registers. Same values, same MFMA order: same bits.
+struct DxPre { float b[2][4]; };
+__device__ __forceinline__ DxPre tile_bwd_dx_prefetch(int Nvalid, const float* __restrict__ W, int ldw, int K) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
   const int j = lane & 15, g = lane >> 4;
-  for (int kb = wave * 16; kb < K; kb += nw * 16) {
+  DxPre p;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const float* wp = W + min((wave + q * nw) * 16 + j, K - 1);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) p.b[q][s] = gload(wp + (size_t)min(4 * g + s, Nvalid - 1) * ldw);
+  }
+  return p;
+}
+template <bool FULL, class Epi>
+__device__ __forceinline__ void tile_bwd_dx_impl(const float* dYs, int ldy, int Npad, int Nvalid, const float* __restrict__ W, int ldw, int K, Epi epi, const DxPre* pre = nullptr) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int j = lane & 15, g = lane >> 4;
+  int kb_first = wave * 16;
+  if (pre && Npad == 16) {   // (uniform) the wave's first two kb blocks from registers, any further ones by the loop below
+    kb_first += 2 * nw * 16;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int kb = (wave + q * nw) * 16;
+      if (kb < K) {
+        f32x4 acc0 = zero4(), acc1 = zero4();
+        const f32x4 a = *reinterpret_cast<const f32x4*>(dYs + j * ldy + 4 * g);
+        acc0 = mfma16(a[0], pre->b[q][0], acc0);
+        acc1 = mfma16(a[1], pre->b[q][1], acc1);
+        acc0 = mfma16(a[2], pre->b[q][2], acc0);
+        acc1 = mfma16(a[3], pre->b[q][3], acc1);
+        f32x4 acc = acc0 + acc1;
+        epi(kb, acc);
+      }
+    }
+  }
+  for (int kb = kb_first; kb < K; kb += nw * 16) {
     f32x4 acc0 = zero4(), acc1 = zero4();
     const float* wp = W + min(kb + j, K - 1);
     const float* yr = dYs + j * ldy + 4 * g;
@@ -191,9 +225,9 @@ __device__ __forceinline__ void tile_bwd_dx_impl(const float* dYs, int ldy, int 
   }
 }
 template <class Epi>
-__device__ __forceinline__ void tile_bwd_dx(const float* dYs, int ldy, int Npad, int Nvalid, const float* __restrict__ W, int ldw, int K, Epi epi) {
-  if (Nvalid == Npad) tile_bwd_dx_impl<true>(dYs, ldy, Npad, Nvalid, W, ldw, K, epi);
-  else tile_bwd_dx_impl<false>(dYs, ldy, Npad, Nvalid, W, ldw, K, epi);
+__device__ __forceinline__ void tile_bwd_dx(const float* dYs, int ldy, int Npad, int Nvalid, const float* __restrict__ W, int ldw, int K, Epi epi, const DxPre* pre = nullptr) {
+  if (Nvalid == Npad) tile_bwd_dx_impl<true>(dYs, ldy, Npad, Nvalid, W, ldw, K, epi, pre);
+  else tile_bwd_dx_impl<false>(dYs, ldy, Npad, Nvalid, W, ldw, K, epi, pre);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -517,6 +551,90 @@ __device__ __forceinline__ void l1_compute_regs(const L1Pre& w, const float* Xs,
     }
   }
 }
+// The first layer in two parts, for a caller whose leading S_whole input columns are in LDS before the rest arrive (target_k(s', a'): s' at launch, a' from another
+// workgroup): `begin` runs the k-blocks that lie wholly inside them (16 u + 16 <= S_whole) ahead of the caller's wait, `finish` the others in the same order, then
+// acc0 + acc1 and the epilogue. The accumulators of both column tiles (at most two per wave: N <= 32 * waves) live across the wait, 16 VGPRs. Every accumulator sees the
+// MFMAs of l1_compute_regs / l1_compute_lds in their order: same bits.
+struct L1Acc { f32x4 a0[2], a1[2]; };
+__device__ __forceinline__ void l1_compute_regs_begin(const L1Pre& w, const float* Xs, int ldx, int Kpad, int N, int S_whole, L1Acc& acc) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6, j = lane & 15, g = lane >> 4;
+  const float* xr = Xs + j * ldx + 4 * g;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    acc.a0[q] = zero4(); acc.a1[q] = zero4();
+    if ((wave + q * nw) * 16 < N) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) if (16 * u < Kpad && 16 * u + 16 <= S_whole) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(xr + 16 * u);
+        acc.a0[q] = mfma16(a[0], w.b[q][u][0], acc.a0[q]);
+        acc.a1[q] = mfma16(a[1], w.b[q][u][1], acc.a1[q]);
+        acc.a0[q] = mfma16(a[2], w.b[q][u][2], acc.a0[q]);
+        acc.a1[q] = mfma16(a[3], w.b[q][u][3], acc.a1[q]);
+      }
+    }
+  }
+}
+template <class Epi>
+__device__ __forceinline__ void l1_compute_regs_finish(const L1Pre& w, const float* Xs, int ldx, int Kpad, int N, int S_whole, L1Acc& acc, Epi epi) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6, j = lane & 15, g = lane >> 4;
+  const float* xr = Xs + j * ldx + 4 * g;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int c0 = (wave + q * nw) * 16;
+    if (c0 < N) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) if (16 * u < Kpad && 16 * u + 16 > S_whole) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(xr + 16 * u);
+        acc.a0[q] = mfma16(a[0], w.b[q][u][0], acc.a0[q]);
+        acc.a1[q] = mfma16(a[1], w.b[q][u][1], acc.a1[q]);
+        acc.a0[q] = mfma16(a[2], w.b[q][u][2], acc.a0[q]);
+        acc.a1[q] = mfma16(a[3], w.b[q][u][3], acc.a1[q]);
+      }
+      const f32x4 s = acc.a0[q] + acc.a1[q];
+      epi(c0, s);
+    }
+  }
+}
+__device__ __forceinline__ void l1_compute_lds_begin(const float* W1s, int ldw1, const float* Xs, int ldx, int Kpad, int N, int S_whole, L1Acc& acc) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6, j = lane & 15, g = lane >> 4;
+  const float* xr = Xs + j * ldx + 4 * g;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    acc.a0[q] = zero4(); acc.a1[q] = zero4();
+    const int c0 = (wave + q * nw) * 16;
+    if (c0 < N) {
+      const float* wr = W1s + (c0 + j) * ldw1 + 4 * g;
+      for (int k0 = 0; k0 < Kpad && k0 + 16 <= S_whole; k0 += 16) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(xr + k0), bq = *reinterpret_cast<const f32x4*>(wr + k0);
+        acc.a0[q] = mfma16(a[0], bq[0], acc.a0[q]);
+        acc.a1[q] = mfma16(a[1], bq[1], acc.a1[q]);
+        acc.a0[q] = mfma16(a[2], bq[2], acc.a0[q]);
+        acc.a1[q] = mfma16(a[3], bq[3], acc.a1[q]);
+      }
+    }
+  }
+}
+template <class Epi>
+__device__ __forceinline__ void l1_compute_lds_finish(const float* W1s, int ldw1, const float* Xs, int ldx, int Kpad, int N, int S_whole, L1Acc& acc, Epi epi) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6, j = lane & 15, g = lane >> 4;
+  const float* xr = Xs + j * ldx + 4 * g;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int c0 = (wave + q * nw) * 16;
+    if (c0 < N) {
+      const float* wr = W1s + (c0 + j) * ldw1 + 4 * g;
+      for (int k0 = max(S_whole, 0) & ~15; k0 < Kpad; k0 += 16) {   // the first k-block that begin left out
+        const f32x4 a = *reinterpret_cast<const f32x4*>(xr + k0), bq = *reinterpret_cast<const f32x4*>(wr + k0);
+        acc.a0[q] = mfma16(a[0], bq[0], acc.a0[q]);
+        acc.a1[q] = mfma16(a[1], bq[1], acc.a1[q]);
+        acc.a0[q] = mfma16(a[2], bq[2], acc.a0[q]);
+        acc.a1[q] = mfma16(a[3], bq[3], acc.a1[q]);
+      }
+      const f32x4 s = acc.a0[q] + acc.a1[q];
+      epi(c0, s);
+    }
+  }
+}
 // The tile's [16][Kpad] input rows (load_rows_cat's values: cat(f1, f2), zero-padded; through il_batch.gather when `gather`), two elements per thread at most
 // (16 * Kpad <= 2 * blockDim.x): index, then element, requested into registers; rows_commit writes them to LDS.
 struct RowsPre { int64_t sr[2]; float v[2]; };
@@ -664,6 +782,8 @@ __device__ __forceinline__ void quad_release(unsigned* lines, int q) {   // cons
 // The K/16 k-blocks are dealt round-robin to the waves; partial tiles are reduced through LDS (`part` >= (K/16)*256 floats; K % 16 == 0).
 // Contains __syncthreads(); every thread of the block must call. Result valid after return.
 // ---------------------------------------------------------------------------------------------
+// (Measured and dropped, profiles/tail_loads.txt: the bias lane of the reduction below requested here as well, for actor(s')'s head - the actor's b3 starts on a line of
+// its own that the previous optimiser launch rewrote. The head's interval shrank by 0.3 us, inside the spread of the parent's own readings, and the headline did not move.)
 struct SmallPre { f32x4 b[2]; };
 __device__ __forceinline__ SmallPre tile_fwd_small_prefetch(const float* __restrict__ W, int ldw, int N, int K) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;

@@ -849,8 +849,13 @@ __device__ __forceinline__ void target_pair(const il_sac& d, const il_batch& b, 
   Panel16 pn; panel_prefetch(pn, W + ws.pk_tf + (size_t)k * H * H, t2);   // (this workgroup is about to wait for its tile's actor(s'): being held at the issue stage costs nothing here)
   if (!w1_regs) w1_commit(w1, W1s, ldw1, IN, INp, H, w1_lanes);
   rows_commit(rp, Xs, ldx, INp, S);
+  // The k-blocks of the first layer that are s' alone (16 u + 16 <= S) run here, where the workgroup idles, their accumulators kept across the wait: behind it are the
+  // a' trip, the remaining k-blocks and the epilogue (l1_compute_*_begin / _finish: the MFMA order of l1_compute_*, same bits). The barrier covers the LDS writes above.
+  __syncthreads();
+  L1Acc l1acc;
+  if (w1_regs) l1_compute_regs_begin(w1r, Xs, ldx, INp, H, S, l1acc); else l1_compute_lds_begin(W1s, ldw1, Xs, ldx, INp, H, S, l1acc);
   IL_TL(10, 1);
-  tile_await_bits<false>(ctr, 1u, 0u, tile_timeouts(d));   // a' of this tile, written through by its actor(s') workgroup (the barrier also covers the LDS writes above)
+  tile_await_bits<false>(ctr, 1u, 0u, tile_timeouts(d));   // a' of this tile, written through by its actor(s') workgroup
   IL_TL(10, 2);
   for (int i = threadIdx.x; i < IL_TILE_R * A; i += blockDim.x) { const int r = i / A, c = i - r * A; Xs[r * ldx + S + c] = sload1(W, ws.n_a2 + (int64_t)(row0 + r) * A + c); }
 #ifdef IL_EXP_CHECK
@@ -863,7 +868,7 @@ __device__ __forceinline__ void target_pair(const il_sac& d, const il_batch& b, 
 #pragma unroll
       for (int r = 0; r < 4; ++r) H1s[(4 * g + r) * ldh + col] = fmaxf(acc[r] + bb, 0.f);
     };
-    if (w1_regs) l1_compute_regs(w1r, Xs, ldx, INp, H, epi1); else l1_compute_lds(W1s, ldw1, Xs, ldx, INp, H, epi1);
+    if (w1_regs) l1_compute_regs_finish(w1r, Xs, ldx, INp, H, S, l1acc, epi1); else l1_compute_lds_finish(W1s, ldw1, Xs, ldx, INp, H, S, l1acc, epi1);
   }
   __syncthreads();
   IL_TL(10, 3);
@@ -1061,6 +1066,15 @@ __device__ __forceinline__ void actor_bwd_tile(const il_sac& d, const il_batch& 
   const int nb = H >> 4, pt0 = part * nb / nparts, pt1 = (part + 1) * nb / nparts;   // this part's output tiles of the last GEMM
   const size_t poff = (size_t)min(wave * 16 + j, H - 1) * B + row0 + 4 * g;
   const f32x4 hv2p = gload4(h2 + poff), hv1p = gload4(h1 + (size_t)min((pt0 + wave) * 16 + j, H - 1) * B + row0 + 4 * g);
+  // PARK (a helper that waits for the critics): what the first GEMM behind the wait needs besides dz3 - this wave's W3 lanes of its (up to) two kb blocks and the h2
+  // lanes of the second one - is requested here too, 12 registers across the wait, instead of behind the barrier that follows dz3 (a_h2 was written by the chain
+  // launch on other XCDs, W3 by the previous actor optimiser launch: both trips sat on the launch's last leg).
+  const int kb2 = PARK ? (wave + (int)(blockDim.x >> 6)) * 16 : -1;   // the wave's second kb block of that GEMM
+  f32x4 hv2q = zero4(); DxPre w3dx = {};
+  if (PARK) {
+    hv2q = gload4(h2 + (size_t)min(kb2 + j, H - 1) * B + row0 + 4 * g);
+    w3dx = tile_bwd_dx_prefetch(2 * A, net.W3, H, H);
+  }
   const bool stamp = tile == 0 && part == 0;
   IL_STAMP(stamp, 24);
   for (int i = tid; i < IL_TILE_R * ldz; i += blockDim.x) DZ3s[i] = 0.f;
@@ -1135,12 +1149,13 @@ __device__ __forceinline__ void actor_bwd_tile(const il_sac& d, const il_batch& 
   // dz2 = (dz3 . W3) [h2 > 0]
   tile_bwd_dx(DZ3s, ldz, 16, 2 * A, net.W3, H, H, [&](int kb, f32x4 acc) {
     const size_t off = (size_t)(kb + j) * B + row0 + 4 * g;
-    const f32x4 hv = (kb == wave * 16) ? hv2p : *reinterpret_cast<const f32x4*>(h2 + off);
+    const f32x4 hv = (kb == wave * 16) ? hv2p : ((PARK && kb == kb2) ? hv2q : *reinterpret_cast<const f32x4*>(h2 + off));
     f32x4 o;
 #pragma unroll
     for (int r = 0; r < 4; ++r) { o[r] = hv[r] > 0.f ? acc[r] : 0.f; DZ2s[(4 * g + r) * ldh + kb + j] = o[r]; }
     if (part == 0) wstore4<false>(W, ws.a_dz2 + (int64_t)off, o);
-  });
+  }, PARK ? &w3dx : nullptr);
+  IL_TL(3, 3);
   __syncthreads();
   IL_STAMP(stamp, 28);
   auto epi_dz1 = [&](int kb, f32x4 acc) {

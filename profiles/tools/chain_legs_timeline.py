@@ -52,6 +52,8 @@ for lo, name in ((0, "actor(s') half 1"), (nt, "actor(s') half 0")):
   a = c[lo:lo + nt]
   row(f'{name}: prologue done', a[:, 1] - a[:, 0]); row(f'{name}: rows in LDS', a[:, 2] - a[:, 0]); row(f'{name}: layer 1 done', a[:, 3] - a[:, 0])
 a = c[nt:2 * nt]; row("actor(s') half 0: arrival, after the launch's first workgroup", a[:, 7] - t_chain)
+row("actor(s') half 0: partner's half received -> head done (slots 5 -> 6)", a[:, 6] - a[:, 5])   # (the head: profiles/tail_loads.txt)
+a = c[2 * nt:6 * nt]; row("targets, both halves: a' seen -> layer 1 done (slots 2 -> 3)", a[:, 3] - a[:, 2])   # (the first layer in two parts)
 a = c[4 * nt:6 * nt]; row("targets half 0: arrival, after the launch's first workgroup", a[:, 7] - t_chain)
 a = c[6 * nt:7 * nt]; row("relabel: rewards written, after the launch's first workgroup", a[:, 6] - t_chain)
 a = c[7 * nt:9 * nt]

@@ -55,3 +55,8 @@ h = h[h[:, 7] >= t0]
 if h.size:
   row('helpers: both critics of the tile seen', us(h[:, 2] - t0))
   row('helpers: done', us(h[:, 7] - t0))
+  # the helpers' tail (profiles/tail_loads.txt): everything behind the wait for the critics; slot 3 (behind tile_bwd_dx, dz2 in LDS) only in builds that stamp it
+  row('helpers: critics seen -> done', us(h[:, 7] - h[:, 2]))
+  if (h[:, 3] >= h[:, 2]).all():
+    row('helpers: critics seen -> dz2 done', us(h[:, 3] - h[:, 2]))
+    row('helpers: dz2 done -> done', us(h[:, 7] - h[:, 3]))
