@@ -736,8 +736,16 @@ __device__ __forceinline__ bool quad_same_xcd(unsigned* line) {   // producer: e
 // take part - thread t_first, which stored this quarter's own flag (pair_publish(.., t_first)), polls the three flags together per round (bounded like every device-side
 // wait), then they copy with sc0 sc1 loads as in pair_receive - so the
 // waves below t_first may have a panel in flight meanwhile: their loads do not queue in front of the hop's (3 * 64 * 4 lanes <= 4 per thread of the copying waves).
-template <class Timeout>
-__device__ __forceinline__ void quad_receive(unsigned* lines, const float* slabs, int q, float* Ts, int ld, int t_first, Timeout timed_out) {
+// General form: put(u, row, col, v) per received element, u in [0, 4) = which of the calling thread's (at most four) lanes - its column 64 p + c, p = (q + 1 + (i >> 8)) & 3,
+// c = (i >> 2) & 63 with i = threadIdx.x - t_first + u * (blockDim.x - t_first), is known at the workgroup's start: quad_receive_cols names it for a prologue that requests
+// per-column operands of `put` (k_policy_critic_quad: the w3 lanes of the mask dz2 = w3 [h2 > 0], written at the hop instead of in a pass of its own behind it).
+__device__ __forceinline__ int quad_receive_cols(int q, int t_first, int u) {   // -1: lane u of this thread takes no part
+  const int n = (int)blockDim.x - t_first, i = (int)threadIdx.x - t_first + u * n;
+  if ((int)threadIdx.x < t_first || i >= 3 * 64 * 4) return -1;
+  return 64 * ((q + 1 + (i >> 8)) & 3) + ((i >> 2) & 63);
+}
+template <class Timeout, class Put>
+__device__ __forceinline__ void quad_receive_each(unsigned* lines, const float* slabs, int q, int t_first, Timeout timed_out, Put put) {
   if ((int)threadIdx.x == t_first) {
     unsigned* l0 = lines + ((q + 1) & 3) * IL_CTR_STRIDE; unsigned* l1 = lines + ((q + 2) & 3) * IL_CTR_STRIDE; unsigned* l2 = lines + ((q + 3) & 3) * IL_CTR_STRIDE;
     int spins = 0;
@@ -763,10 +771,14 @@ __device__ __forceinline__ void quad_receive(unsigned* lines, const float* slabs
       const int i = i0 + u * n, p = (q + 1 + (i >> 8)) & 3, c = (i >> 2) & 63, r4 = (i & 3) * 4;
       if (i < 3 * 64 * 4)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) Ts[(r4 + e) * ld + 64 * p + c] = v[u][e];
+        for (int e = 0; e < 4; ++e) put(u, r4 + e, 64 * p + c, v[u][e]);
     }
   }
   __syncthreads();
+}
+template <class Timeout>
+__device__ __forceinline__ void quad_receive(unsigned* lines, const float* slabs, int q, float* Ts, int ld, int t_first, Timeout timed_out) {
+  quad_receive_each(lines, slabs, q, t_first, timed_out, [&](int, int row, int col, float v) { Ts[row * ld + col] = v; });
 }
 __device__ __forceinline__ void quad_release(unsigned* lines, int q) {   // consumer q, after its last use of the hop (one thread); the third consumer of a slab clears its line
   unsigned* l0 = lines + ((q + 1) & 3) * IL_CTR_STRIDE; unsigned* l1 = lines + ((q + 2) & 3) * IL_CTR_STRIDE; unsigned* l2 = lines + ((q + 3) & 3) * IL_CTR_STRIDE;

@@ -1484,7 +1484,8 @@ __device__ __forceinline__ void policy_critic_pair(const il_sac& d, const il_bat
 // Quad mode of k_policy_critic (k_policy_critic_quad): (critic k, tile) is FOUR 512-thread workgroups. In pair mode each SIMD issues two waves x 64 MFMAs of the hidden
 // layer's forward and again of its backward (1.7 us each) and each CU pulls a 128 KB panel; here wave w < 4 of quarter q owns output tile 4 q + w - the MFMAs, k order and
 // operands of wave 4 q + w of k_policy_critic - so one wave per SIMD issues 64 MFMAs and a CU pulls 64 KB. Waves 4 .. 7 share the first layer (computed in full by every
-// quarter, as in the pair), the hop copies and the Q pass, and wait at the barriers while the MFMA waves run. The hop is four-way (quad_receive: every quarter reads the
+// quarter, as in the pair) and the hop copies, which also write the backward's mask (below), and wait at the barriers while the MFMA waves run - in quarter 0 they sum Q
+// beside the backward GEMM; no other quarter computes it. The hop is four-way (quad_receive_each: every quarter reads the
 // other three 4 KB slabs); dQ/da: wave w of quarter q forms the partial tile of n-block 4 q + w and writes it through, as in the pair; the tile's helpers wait for eight
 // arrivals. A quad waits for each other: every workgroup must be resident - (8 + helpers) * nt within the budget of policy_critic_quad_ok. Bit-identical to k_policy_critic.
 __device__ __forceinline__ void policy_critic_quad(const il_sac& d, const il_batch& b, int k, int tile, int q, float* smem) {
@@ -1492,6 +1493,8 @@ __device__ __forceinline__ void policy_critic_quad(const il_sac& d, const il_bat
   const int nt = B / IL_TILE_R, row0 = tile * IL_TILE_R;
   const int INp = round_up16(IN), ldx = INp + 4, ldh = H + 4;
   float* Xs = smem; float* H1s = Xs + IL_TILE_R * ldx; float* H2s = H1s + IL_TILE_R * ldh; float* W1s = pair_w1s(smem, INp, H);
+  float* DZ2s = H2s + IL_TILE_R * ldh;   // [16][H + 4], in the (H / 16 + 1) * 256 + 64 floats that pair_w1s leaves between H2s and W1s for the other roles' reductions: none in a quad
+  constexpr int ldq = 256 + 4;           // ldh as a constant (H = 256 in a quad, pair_shape_ok) where the hop writes: a row is an immediate offset, not a multiply per element
   const int ldw1 = INp + 4, w1_lanes = H * IN / 4;
   const SacWs ws = sac_ws(S, A, H, B);
   float* W = d.workspace;
@@ -1512,14 +1515,23 @@ __device__ __forceinline__ void policy_critic_quad(const il_sac& d, const il_bat
   if (w1_regs) l1_prefetch(w1r, p.W1, IN, INp, H); else w1_issue(w1, p.W1, w1_lanes);
   rows_issue(rp, INp, b.states, b.ld_states, S, W + ws.a_anew, A, A, row0, false, 0, true);
   const float pb1a = gload(p.b1 + wave * 16 + j), pb1b = gload(p.b1 + min((wave + nw) * 16 + j, H - 1)), pb3 = gload(p.b3);
-  float w3v[4];
+  // w3, three ways: the Q waves (waves 4 .. 7 of quarter 0) hold whole rows' lanes for Q = h2 . w3; an MFMA wave holds the lane of its own column and a receiving thread
+  // the lanes of the (at most four) foreign columns it copies, for the mask dz2 = w3 [h2 > 0] that both write into DZ2s beside the raw h2 (below)
+  // (requested by every wave, behind indices clamped into range, and by a condition the whole workgroup shares: a branch on the wave here puts the zeroes of the other
+  // side's registers behind its loads - a wait for them in front of the issue fence, 0.3 us of prologue when it was tried)
+  const bool qw = !mw && q == 0;
+  float w3v[4] = {0.f, 0.f, 0.f, 0.f}, w3r[4];
 #pragma unroll
-  for (int u = 0; u < 4; ++u) w3v[u] = gload(p.W3 + min(lane + 64 * u, H - 1));
+  for (int u = 0; u < 4; ++u) w3r[u] = gload(p.W3 + max(quad_receive_cols(q, 256, u), 0));
+  if (q == 0) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) w3v[u] = gload(p.W3 + min(lane + 64 * u, H - 1));
+  }
   // the MFMA waves' own operands: bias of tile t2 and n-block t2 of the first action k-block of W1 (tile_bwd_dx_cols_prefetch's lanes, for this wave's dQ/da partial tile)
   const int kb0 = (S >> 4) << 4;
-  float pb2 = 0.f, w1c[4] = {0.f, 0.f, 0.f, 0.f};
+  float pb2 = 0.f, w3c = 0.f, w1c[4] = {0.f, 0.f, 0.f, 0.f};
   if (mw) {
-    pb2 = gload(p.b2 + t2 * 16 + j);
+    pb2 = gload(p.b2 + t2 * 16 + j); w3c = gload(p.W3 + t2 * 16 + j);
     const float* wp = p.W1 + min(kb0 + j, IN - 1);
 #pragma unroll
     for (int s_ = 0; s_ < 4; ++s_) w1c[s_] = gload(wp + (size_t)(t2 * 16 + 4 * g + s_) * IN);
@@ -1549,7 +1561,7 @@ __device__ __forceinline__ void policy_critic_quad(const il_sac& d, const il_bat
       const int col = c0 + j;
       f32x4 hv;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) { hv[r] = fmaxf(acc[r] + pb2, 0.f); H2s[(4 * g + r) * ldh + col] = hv[r]; }
+      for (int r = 0; r < 4; ++r) { hv[r] = fmaxf(acc[r] + pb2, 0.f); H2s[(4 * g + r) * ldh + col] = hv[r]; DZ2s[(4 * g + r) * ldq + col] = hv[r] > 0.f ? w3c : 0.f; }
       debug_mask4(d, 7 + 2 * k, row0 + 4 * g, col, hv);
       pair_store(slabs + (size_t)q * IL_TILE_R * 64, (int64_t)(col - 64 * q) * 16 + 4 * g, hv, near);
     });
@@ -1557,26 +1569,36 @@ __device__ __forceinline__ void policy_critic_quad(const il_sac& d, const il_bat
   pair_publish(lines + q * IL_CTR_STRIDE, 256);
   IL_TL(11, 3);
   Panel16 pk; if (mw) panel_prefetch(pk, W + ws.pk_cb + (size_t)k * H * H, t2);   // the whole backward panel (64 KB per CU) streams in under the hop: waves 4 .. 7 receive
-  quad_receive(lines, slabs, q, H2s, ldh, 256, timed_out);
+  // The hop writes what the backward needs - dQ/dh2 with upstream 1 (scaling and min-selection happen in the tail), dz2 = w3 [h2 > 0] - straight into DZ2s, as the MFMA
+  // waves did for their own columns above; the raw value goes to H2s in quarter 0 alone, whose Q waves are its only reader.
+  quad_receive_each(lines, slabs, q, 256, timed_out, [&](int u, int row, int col, float v) {
+    if (q == 0) H2s[row * ldq + col] = v;
+    DZ2s[row * ldq + col] = v > 0.f ? w3r[u] : 0.f;
+  });
   IL_TL(11, 4);
-  // Q = h2 . w3 + b3 and dz2 = w3 [h2 > 0] in place: whole rows, computed by every quarter (quarter 0 stores Q)
-  for (int r = wave; r < IL_TILE_R; r += nw) {
-    float sq_ = 0.f;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int n = lane + 64 * u;
-      if (n < H) { const float h = H2s[r * ldh + n]; sq_ += h * w3v[u]; H2s[r * ldh + n] = h > 0.f ? w3v[u] : 0.f; }
-    }
-    sq_ = wave_sum(sq_);
-    if (lane == 0 && q == 0) wstore1(W, ws.p_q + (int64_t)k * B + row0 + r, sq_ + pb3);   // (written through: the helpers read it without an acquire)
-  }
-  __syncthreads();
-  IL_TL(11, 5);
-  if (mw) {
-    tile_packed_regs(H2s, ldh, pk, t2, [&](int kb, f32x4 acc) {
+  if (mw) {   // behind the receive's barrier at once
+    tile_packed_regs(DZ2s, ldq, pk, t2, [&](int kb, f32x4 acc) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) { float* h = H1s + (4 * g + r) * ldh + kb + j; *h = *h > 0.f ? acc[r] : 0.f; }   // dz1 in place, this wave's columns
     });
+  } else if (qw) {
+    // Q = h2 . w3 + b3 beside the backward, over the raw tile: whole rows, one wave per row (the lanes, the u order and the wave_sum of k_policy_critic's pass; H = 256
+    // in a quad). A wave's four rows are read at once - one LDS trip, where a read per term cost 0.4 us a row. Only the helpers read Q, behind the arrival - the drain
+    // and barrier in front of it cover these stores.
+    float hq[4][4];
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr)
+#pragma unroll
+      for (int u = 0; u < 4; ++u) hq[rr][u] = H2s[(wave - 4 + 4 * rr) * ldh + lane + 64 * u];
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      float sq_ = 0.f;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) sq_ += hq[rr][u] * w3v[u];
+      sq_ = wave_sum(sq_);
+      if (lane == 0) wstore1(W, ws.p_q + (int64_t)k * B + row0 + wave - 4 + 4 * rr, sq_ + pb3);   // (written through: the helpers read it without an acquire)
+    }
+    IL_TLT(11, 5, 256);
   }
   __syncthreads();
   IL_TL(11, 6);
@@ -1636,7 +1658,10 @@ __device__ __forceinline__ void policy_critic_helper(const il_sac& d, const il_b
     }
     __syncthreads();
     IL_TL(3, 2);
-    if (threadIdx.x == 0 && __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == arrivals - 1u + (unsigned)helpers)
+    // This helper is through: counted by a thread of the LAST wave, which holds no head thread (16 A <= 128 of them, waves 0 and 1). The count is a returning atomic -
+    // the last of `helpers` clears the counter for the next launch, which follows in stream order - and in thread 0 its round trip stood in front of that wave's loads of
+    // Q and the dQ/da partial tiles, the first of the launch's last leg; here it travels beside them.
+    if (threadIdx.x == blockDim.x - 64 && __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == arrivals - 1u + (unsigned)helpers)
       __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   };
   if ((d.hidden >> 4) <= helpers * (int)(blockDim.x >> 6)) actor_bwd_tile<16, true, true>(d, b, tile, out_logp, out_q, smem, part, helpers, wait);   // one output tile of the last GEMM per wave at most

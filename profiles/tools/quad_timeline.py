@@ -4,8 +4,10 @@ SAC+GAIL update of the headline schedule, from a -DIL_TIMELINE build:
   bash profiles/tools/build_variants.sh tl:"-DIL_TIMELINE -w"
   IL_HIP_LIBRARY=variants/tl/libil_hip.so python profiles/tools/quad_timeline.py [replays]
 
-The critic workgroups stamp slots 0 .. 7 of timeline kernel 11 (launched, prologue requested, layer 1 done, layer 2 done + published, the other parts' h2 received, Q + mask
-done, layer 2 backward done, arrival signalled); the helpers stamp kernel 3. Per-phase durations are per workgroup (one slot to the next), then min / median / max over
+The critic workgroups stamp slots 0 .. 7 of timeline kernel 11 (launched, prologue requested, layer 1 done, layer 2 done + published, the other parts' h2 received, slot 5,
+layer 2 backward done, arrival signalled); the helpers stamp kernel 3. Slot 5: in the quad launch "Q stored", stamped by thread 256 of quarter 0 alone (its waves 4 .. 7 sum
+Q beside the backward; the mask is written at the hop) - the other quarters leave it 0 and the row is over quarter 0's workgroups; in the pair launch, and in builds of
+the quad from before the mask moved to the hop, every workgroup's "Q + mask done", between the hop and the backward. Per-phase durations are per workgroup (one slot to the next), then min / median / max over
 the critic workgroups of the last replay; absolute times are microseconds after the launch's first workgroup started."""
 import ctypes as C
 import sys
@@ -44,8 +46,10 @@ def row(name, a):
 print(f'B = {plan.B}; {"QUAD" if parts == 4 else "PAIR"} mode ({2 * parts * nt} critic workgroups); us: min / median / max over them')
 print('durations')
 for lo, hi, name in ((0, 1, 'prologue (rows, W1, panel requested)'), (1, 2, 'layer 1'), (2, 3, 'layer 2 forward + publish'), (3, 4, 'hop (other parts received)'),
-                     (4, 5, 'Q + mask'), (5, 6, 'layer 2 backward'), (6, 7, 'dQ/da partials + arrival')):
+                     (4, 6, 'received -> layer 2 backward done'), (6, 7, 'dQ/da partials + arrival')):
   row(name, us(c[:, hi] - c[:, lo]))
+qs = c[c[:, 5] >= c[:, 4]]   # (a slot 5 of this replay)
+if len(qs): row(f'received -> slot 5 ({len(qs)} workgroups: Q stored / Q + mask)', us(qs[:, 5] - qs[:, 4]))
 row('whole critic workgroup', us(c[:, 7] - c[:, 0]))
 print('absolute (after the first critic workgroup started)')
 for s, name in ((2, 'layer 1 done'), (3, 'layer 2 forward done'), (4, 'received'), (6, 'layer 2 backward done'), (7, 'arrived')):
