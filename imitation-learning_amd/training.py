@@ -1406,7 +1406,38 @@ class PretrainPlan:
     return self._loss
 
 
-class PopulationPlan:
+class _Branches:
+  """What PopulationPlan and BatchedPopulationPlan share: members advanced side by side, each on a stream of its own that forks from and joins the current stream
+  (captured: parallel branches of one graph), and the capture / replay of whatever run() enqueues."""
+  graph = None
+
+  def _run_branches(self, members):
+    main = torch.cuda.current_stream()
+    for m, s in zip(members, self.streams):
+      s.wait_stream(main)
+      with torch.cuda.stream(s):
+        m.run()
+    for s in self.streams:
+      main.wait_stream(s)
+
+  def _before_capture(self):
+    """Whatever must be asked or uploaded in front of a capture: an exception inside one would leave the stream capturing, and an upload is no graph node."""
+
+  def capture(self, warmup: int = 0):
+    for _ in range(warmup):
+      self.run()
+    self._before_capture()
+    torch.cuda.synchronize()
+    self.graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(self.graph):
+      self.run()
+    return self
+
+  def replay(self):
+    self.graph.replay()
+
+
+class PopulationPlan(_Branches):
   """N independent learners (seeds / hyper-parameter trials: how the reference is actually used, README.md:96-99, train_all.py) advanced
   by ONE hipGraph replay: every learner's update block is a branch of the graph on its own stream, so their latency-bound kernels
   (16-64 workgroups each) fill the 256 CUs side by side.  Each learner owns its replay ring, index stream, scratch and noise state."""
@@ -1417,30 +1448,14 @@ class PopulationPlan:
       p.overlap = False  # one stream per learner: the learners themselves are the concurrency (nested fork/join breaks hipGraph capture on ROCm 7.2)
       p._set_device_sync(False)
     self.streams = [torch.cuda.Stream() for _ in self.plans]
-    self.graph = None
 
   def run(self):
-    main = torch.cuda.current_stream()
-    for p, s in zip(self.plans, self.streams):
-      s.wait_stream(main)
-      with torch.cuda.stream(s):
-        p.run()
-    for s in self.streams:
-      main.wait_stream(s)
+    self._run_branches(self.plans)
 
   def capture(self, warmup: int = 0):
     for p in self.plans:
       p.memory.stream().device_state(p.rows.device)
-    for _ in range(warmup):
-      self.run()
-    torch.cuda.synchronize()
-    self.graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(self.graph):
-      self.run()
-    return self
-
-  def replay(self):
-    self.graph.replay()
+    return super().capture(warmup)
 
 
 def gmmil_whole_lanes(batches, state_size: int, action_size: int, state_only) -> int:
@@ -1459,21 +1474,221 @@ def _device_array(structs, device) -> Tensor:
   return torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
 
 
-class BatchedPopulationPlan:
+# ---- what one update of a population does besides SAC's launches: one namespace per algorithm, chosen once (POPULATION_STEPS) by BatchedPopulationPlan, which keeps the state
+def _reward_ptrs(plans, dev) -> Tensor:
+  """Every learner's reward buffer, for the reward launches that index them with the learner id."""
+  return torch.tensor([p.rewards.data_ptr() for p in plans], dtype=torch.int64, device=dev)
+
+
+def _refuse_mixing(plans, algorithm: str):
+  assert not any(p.mix_expert or p.bc_aux for p in plans), f'BatchedPopulationPlan({algorithm}): mixed batches / the BC auxiliary step have no population launches'
+
+
+class _SacStep:
+  """SAC learners: the gathers and the SAC launches are the whole update. Also the members every step has, as the no-ops the others replace."""
+  reward = None   # reward(pop, st): the reward / discriminator launch on stream `st`. None: no such launch, and no second stream
+
+  def check(self, plans): pass                              # the shapes one launch can serve and the configurations it refuses
+  def build(self, pop, plans, dev): pass                    # the step's device arrays, as attributes of `pop`
+  def before_launch(self, pop): pass                        # asked in front of the first launch: a refused update draws no indices
+  def first_update(self, pop, st, prepared): return False   # behind the gathers, on the main stream. True: that was the whole update
+  def before_forward(self, pop, st): pass                   # launches on the main stream between the gathers and the forward kernels
+  def before_capture(self, pop): pass                       # asked or uploaded in front of a capture (_Branches._before_capture)
+
+
+class _PwilStep(_SacStep):
+  """PWIL learners, whose update is SAC's: no reward step, the acting side stores the coupling reward with every transition (PopulationActingWorker(reward_models=...):
+  il_pwil_act_reward_population)."""
+  def check(self, plans): _refuse_mixing(plans, 'PWIL')
+
+
+class _GailStep(_SacStep):
+  """GAIL learners: `il_gail_step_population`, discriminator step + relabel of every learner; learners whose loss is Mixup: `il_gail_mixup_step_population`, at any shared
+  `mixup_alpha`. alpha = 1 mixes with the on-chip U(0,1) stream of every learner's key and counter; any other alpha has ONE launch draw every learner's Beta(alpha, alpha)
+  coefficients into its own `eps_mix` (UpdatePlan allocated it) in front of the gradient launch - where plan.run() has il_noise_fill_beta."""
+
+  def build(self, pop, plans, dev):
+    p0 = plans[0]
+    pop.disc_descs = _device_array([p.disc for p in plans], dev)
+    pop.expert_batches = _device_array([p.eb for p in plans], dev)
+    pop.reward_ptrs = _reward_ptrs(plans, dev)
+    assert len({int(p.disc.loss_function) for p in plans}) == 1, 'BatchedPopulationPlan(GAIL): the discriminators of one population share loss_function'
+    pop.mixup_alpha, pop.extras, pop._extras_host = None, None, None
+    if int(p0.disc.loss_function) == LOSS_FUNCTIONS['Mixup']:
+      alphas = {1.0 if p._beta_alpha is None else float(p._beta_alpha) for p in plans}
+      assert len(alphas) == 1, f'BatchedPopulationPlan(GAIL): the Mixup learners of one population share mixup_alpha (got {sorted(alphas)})'
+      pop.mixup_alpha = alphas.pop()
+      if pop.mixup_alpha != 1.0:
+        extras = [_lib.GailExtra(eps_mix=p.eps_mix.data_ptr()) for p in plans]
+        pop._extras_host = (_lib.GailExtra * pop.L)(*extras)   # the entry point decides its refusals on this copy
+        pop.extras = _device_array(extras, dev)
+
+  def reward(self, pop, st):
+    """Mixup with alpha != 1: the coefficient launch inside reads each learner's update counter on the device, like the gradient launch behind it does for its
+    gradient-penalty draws - both sit behind the previous update's actor step, which bumps it."""
+    L, p0 = _lib.lib(), pop.plans[0]
+    if pop.mixup_alpha is None:
+      _lib.check(L.il_gail_step_population(_lib.ptr(pop.disc_descs), _lib.ptr(pop.batches), _lib.ptr(pop.expert_batches), _lib.ptr(pop.reward_ptrs), pop.L, C.byref(p0.disc), st))
+    else:
+      _lib.check(L.il_gail_mixup_step_population(_lib.ptr(pop.disc_descs), _lib.ptr(pop.batches), _lib.ptr(pop.expert_batches), _lib.ptr(pop.reward_ptrs), pop.L, C.byref(p0.disc),
+                                                 _lib.ptr(pop.extras) if pop.extras is not None else None,
+                                                 C.cast(pop._extras_host, C.c_void_p) if pop._extras_host is not None else None, pop.mixup_alpha, st))
+
+
+class _RedStep(_SacStep):
+  """RED learners: `il_red_reward_population`, every learner's eval-mode reward under its own predictor and target arenas and sigma_1 (set_sigma), read on the device from
+  its descriptor (8 workgroups per learner at batch 256)."""
+
+  def check(self, plans):
+    shape = lambda r: (r.state_dim, r.action_dim, r.hidden, r.depth, r.activation, r.state_only, r.batch)   # what sizes il_red_reward_population's tile and grid
+    assert all(shape(p.red) == shape(plans[0].red) for p in plans), 'BatchedPopulationPlan(RED): the discriminators of one population share dims, hidden, depth, activation, state_only and batch'
+    _refuse_mixing(plans, 'RED')
+
+  def build(self, pop, plans, dev):
+    pop.red_descs = _device_array([p.red for p in plans], dev)
+    pop.reward_ptrs = _reward_ptrs(plans, dev)
+
+  def reward(self, pop, st):
+    assert not any(p.discriminator.training for p in pop.plans), 'BatchedPopulationPlan(RED): discriminator.eval() first (train.py:147)'
+    _lib.check(_lib.lib().il_red_reward_population(_lib.ptr(pop.red_descs), _lib.ptr(pop.batches), _lib.ptr(pop.reward_ptrs), pop.L, C.byref(pop.plans[0].red), st))
+
+
+class _GmmilStep(_SacStep):
+  """GMMIL learners: `il_gmmil_reward_population`, every learner's kernel-mean-embedding reward on its own batches, under its own frozen bandwidths, with its own workspace
+  (16 workgroups per learner at batch 128). The FIRST run() is eager - every learner fixes its bandwidths from its first batch on the host (models.py:193-195), one read per
+  learner, once - and cannot be captured; from the second on an update is the same launches as for the others."""
+
+  def check(self, plans):
+    shape = lambda d: (d.state_size, d.action_size, bool(d.state_only))   # with B: what sizes il_gmmil_reward_population's grid, column block and workspaces
+    assert all(shape(p.discriminator) == shape(plans[0].discriminator) for p in plans), 'BatchedPopulationPlan(GMMIL): the learners of one population share state_size, action_size and state_only'
+    _refuse_mixing(plans, 'GMMIL')
+
+  def build(self, pop, plans, dev):
+    pop.gmmil_learners = None   # the il_gmmil_learner array, built once every learner's bandwidths are frozen (after the first run())
+
+  def first_update(self, pop, st, prepared) -> bool:
+    if any(p.discriminator.gamma_1 is None for p in pop.plans):
+      # the first update: each learner's own median heuristic on its first batch (host-side, once), its reward by its own eager call; then the SAC launches in stream order
+      assert not torch.cuda.is_current_stream_capturing(), 'UpdatePlan(GMMIL): run() once before capture() (the first batch fixes the kernel bandwidths)'
+      for p in pop.plans: p._enqueue_reward_model(st)
+      pop._sac_update(prepared, st)
+      pop._prepared = True
+      self.freeze(pop)   # here, not in the next run(): that one may be captured, and the array's upload is no graph node
+      return True
+    if pop.gmmil_learners is None: self.freeze(pop)
+    return False
+
+  def freeze(self, pop):
+    """Once, after the first update froze every learner's bandwidths: the device array il_gmmil_reward_population indexes with the learner id - each learner's two
+    batch descriptors, gamma_1 and gamma_2, its reward buffer, and its own zero-filled workspace (own partial sums and arrival counters), kept by the plan."""
+    p0, dev = pop.plans[0], pop.plans[0].rows.device
+    d0 = p0.discriminator
+    D = d0.state_size + (0 if d0.state_only else d0.action_size)
+    pop.gmmil_ws_floats = int(_lib.lib().il_gmmil_workspace_floats(pop.B, pop.B, D))
+    stride = (pop.gmmil_ws_floats + 63) // 64 * 64   # every learner's workspace starts on a 256-byte boundary (the partial sums leave as 8-byte exchanges)
+    pop.gmmil_ws = torch.zeros((pop.L, stride), dtype=torch.float32, device=dev)
+    pop.gmmil_whole_lanes = gmmil_whole_lanes([b for p in pop.plans for b in (p.pb, p.eb)], d0.state_size, d0.action_size, d0.state_only)
+    pop.gmmil_learners = _device_array([_lib.GmmilLearner(p.pb, p.eb, float(p.discriminator.gamma_1), float(p.discriminator.gamma_2), pop.gmmil_ws[l].data_ptr(), p.rewards.data_ptr())
+                                        for l, p in enumerate(pop.plans)], dev)
+
+  def before_capture(self, pop):
+    assert not any(p.discriminator.gamma_1 is None for p in pop.plans), 'UpdatePlan(GMMIL): run() once before capture() (the first batch fixes the kernel bandwidths)'
+    for sub in (pop.subs or [pop]):
+      if sub.gmmil_learners is None: self.freeze(sub)   # (learners whose bandwidths were fixed before this plan was built)
+
+  def reward(self, pop, st):
+    d0 = pop.plans[0].discriminator
+    _lib.check(_lib.lib().il_gmmil_reward_population(_lib.ptr(pop.gmmil_learners), pop.L, pop.B, pop.B, d0.state_size, d0.action_size, int(d0.state_only), pop.gmmil_whole_lanes,
+                                                     pop.gmmil_ws_floats, st))
+
+
+class _DrilStep(_SacStep):
+  """DRIL learners: `il_dril_reward_population`, every learner's Monte-Carlo-dropout reward under its own ensemble, threshold q, Philox key and device counter (UpdatePlan
+  pointed it at the learner's SAC counter), read on the device from its descriptor (5-member ensembles, 8 rows per workgroup: 32 workgroups per learner at batch 256). With
+  `bc_aux` also `il_bc_step_population`, the behavioural-cloning auxiliary step of every actor on its own expert batch (train.py:201): on the main stream, in front of the
+  forward kernels that read the actor it moves; the reward launch reads neither the actor nor its workspace."""
+
+  def check(self, plans):
+    shape = lambda d: (d.state_dim, d.action_dim, d.hidden, d.depth, d.activation, d.p_in, d.p, d.batch)   # what sizes il_dril_reward_population's tile and grid and sets its keep probability
+    assert all(shape(p.dril) == shape(plans[0].dril) for p in plans), 'BatchedPopulationPlan(DRIL): the ensembles of one population share dims, hidden, depth, activation, both dropout probabilities and batch'
+    assert all(p.discriminator.q is not None for p in plans), 'BatchedPopulationPlan(DRIL): set_uncertainty_threshold first (train.py:126)'
+    assert not any(p.mix_expert for p in plans), 'BatchedPopulationPlan(DRIL): mixed batches have no population launches'
+    assert len({p.bc_aux for p in plans}) == 1, 'BatchedPopulationPlan(DRIL): the BC auxiliary step (il_bc_step_population) runs for every learner of a population or for none'
+
+  def build(self, pop, plans, dev):
+    pop.dril_descs = _device_array([p.dril for p in plans], dev)
+    pop.reward_ptrs = _reward_ptrs(plans, dev)
+    pop.bc_aux = bool(plans[0].bc_aux)
+    if pop.bc_aux: pop.expert_batches = _device_array([p.eb for p in plans], dev)
+
+  def reward(self, pop, st):
+    # at the offset UpdatePlan uses. The launch only READS the learners' noise counters, which the actor optimiser launch of the SKIP_FORWARD half bumps: behind the join,
+    # and in front of the next update's fork (side.wait_stream(main)), so both schedules read the value plan.run() reads
+    _lib.check(_lib.lib().il_dril_reward_population(_lib.ptr(pop.dril_descs), _lib.ptr(pop.batches), _lib.ptr(pop.reward_ptrs), None, pop.L, C.byref(pop.plans[0].dril), 0x40000000, st))
+
+  def before_forward(self, pop, st):
+    if pop.bc_aux:
+      _lib.check(_lib.lib().il_bc_step_population(_lib.ptr(pop.sac_descs), _lib.ptr(pop.expert_batches), pop.L, C.byref(pop.plans[0].sac), None, 0, st))
+
+
+class _AdrilStep(_SacStep):
+  """AdRIL / SQIL learners: `il_batch_mix_relabel_population`, every learner's expert rows mixed in and its rewards relabelled (models.py:293-318) under its own {n_expert,
+  round, policy trajectories} and 1 / |expert trajectories|: ONE launch between the gathers and the SAC launches, on the one stream - it edits the rows the forward kernels
+  read. label, update_freq, n and the row are the launch's, everything else is the learner's. The per-update scalars live in one (L, 3) device tensor, `pop.dyn`: learner
+  l's il_mix_learner.dyn points at row l (8-byte words, so every row is aligned)."""
+
+  def check(self, plans):
+    p0 = plans[0]
+    shape = lambda p: (p.B, p.discriminator.update_freq, p.discriminator.balanced, p.memory.row, p.expert_memory.row, p.memory.state_size, p.memory.action_size)
+    assert all(shape(p) == shape(p0) for p in plans) and p0.memory.row == p0.expert_memory.row, 'BatchedPopulationPlan(AdRIL): the relabellers of one population share batch, update_freq, balanced and the ring row'
+    _refuse_mixing(plans, 'AdRIL')
+
+  def build(self, pop, plans, dev):
+    import numpy as np
+    r0 = plans[0].discriminator
+    pop.dyn = torch.zeros((pop.L, 3), dtype=torch.int64, device=dev)
+    pop._dyn_set = False
+    assert all(p.rows.data_ptr() % 16 == 0 and p.erows.data_ptr() % 16 == 0 for p in plans), 'BatchedPopulationPlan(AdRIL): row buffers off the 16-byte grid'
+    pop.mix_learners = _device_array([_lib.MixLearner(p.rows.data_ptr(), p.erows.data_ptr(), pop.dyn[l].data_ptr(),
+                                                      float(np.float32(1 / p.expert_memory.num_trajectories)) if r0.update_freq > 0 else 0.0)
+                                      for l, p in enumerate(plans)], dev)
+    pop.mix_label = 2 if r0.update_freq > 0 else 1
+
+  def relabel_args(self, pop, step: int, num_trajectories):
+    words = []
+    for p, count in zip(pop.plans, num_trajectories):
+      r = p.discriminator
+      if r.balanced:
+        n_expert = pop.B if r.sample_expert else 0
+        r.sample_expert = not r.sample_expert
+      else:
+        n_expert = pop.B // 2
+      words.append([n_expert, -(-int(step) // r.update_freq) if r.update_freq > 0 else 0, int(count)])
+    pop.dyn.copy_(torch.tensor(words, dtype=torch.int64))   # pageable source: staged synchronously, ordered on the current stream
+    pop._dyn_set = True
+
+  def before_launch(self, pop):
+    # a captured launch reads whatever relabel_args() stored before it is replayed
+    assert torch.cuda.is_current_stream_capturing() or pop._dyn_set, 'BatchedPopulationPlan(AdRIL): call relabel_args(step, [memory.num_trajectories ...]) before every update'
+
+  def before_forward(self, pop, st):
+    p0 = pop.plans[0]
+    m = p0.memory
+    _lib.check(_lib.lib().il_batch_mix_relabel_population(_lib.ptr(pop.mix_learners), pop.L, pop.B, m.state_size, m.action_size, pop.mix_label, p0.discriminator.update_freq, st))
+    if not torch.cuda.is_current_stream_capturing(): pop._dyn_set = False
+
+
+POPULATION_STEPS = {'SAC': _SacStep(), 'GAIL': _GailStep(), 'RED': _RedStep(), 'GMMIL': _GmmilStep(), 'DRIL': _DrilStep(), 'PWIL': _PwilStep(), 'AdRIL': _AdrilStep()}
+
+
+class BatchedPopulationPlan(_Branches):
   """N independent learners with identical shapes advanced by the SAME kernel launches (`il_*_population`): the learner id is a grid
   dimension, so one update of the whole population costs 11 launches instead of 11 N.  This is the route from the latency-bound
   single-learner regime towards the HBM roofline.  Every learner keeps its own replay ring, MT19937 index stream,
-  networks, optimiser state, scratch and Philox counter (build the `UpdatePlan`s with distinct `learner_id`s).  SAC, GAIL (`il_gail_step_population`: discriminator step +
-  relabel; learners whose loss is Mixup: `il_gail_mixup_step_population`, at any shared `mixup_alpha`), DRIL (`il_dril_reward_population`: every learner's Monte-Carlo-dropout reward under its own ensemble, threshold, Philox key and counter; with `bc_aux` also
-  `il_bc_step_population`, the behavioural-cloning auxiliary step of every actor on its own expert batch, in front of the forward kernels), RED (`il_red_reward_population`: every learner's eval-mode reward under its own predictor, target and sigma_1) and GMMIL (`il_gmmil_reward_population`: every
-  learner's kernel-mean-embedding reward on its own batches, under its own frozen bandwidths, with its own workspace) learners, and PWIL learners, whose update is SAC's (no
-  reward step: the acting side stores the coupling reward with every transition), and AdRIL / SQIL learners (`il_batch_mix_relabel_population`: every learner's expert
-  rows mixed in and its rewards relabelled under its own {n_expert, round, policy trajectories} and 1 / |expert trajectories|, ONE launch between the gathers and the SAC
-  launches, on the one stream - it edits the rows the forward kernels read; `relabel_args(step, [num_trajectories ...])` stages the 3 L words of the next update with one
-  stream-ordered copy and is due before every run() / replay(), like `UpdatePlan.relabel_args`); GAIL's, DRIL's, RED's and GMMIL's reward launches run
-  on a second stream beside the reward-independent forward kernels (IL_POP_OVERLAP=0: in stream order).  GMMIL: the FIRST run() is eager - every learner fixes its
-  bandwidths from its first batch on the host (models.py:193-195), one read per learner, once - and cannot be captured; from the second on an update is the same launches
-  as for the others."""
+  networks, optimiser state, scratch and Philox counter (build the `UpdatePlan`s with distinct `learner_id`s).
+
+  What an algorithm adds to the gathers and the SAC launches is its entry of POPULATION_STEPS; run() is the schedule they share. The steps that have a reward launch (GAIL,
+  RED, GMMIL, DRIL) run it on a second stream beside the reward-independent forward kernels (IL_POP_OVERLAP=0: in stream order)."""
 
   def __init__(self, plans, groups: Optional[int] = None):
     self.plans = list(plans)
@@ -1487,32 +1702,14 @@ class BatchedPopulationPlan:
       self.subs = [BatchedPopulationPlan(self.plans[i:i + per], groups=1) for i in range(0, len(self.plans), per)]
       self.streams = [torch.cuda.Stream() for _ in self.subs]
       for sub in self.subs: sub.side = None   # nested fork / join breaks hipGraph capture on ROCm 7.2: inside a branch the discriminator kernels stay in stream order (the other branches run beside them)
-      self.algorithm, self.B, self.L, self.graph = self.subs[0].algorithm, self.subs[0].B, len(self.plans), None
+      self.algorithm, self.B, self.L, self.step = self.subs[0].algorithm, self.subs[0].B, len(self.plans), self.subs[0].step
       return
     for p in self.plans:
       p._set_device_sync(False)   # one stream, one set of launches for all learners: plain stream order
     p0 = self.plans[0]
-    assert all(p.algorithm == p0.algorithm and p.B == p0.B for p in self.plans) and p0.algorithm in ('SAC', 'GAIL', 'RED', 'GMMIL', 'DRIL', 'PWIL', 'AdRIL'), 'the population launches exist for SAC, GAIL, RED, GMMIL, DRIL, PWIL and AdRIL learners of one batch size'
-    if p0.algorithm == 'AdRIL':   # il_batch_mix_relabel_population: label, update_freq, n and the row are the launch's, everything else is the learner's
-      shape = lambda p: (p.B, p.discriminator.update_freq, p.discriminator.balanced, p.memory.row, p.expert_memory.row, p.memory.state_size, p.memory.action_size)
-      assert all(shape(p) == shape(p0) for p in self.plans) and p0.memory.row == p0.expert_memory.row, 'BatchedPopulationPlan(AdRIL): the relabellers of one population share batch, update_freq, balanced and the ring row'
-      assert not any(p.mix_expert or p.bc_aux for p in self.plans), 'BatchedPopulationPlan(AdRIL): mixed batches / the BC auxiliary step have no population launches'
-    if p0.algorithm == 'PWIL':   # a SAC update: PWIL's reward is stored with every transition, by the acting side (PopulationActingWorker(reward_models=...): il_pwil_act_reward_population)
-      assert not any(p.mix_expert or p.bc_aux for p in self.plans), 'BatchedPopulationPlan(PWIL): mixed batches / the BC auxiliary step have no population launches'
-    if p0.algorithm == 'RED':
-      shape = lambda r: (r.state_dim, r.action_dim, r.hidden, r.depth, r.activation, r.state_only, r.batch)   # what sizes il_red_reward_population's tile and grid
-      assert all(shape(p.red) == shape(p0.red) for p in self.plans), 'BatchedPopulationPlan(RED): the discriminators of one population share dims, hidden, depth, activation, state_only and batch'
-      assert not any(p.mix_expert or p.bc_aux for p in self.plans), 'BatchedPopulationPlan(RED): mixed batches / the BC auxiliary step have no population launches'
-    if p0.algorithm == 'GMMIL':
-      shape = lambda d: (d.state_size, d.action_size, bool(d.state_only))   # with B: what sizes il_gmmil_reward_population's grid, column block and workspaces
-      assert all(shape(p.discriminator) == shape(p0.discriminator) for p in self.plans), 'BatchedPopulationPlan(GMMIL): the learners of one population share state_size, action_size and state_only'
-      assert not any(p.mix_expert or p.bc_aux for p in self.plans), 'BatchedPopulationPlan(GMMIL): mixed batches / the BC auxiliary step have no population launches'
-    if p0.algorithm == 'DRIL':
-      shape = lambda d: (d.state_dim, d.action_dim, d.hidden, d.depth, d.activation, d.p_in, d.p, d.batch)   # what sizes il_dril_reward_population's tile and grid and sets its keep probability
-      assert all(shape(p.dril) == shape(p0.dril) for p in self.plans), 'BatchedPopulationPlan(DRIL): the ensembles of one population share dims, hidden, depth, activation, both dropout probabilities and batch'
-      assert all(p.discriminator.q is not None for p in self.plans), 'BatchedPopulationPlan(DRIL): set_uncertainty_threshold first (train.py:126)'
-      assert not any(p.mix_expert for p in self.plans), 'BatchedPopulationPlan(DRIL): mixed batches have no population launches'
-      assert len({p.bc_aux for p in self.plans}) == 1, 'BatchedPopulationPlan(DRIL): the BC auxiliary step (il_bc_step_population) runs for every learner of a population or for none'
+    assert all(p.algorithm == p0.algorithm and p.B == p0.B for p in self.plans) and p0.algorithm in POPULATION_STEPS, 'the population launches exist for SAC, GAIL, RED, GMMIL, DRIL, PWIL and AdRIL learners of one batch size'
+    self.step = POPULATION_STEPS[p0.algorithm]
+    self.step.check(self.plans)
     if any(getattr(p, 'general', False) for p in self.plans):
       raise NotImplementedError('BatchedPopulationPlan: actor / critic shapes outside depth 2 / ReLU / hidden <= 256 / action_size <= 8 have no population launches (PopulationPlan runs them as independent graph branches)')
     self.algorithm, self.B, self.L, dev = p0.algorithm, p0.B, len(self.plans), p0.rows.device
@@ -1527,45 +1724,10 @@ class BatchedPopulationPlan:
                                   p.eidx.data_ptr() if e else None, p.erows.data_ptr() if e else None))
     self.sample_args = _device_array(args, dev)
     self.max_row = max([p.memory.row for p in self.plans] + [p.expert_memory.row for p in self.plans if p.has_expert])
-    if self.algorithm == 'GAIL':
-      self.disc_descs = _device_array([p.disc for p in self.plans], dev)
-      self.expert_batches = _device_array([p.eb for p in self.plans], dev)
-      self.reward_ptrs = torch.tensor([p.rewards.data_ptr() for p in self.plans], dtype=torch.int64, device=dev)
-      # Mixup (il_gail_mixup_step_population): alpha = 1 mixes with the on-chip U(0,1) stream of every learner's key and counter; any other alpha has ONE launch draw every
-      # learner's Beta(alpha, alpha) coefficients into its own `eps_mix` (UpdatePlan allocated it) in front of the gradient launch - where plan.run() has il_noise_fill_beta
-      assert len({int(p.disc.loss_function) for p in self.plans}) == 1, 'BatchedPopulationPlan(GAIL): the discriminators of one population share loss_function'
-      self.mixup_alpha, self.extras, self._extras_host = None, None, None
-      if int(p0.disc.loss_function) == LOSS_FUNCTIONS['Mixup']:
-        alphas = {1.0 if p._beta_alpha is None else float(p._beta_alpha) for p in self.plans}
-        assert len(alphas) == 1, f'BatchedPopulationPlan(GAIL): the Mixup learners of one population share mixup_alpha (got {sorted(alphas)})'
-        self.mixup_alpha = alphas.pop()
-        if self.mixup_alpha != 1.0:
-          extras = [_lib.GailExtra(eps_mix=p.eps_mix.data_ptr()) for p in self.plans]
-          self._extras_host = (_lib.GailExtra * self.L)(*extras)   # the entry point decides its refusals on this copy
-          self.extras = _device_array(extras, dev)
-    if self.algorithm == 'RED':   # every learner's own predictor / target arenas and sigma_1 (set_sigma): read on the device from its descriptor
-      self.red_descs = _device_array([p.red for p in self.plans], dev)
-      self.reward_ptrs = torch.tensor([p.rewards.data_ptr() for p in self.plans], dtype=torch.int64, device=dev)
     self.bc_aux = False
-    if self.algorithm == 'DRIL':   # every learner's own ensemble, threshold q, Philox key and device counter (UpdatePlan pointed it at the learner's SAC counter): read on the device from its descriptor
-      self.dril_descs = _device_array([p.dril for p in self.plans], dev)
-      self.reward_ptrs = torch.tensor([p.rewards.data_ptr() for p in self.plans], dtype=torch.int64, device=dev)
-      self.bc_aux = bool(p0.bc_aux)
-      if self.bc_aux: self.expert_batches = _device_array([p.eb for p in self.plans], dev)
-    if self.algorithm == 'AdRIL':   # one (L, 3) device tensor for the per-update scalars: learner l's il_mix_learner.dyn points at row l (8-byte words, so every row is aligned)
-      import numpy as np
-      r0 = p0.discriminator
-      self.dyn = torch.zeros((self.L, 3), dtype=torch.int64, device=dev)
-      self._dyn_set = False
-      assert all(p.rows.data_ptr() % 16 == 0 and p.erows.data_ptr() % 16 == 0 for p in self.plans), 'BatchedPopulationPlan(AdRIL): row buffers off the 16-byte grid'
-      self.mix_learners = _device_array([_lib.MixLearner(p.rows.data_ptr(), p.erows.data_ptr(), self.dyn[l].data_ptr(),
-                                                         float(np.float32(1 / p.expert_memory.num_trajectories)) if r0.update_freq > 0 else 0.0)
-                                         for l, p in enumerate(self.plans)], dev)
-      self.mix_label = 2 if r0.update_freq > 0 else 1
-    self.gmmil_learners = None   # GMMIL: the il_gmmil_learner array, built once every learner's bandwidths are frozen (after the first run())
-    self.graph = None
+    self.step.build(self, self.plans, dev)
     self._prepared = False
-    self.side = torch.cuda.Stream() if self.algorithm in ('GAIL', 'RED', 'GMMIL', 'DRIL') and os.environ.get('IL_POP_OVERLAP', '1') != '0' else None
+    self.side = torch.cuda.Stream() if self.step.reward is not None and os.environ.get('IL_POP_OVERLAP', '1') != '0' else None
 
   def relabel_args(self, step: int, num_trajectories):
     """AdRIL / SQIL: `UpdatePlan.relabel_args` for every learner of the population (`num_trajectories`: one count per learner, in plan order) - each learner's balanced
@@ -1577,126 +1739,37 @@ class BatchedPopulationPlan:
       for sub in self.subs:
         sub.relabel_args(step, num_trajectories[at:at + sub.L]); at += sub.L
       return
-    words = []
-    for p, count in zip(self.plans, num_trajectories):
-      r = p.discriminator
-      if r.balanced:
-        n_expert = self.B if r.sample_expert else 0
-        r.sample_expert = not r.sample_expert
-      else:
-        n_expert = self.B // 2
-      words.append([n_expert, -(-int(step) // r.update_freq) if r.update_freq > 0 else 0, int(count)])
-    self.dyn.copy_(torch.tensor(words, dtype=torch.int64))   # pageable source: staged synchronously, ordered on the current stream
-    self._dyn_set = True
+    self.step.relabel_args(self, step, num_trajectories)
 
-  def _gail_step(self, st):
-    """Discriminator step + relabel of every learner on stream `st`. Mixup with alpha != 1: the coefficient launch inside reads each learner's update counter on the device,
-    like the gradient launch behind it does for its gradient-penalty draws - both sit behind the previous update's actor step, which bumps it."""
-    L, p0 = _lib.lib(), self.plans[0]
-    if self.mixup_alpha is None:
-      _lib.check(L.il_gail_step_population(_lib.ptr(self.disc_descs), _lib.ptr(self.batches), _lib.ptr(self.expert_batches), _lib.ptr(self.reward_ptrs), self.L, C.byref(p0.disc), st))
-    else:
-      _lib.check(L.il_gail_mixup_step_population(_lib.ptr(self.disc_descs), _lib.ptr(self.batches), _lib.ptr(self.expert_batches), _lib.ptr(self.reward_ptrs), self.L, C.byref(p0.disc),
-                                                 _lib.ptr(self.extras) if self.extras is not None else None,
-                                                 C.cast(self._extras_host, C.c_void_p) if self._extras_host is not None else None, self.mixup_alpha, st))
+  def _sac_update(self, flags: int, st):
+    _lib.check(_lib.lib().il_sac_update_population(_lib.ptr(self.sac_descs), _lib.ptr(self.batches), self.L, C.byref(self.plans[0].sac), flags, st))
 
   def run(self):
     if self.subs is not None:
-      main = torch.cuda.current_stream()
-      for sub, s in zip(self.subs, self.streams):
-        s.wait_stream(main)
-        with torch.cuda.stream(s):
-          sub.run()
-      for s in self.streams:
-        main.wait_stream(s)
-      return
-    L, st, p0 = _lib.lib(), _lib.stream_ptr(), self.plans[0]
+      return self._run_branches(self.subs)
+    step, st = self.step, _lib.stream_ptr()
     prepared = _lib.IL_FLAG_SAC_PREPARED if (self._prepared and not self.bc_aux) else 0   # the BC auxiliary step moves the actor every update: its lane-ordered copies are re-derived (UpdatePlan.run: flag = 0)
-    if self.algorithm == 'AdRIL':   # asked in front of the first launch: a refused update draws no indices
-      capturing = torch.cuda.is_current_stream_capturing()   # a captured launch reads whatever relabel_args() stored before it is replayed
-      assert capturing or self._dyn_set, 'BatchedPopulationPlan(AdRIL): call relabel_args(step, [memory.num_trajectories ...]) before every update'
-    _lib.check(L.il_replay_sample_population(_lib.ptr(self.sample_args), self.L, self.B, self.max_row, st))
-    if self.algorithm == 'AdRIL':   # models.py:293-318 for every learner, in stream order between the gathers and the forward kernels that read the rows it edits
-      m = p0.memory
-      _lib.check(L.il_batch_mix_relabel_population(_lib.ptr(self.mix_learners), self.L, self.B, m.state_size, m.action_size, self.mix_label, p0.discriminator.update_freq, st))
-      if not capturing: self._dyn_set = False
-    if self.algorithm == 'RED':
-      assert not any(p.discriminator.training for p in self.plans), 'BatchedPopulationPlan(RED): discriminator.eval() first (train.py:147)'
-    if self.algorithm == 'GMMIL':
-      if any(p.discriminator.gamma_1 is None for p in self.plans):
-        # the first update: each learner's own median heuristic on its first batch (host-side, once), its reward by its own eager call; then the SAC launches in stream order
-        assert not torch.cuda.is_current_stream_capturing(), 'UpdatePlan(GMMIL): run() once before capture() (the first batch fixes the kernel bandwidths)'
-        for p in self.plans: p._enqueue_reward_model(st)
-        _lib.check(L.il_sac_update_population(_lib.ptr(self.sac_descs), _lib.ptr(self.batches), self.L, C.byref(p0.sac), prepared, st))
-        self._prepared = True
-        self._gmmil_freeze()   # here, not in the next run(): that one may be captured, and the array's upload is no graph node
-        return
-      if self.gmmil_learners is None: self._gmmil_freeze()
-      d0 = p0.discriminator
-      gmmil_args = (_lib.ptr(self.gmmil_learners), self.L, self.B, self.B, d0.state_size, d0.action_size, int(d0.state_only), self.gmmil_whole_lanes, self.gmmil_ws_floats)
-    if self.algorithm == 'DRIL':
-      # the Monte-Carlo-dropout reward of every learner at the offset UpdatePlan uses. It only READS the learners' noise counters, which the actor optimiser launch of the
-      # SKIP_FORWARD half bumps: behind the join below, and in front of the next update's fork (side.wait_stream(main)), so both schedules read the value plan.run() reads
-      dril_args = (_lib.ptr(self.dril_descs), _lib.ptr(self.batches), _lib.ptr(self.reward_ptrs), None, self.L, C.byref(p0.dril), 0x40000000)
-    if self.algorithm in ('GAIL', 'RED', 'GMMIL', 'DRIL') and self.side is not None:
+    step.before_launch(self)
+    _lib.check(_lib.lib().il_replay_sample_population(_lib.ptr(self.sample_args), self.L, self.B, self.max_row, st))
+    if step.first_update(self, st, prepared): return
+    if self.side is not None:
       # The discriminator kernels (48 small workgroups per learner, latency-bound: ~60 us of a ~450 us replay at 32 learners) run on a second stream beside the
       # reward-independent forward kernels of every learner and join before the critic loss. One fork / join per replay (its ~10 us of queue signalling is paid once
       # for the whole population, unlike in the single-learner update where it is why the branches hand over on the device instead).
       main = torch.cuda.current_stream()
       self.side.wait_stream(main)
       with torch.cuda.stream(self.side):
-        if self.algorithm == 'GAIL':
-          self._gail_step(_lib.stream_ptr())
-        elif self.algorithm == 'RED':   # the eval-mode reward of every learner (8 workgroups per learner at batch 256), the same fork and join
-          _lib.check(L.il_red_reward_population(_lib.ptr(self.red_descs), _lib.ptr(self.batches), _lib.ptr(self.reward_ptrs), self.L, C.byref(p0.red), _lib.stream_ptr()))
-        elif self.algorithm == 'DRIL':   # 5-member ensembles, 8 rows per workgroup (32 workgroups per learner at batch 256), the same fork and join
-          _lib.check(L.il_dril_reward_population(*dril_args, _lib.stream_ptr()))
-        else:   # GMMIL: every learner's reward (16 workgroups per learner at batch 128), the same fork and join
-          _lib.check(L.il_gmmil_reward_population(*gmmil_args, _lib.stream_ptr()))
-      if self.bc_aux:   # train.py:201 on the main stream, in front of the forward kernels that read the actor it moves; the reward launch reads neither the actor nor its workspace
-        _lib.check(L.il_bc_step_population(_lib.ptr(self.sac_descs), _lib.ptr(self.expert_batches), self.L, C.byref(p0.sac), None, 0, st))
-      _lib.check(L.il_sac_update_population(_lib.ptr(self.sac_descs), _lib.ptr(self.batches), self.L, C.byref(p0.sac), prepared | _lib.IL_FLAG_SAC_FORWARD_ONLY, st))
+        step.reward(self, _lib.stream_ptr())
+    elif step.reward is not None:
+      step.reward(self, st)
+    step.before_forward(self, st)   # behind the reward launch in the issue order of either schedule
+    if self.side is not None:
+      self._sac_update(prepared | _lib.IL_FLAG_SAC_FORWARD_ONLY, st)
       main.wait_stream(self.side)
-      _lib.check(L.il_sac_update_population(_lib.ptr(self.sac_descs), _lib.ptr(self.batches), self.L, C.byref(p0.sac), _lib.IL_FLAG_SAC_SKIP_FORWARD, st))
+      self._sac_update(_lib.IL_FLAG_SAC_SKIP_FORWARD, st)
     else:
-      if self.algorithm == 'GAIL':
-        self._gail_step(st)
-      if self.algorithm == 'RED':
-        _lib.check(L.il_red_reward_population(_lib.ptr(self.red_descs), _lib.ptr(self.batches), _lib.ptr(self.reward_ptrs), self.L, C.byref(p0.red), st))
-      if self.algorithm == 'GMMIL':
-        _lib.check(L.il_gmmil_reward_population(*gmmil_args, st))
-      if self.algorithm == 'DRIL':
-        _lib.check(L.il_dril_reward_population(*dril_args, st))
-        if self.bc_aux:
-          _lib.check(L.il_bc_step_population(_lib.ptr(self.sac_descs), _lib.ptr(self.expert_batches), self.L, C.byref(p0.sac), None, 0, st))
-      _lib.check(L.il_sac_update_population(_lib.ptr(self.sac_descs), _lib.ptr(self.batches), self.L, C.byref(p0.sac), prepared, st))
+      self._sac_update(prepared, st)
     self._prepared = True
 
-  def _gmmil_freeze(self):
-    """GMMIL, once, after the first update froze every learner's bandwidths: the device array il_gmmil_reward_population indexes with the learner id - each learner's two
-    batch descriptors, gamma_1 and gamma_2, its reward buffer, and its own zero-filled workspace (own partial sums and arrival counters), kept by this plan."""
-    p0, dev = self.plans[0], self.plans[0].rows.device
-    d0 = p0.discriminator
-    D = d0.state_size + (0 if d0.state_only else d0.action_size)
-    self.gmmil_ws_floats = int(_lib.lib().il_gmmil_workspace_floats(self.B, self.B, D))
-    stride = (self.gmmil_ws_floats + 63) // 64 * 64   # every learner's workspace starts on a 256-byte boundary (the partial sums leave as 8-byte exchanges)
-    self.gmmil_ws = torch.zeros((self.L, stride), dtype=torch.float32, device=dev)
-    self.gmmil_whole_lanes = gmmil_whole_lanes([b for p in self.plans for b in (p.pb, p.eb)], d0.state_size, d0.action_size, d0.state_only)
-    self.gmmil_learners = _device_array([_lib.GmmilLearner(p.pb, p.eb, float(p.discriminator.gamma_1), float(p.discriminator.gamma_2), self.gmmil_ws[l].data_ptr(), p.rewards.data_ptr())
-                                         for l, p in enumerate(self.plans)], dev)
-
-  def capture(self, warmup: int = 0):
-    for _ in range(warmup):
-      self.run()
-    if self.algorithm == 'GMMIL':   # asked in front of the capture: an exception inside one would leave the stream capturing
-      assert not any(p.discriminator.gamma_1 is None for p in self.plans), 'UpdatePlan(GMMIL): run() once before capture() (the first batch fixes the kernel bandwidths)'
-      for pop in (self.subs or [self]):
-        if pop.gmmil_learners is None: pop._gmmil_freeze()   # (learners whose bandwidths were fixed before this plan was built)
-    torch.cuda.synchronize()
-    self.graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(self.graph):
-      self.run()
-    return self
-
-  def replay(self):
-    self.graph.replay()
+  def _before_capture(self):
+    self.step.before_capture(self)

@@ -64,6 +64,89 @@ def pretrain_bc(cfg, actor, expert_memory, state_size, action_size):
     il.behavioural_cloning_update(actor, batch, optimiser)
 
 
+class _Learner:
+  """Everything one learner owns: train() has one, a seed sweep one per job."""
+
+
+def new_metrics() -> dict:
+  return dict(train_steps=[], train_returns=[], test_steps=[], test_returns=[], test_returns_normalized=[], update_steps=[], predicted_rewards=[], alphas=[], entropies=[], Q_values=[])
+
+
+def build_agent(ln, cfg, state_size, action_size, dev):
+  """Actor, critic, target, the three optimisers and the replay memory of one learner, as attributes of `ln` - in the order that consumes the process seed, which the
+  caller has set in front."""
+  ln.actor, ln.critic, ln.log_alpha = il.SoftActor(state_size, action_size, cfg.reinforcement.actor), il.TwinCritic(state_size, action_size, cfg.reinforcement.critic), torch.zeros(1, device=dev)
+  ln.target_critic, ln.entropy_target = il.create_target_network(ln.critic), cfg.reinforcement.target_temperature * action_size
+  ln.actor_optimiser = il.AdamW(ln.actor, lr=cfg.training.learning_rate, weight_decay=cfg.training.weight_decay)
+  ln.critic_optimiser = il.AdamW(ln.critic, lr=cfg.training.learning_rate, weight_decay=cfg.training.weight_decay)
+  ln.temperature_optimiser = il.Adam(ln.log_alpha, lr=cfg.training.learning_rate)
+  ln.memory = il.ReplayMemory(cfg.memory.size, state_size, action_size, cfg.imitation.absorbing)
+
+
+def build_reward_model(cfg, state_size, action_size, expert_memory, max_episode_steps):
+  """(discriminator, its optimiser) of cfg.algorithm, built behind the agent; (None, None) for SAC and BC."""
+  with_optimiser = lambda d: (d, il.AdamW(d, lr=cfg.imitation.learning_rate, weight_decay=cfg.imitation.weight_decay))
+  if cfg.algorithm == 'AdRIL':   # no parameters: its state is the balanced alternation (update_freq=0: SQIL)
+    return il.RewardRelabeller(cfg.imitation.update_freq, cfg.imitation.balanced), None
+  if cfg.algorithm == 'GAIL':
+    return with_optimiser(il.GAILDiscriminator(state_size, action_size, cfg.imitation, cfg.reinforcement.discount))
+  if cfg.algorithm == 'GMMIL':   # no parameters and no optimiser: its state is the two bandwidths the learner's first batch fixes
+    return il.GMMILDiscriminator(state_size, action_size, cfg.imitation), None
+  if cfg.algorithm == 'PWIL':   # the learner's own atoms: its expert data was subsampled under its seed
+    return il.PWILDiscriminator(state_size, action_size, cfg.imitation, expert_memory, max_episode_steps), None
+  if cfg.algorithm == 'DRIL':   # dropout policy ensemble (train.py:73 builds it as SoftActor(...))
+    return with_optimiser(il.DropoutSoftActor(state_size, action_size, cfg.imitation.discriminator))
+  if cfg.algorithm == 'RED':
+    return with_optimiser(il.REDDiscriminator(state_size, action_size, cfg.imitation))
+  return None, None
+
+
+def pretrain_reward_model(cfg, discriminator, discriminator_optimiser, expert_memory, state_size, action_size):
+  """train.py:114-134 for DRIL and RED: pretrain the "discriminator" on expert data, then fix its reward threshold / bandwidth. Runs while the learner's seed is the
+  process seed (the DRIL ensemble's descriptors read their Philox key from it)."""
+  B = cfg.training.batch_size
+  if pretraining_schedule(cfg) == 'plan' and cfg.imitation.pretraining.iterations > 0:
+    il.PretrainPlan(cfg.algorithm, discriminator, discriminator_optimiser, expert_memory, B, torch.Generator().manual_seed(cfg.seed)).run(cfg.imitation.pretraining.iterations)
+  else:
+    for batch in expert_batches(cfg, expert_memory, state_size, action_size, cfg.imitation.pretraining.iterations):
+      if cfg.algorithm == 'DRIL': il.behavioural_cloning_update(discriminator, batch, discriminator_optimiser)
+      else: il.target_estimation_update(discriminator, batch, discriminator_optimiser)
+  if cfg.algorithm == 'DRIL': discriminator.set_uncertainty_threshold(expert_memory['states'][:expert_memory.size], expert_memory['actions'][:expert_memory.size], cfg.imitation.quantile_cutoff)
+  else: discriminator.set_sigma(expert_memory['states'][:B], expert_memory['actions'][:B])
+
+
+def relabel_row_by_row(discriminator, expert_memory):
+  """PWIL's expert relabel (train.py:135-141) as the reference's loop, a host round trip per row: `+pretraining.schedule=per_function` (A/B runs) and atom sets outside
+  the one-launch coupling; the same bits as PWILDiscriminator.relabel_memory."""
+  for i in range(expert_memory.size):
+    tr = expert_memory[i]
+    expert_memory.rewards[i] = discriminator.compute_reward(tr['states'].unsqueeze(0), tr['actions'].unsqueeze(0))
+    if tr['terminals'] or tr['timeouts']: discriminator.reset()
+
+
+def record_evaluation(cfg, metrics, prefix, step, episode_returns, normalised):
+  """One evaluation into the metrics, and the plots of train.py:216-228."""
+  for key, value in (('test_steps', step), ('test_returns', episode_returns), ('test_returns_normalized', list(normalised))): metrics[key].append(value)
+  lineplot(metrics['test_steps'], metrics['test_returns'], filename=f'{prefix}test_returns', title=f'{cfg.algorithm}: {cfg.env} Test Returns')
+  if len(metrics['train_returns']) > 0:
+    lineplot(metrics['train_steps'], metrics['train_returns'], filename=f'{prefix}train_returns', title=f'Training {cfg.algorithm}: {cfg.env} Train Returns')
+  if cfg.logging.interval > 0 and len(metrics['update_steps']) > 0:   # train.py:224-228
+    if cfg.algorithm != 'SAC': lineplot(metrics['update_steps'], metrics['predicted_rewards'], filename=f'{prefix}predicted_rewards', yaxis='Predicted Reward', title=f'{cfg.algorithm}: {cfg.env} Predicted Rewards')
+    lineplot(metrics['update_steps'], metrics['alphas'], filename=f'{prefix}sac_alpha', yaxis='Alpha', title=f'{cfg.algorithm}: {cfg.env} Alpha')
+    lineplot(metrics['update_steps'], metrics['entropies'], filename=f'{prefix}sac_entropy', yaxis='Entropy', title=f'{cfg.algorithm}: {cfg.env} Entropy')
+    lineplot(metrics['update_steps'], metrics['Q_values'], filename=f'{prefix}Q_values', yaxis='Q-value', title=f'{cfg.algorithm}: {cfg.env} Q-values')
+
+
+def save_run(cfg, prefix, metrics, actor, critic, log_alpha, discriminator, eval_env):
+  """What a finished run leaves behind (train.py:231-240)."""
+  if cfg.save_trajectories:   # train.py:231-234
+    _, trajectories = evaluate_agent(actor, eval_env, cfg.evaluation.episodes, return_trajectories=True, render=cfg.render)
+    torch.save(trajectories, f'{prefix}trajectories.pth')
+  torch.save(dict(actor=actor.state_dict(), critic=critic.state_dict(), log_alpha=log_alpha), f'{prefix}agent.pth')
+  if cfg.algorithm in ('DRIL', 'GAIL', 'RED'): torch.save(discriminator.state_dict(), f'{prefix}discriminator.pth')   # train.py:238
+  torch.save(metrics, f'{prefix}metrics.pth')
+
+
 def check_timeouts_seen(plan, step, last_good):
   """Every update step, no synchronisation: the pinned host words a device-side wait stores into when it gives up (UpdatePlan.watch_timeouts). Raises within the pipeline
   depth of the expiry (one or two updates), naming the last step at which the words still read zero - checkpoints are only ever written after a clean check."""
@@ -118,33 +201,15 @@ def train(cfg, file_prefix: str = '') -> float:
   expert_memory = env.get_dataset(trajectories=cfg.imitation.trajectories, subsample=cfg.imitation.subsample, device=dev)
   state_size, action_size = env.observation_space.shape[0], env.action_space.shape[0]
 
-  actor, critic, log_alpha = il.SoftActor(state_size, action_size, cfg.reinforcement.actor), il.TwinCritic(state_size, action_size, cfg.reinforcement.critic), torch.zeros(1, device=dev)
-  target_critic, entropy_target = il.create_target_network(critic), cfg.reinforcement.target_temperature * action_size
-  actor_optimiser = il.AdamW(actor, lr=cfg.training.learning_rate, weight_decay=cfg.training.weight_decay)
-  critic_optimiser = il.AdamW(critic, lr=cfg.training.learning_rate, weight_decay=cfg.training.weight_decay)
-  temperature_optimiser = il.Adam(log_alpha, lr=cfg.training.learning_rate)
-  memory = il.ReplayMemory(cfg.memory.size, state_size, action_size, cfg.imitation.absorbing)
-
-  discriminator = discriminator_optimiser = None
-  if cfg.algorithm == 'AdRIL':
-    discriminator = il.RewardRelabeller(cfg.imitation.update_freq, cfg.imitation.balanced)
-  elif cfg.algorithm == 'GAIL':
-    discriminator = il.GAILDiscriminator(state_size, action_size, cfg.imitation, cfg.reinforcement.discount)
-    discriminator_optimiser = il.AdamW(discriminator, lr=cfg.imitation.learning_rate, weight_decay=cfg.imitation.weight_decay)
-  elif cfg.algorithm == 'GMMIL':
-    discriminator = il.GMMILDiscriminator(state_size, action_size, cfg.imitation)
-  elif cfg.algorithm == 'PWIL':
-    discriminator = il.PWILDiscriminator(state_size, action_size, cfg.imitation, expert_memory, env.max_episode_steps)
-  elif cfg.algorithm == 'DRIL':
-    discriminator = il.DropoutSoftActor(state_size, action_size, cfg.imitation.discriminator)   # dropout policy ensemble (train.py:73 builds it as SoftActor(...))
-    discriminator_optimiser = il.AdamW(discriminator, lr=cfg.imitation.learning_rate, weight_decay=cfg.imitation.weight_decay)
-  elif cfg.algorithm == 'RED':
-    discriminator = il.REDDiscriminator(state_size, action_size, cfg.imitation)
-    discriminator_optimiser = il.AdamW(discriminator, lr=cfg.imitation.learning_rate, weight_decay=cfg.imitation.weight_decay)
+  ln = _Learner()
+  build_agent(ln, cfg, state_size, action_size, dev)
+  actor, critic, log_alpha, target_critic, entropy_target, memory = ln.actor, ln.critic, ln.log_alpha, ln.target_critic, ln.entropy_target, ln.memory
+  actor_optimiser, critic_optimiser, temperature_optimiser = ln.actor_optimiser, ln.critic_optimiser, ln.temperature_optimiser
+  discriminator, discriminator_optimiser = build_reward_model(cfg, state_size, action_size, expert_memory, env.max_episode_steps)
 
   if world > 1:   # replicas start from rank 0's initialisation (the per-rank torch seeds differ)
     parallel.broadcast_parameters(parallel.replica_tensors(actor, critic, target_critic, log_alpha, discriminator))
-  metrics = dict(train_steps=[], train_returns=[], test_steps=[], test_returns=[], test_returns_normalized=[], update_steps=[], predicted_rewards=[], alphas=[], entropies=[], Q_values=[])
+  metrics = new_metrics()
   score = []
   if cfg.check_time_usage: start_time = time.time()
   B = cfg.training.batch_size
@@ -165,14 +230,7 @@ def train(cfg, file_prefix: str = '') -> float:
       return float(np.mean(normalised))
 
   if cfg.algorithm in ('DRIL', 'RED'):  # train.py:114-134: pretrain the "discriminator" on expert data, then fix its reward threshold / bandwidth
-    if pretraining_schedule(cfg) == 'plan' and cfg.imitation.pretraining.iterations > 0:
-      il.PretrainPlan(cfg.algorithm, discriminator, discriminator_optimiser, expert_memory, B, torch.Generator().manual_seed(cfg.seed)).run(cfg.imitation.pretraining.iterations)
-    else:
-      for batch in expert_batches(cfg, expert_memory, state_size, action_size, cfg.imitation.pretraining.iterations):
-        if cfg.algorithm == 'DRIL': il.behavioural_cloning_update(discriminator, batch, discriminator_optimiser)
-        else: il.target_estimation_update(discriminator, batch, discriminator_optimiser)
-    if cfg.algorithm == 'DRIL': discriminator.set_uncertainty_threshold(expert_memory['states'][:expert_memory.size], expert_memory['actions'][:expert_memory.size], cfg.imitation.quantile_cutoff)
-    else: discriminator.set_sigma(expert_memory['states'][:B], expert_memory['actions'][:B])
+    pretrain_reward_model(cfg, discriminator, discriminator_optimiser, expert_memory, state_size, action_size)
     if cfg.check_time_usage: metrics['pre_training_time'], start_time = time.time() - start_time, time.time()
     if cfg.imitation.mix_expert_data == 'prefill_memory': memory.transfer_transitions(expert_memory)
 
@@ -189,10 +247,7 @@ def train(cfg, file_prefix: str = '') -> float:
         relabelled = True
       except NotImplementedError as e:   # an atom set outside the one-launch coupling's sizes: the loop below
         print(f'[train] {e}; relabelling the expert memory row by row', file=sys.stderr)
-    for i in range(0 if relabelled else expert_memory.size):   # `+pretraining.schedule=per_function`: the reference's loop, a host round trip per row (A/B runs; the same bits)
-      tr = expert_memory[i]
-      expert_memory.rewards[i] = discriminator.compute_reward(tr['states'].unsqueeze(0), tr['actions'].unsqueeze(0))
-      if tr['terminals'] or tr['timeouts']: discriminator.reset()
+    if not relabelled: relabel_row_by_row(discriminator, expert_memory)
   if cfg.algorithm in ('PWIL', 'GMMIL') and cfg.imitation.mix_expert_data == 'prefill_memory':
     memory.transfer_transitions(expert_memory)
 
@@ -349,15 +404,7 @@ def train(cfg, file_prefix: str = '') -> float:
       episode_returns = evaluate_agent(actor, eval_env, cfg.evaluation.episodes)
       normalised = normalise(episode_returns)
       score.append(float(normalised.mean()))
-      for key, value in (('test_steps', step), ('test_returns', episode_returns), ('test_returns_normalized', list(normalised))): metrics[key].append(value)
-      lineplot(metrics['test_steps'], metrics['test_returns'], filename=f'{file_prefix}test_returns', title=f'{cfg.algorithm}: {cfg.env} Test Returns')
-      if len(metrics['train_returns']) > 0:
-        lineplot(metrics['train_steps'], metrics['train_returns'], filename=f'{file_prefix}train_returns', title=f'Training {cfg.algorithm}: {cfg.env} Train Returns')
-      if cfg.logging.interval > 0 and len(metrics['update_steps']) > 0:   # train.py:224-228
-        if cfg.algorithm != 'SAC': lineplot(metrics['update_steps'], metrics['predicted_rewards'], filename=f'{file_prefix}predicted_rewards', yaxis='Predicted Reward', title=f'{cfg.algorithm}: {cfg.env} Predicted Rewards')
-        lineplot(metrics['update_steps'], metrics['alphas'], filename=f'{file_prefix}sac_alpha', yaxis='Alpha', title=f'{cfg.algorithm}: {cfg.env} Alpha')
-        lineplot(metrics['update_steps'], metrics['entropies'], filename=f'{file_prefix}sac_entropy', yaxis='Entropy', title=f'{cfg.algorithm}: {cfg.env} Entropy')
-        lineplot(metrics['update_steps'], metrics['Q_values'], filename=f'{file_prefix}Q_values', yaxis='Q-value', title=f'{cfg.algorithm}: {cfg.env} Q-values')
+      record_evaluation(cfg, metrics, file_prefix, step, episode_returns, normalised)
     if world > 1 and step % cfg.evaluation.interval == 0 and not cfg.check_time_usage:
       # rank 0 has just spent seconds evaluating: align the hosts here, so that no BOUNDED device-side wait of the next update (the peer-window exchange, the hand-off on
       # the all-reduced discriminator step) has to span that gap
@@ -384,12 +431,7 @@ def train(cfg, file_prefix: str = '') -> float:
       dist.destroy_process_group()
       return float('nan')
   if cfg.check_time_usage: metrics['training_time'] = time.time() - start_time
-  if cfg.save_trajectories:   # train.py:231-234
-    _, trajectories = evaluate_agent(actor, eval_env, cfg.evaluation.episodes, return_trajectories=True, render=cfg.render)
-    torch.save(trajectories, f'{file_prefix}trajectories.pth')
-  torch.save(dict(actor=actor.state_dict(), critic=critic.state_dict(), log_alpha=log_alpha), f'{file_prefix}agent.pth')
-  if cfg.algorithm in ('DRIL', 'GAIL', 'RED'): torch.save(discriminator.state_dict(), f'{file_prefix}discriminator.pth')   # train.py:238
-  torch.save(metrics, f'{file_prefix}metrics.pth')
+  save_run(cfg, file_prefix, metrics, actor, critic, log_alpha, discriminator, eval_env)
   if world > 1:
     dist.destroy_process_group()
   return float(np.mean(score)) if score else float('nan')
@@ -410,24 +452,31 @@ def sweep_schedule(cfg) -> str:
 
 
 PWIL_POPULATION_KEY = '+sweep.pwil_population=true'   # the opt-in of PWIL sweeps (`+sweep.schedule` alone keeps them job after job)
-
-
-def pwil_population(cfg) -> bool:
-  return bool((cfg.get('sweep', {}) or {}).get('pwil_population', False))
-
-
 ADRIL_POPULATION_KEY = '+sweep.adril_population=true'   # the opt-in of AdRIL / SQIL sweeps (`+sweep.schedule` alone keeps them job after job)
-
-
-def adril_population(cfg) -> bool:
-  return bool((cfg.get('sweep', {}) or {}).get('adril_population', False))
-
-
 GAIL_MIXUP_POPULATION_KEY = '+sweep.gail_mixup_population=true'   # the opt-in of GAIL sweeps whose loss is Mixup (without it they run job after job, whatever +sweep.schedule says)
 
+# algorithm (Mixup: GAIL with that loss) -> (the key that opts its seed sweeps into a population, how that population trains): what sweep_fallback_reason appends while the
+# key is missing. Each runs as it always has without its key; PWIL's, AdRIL's and Mixup's are keys of their own, which +sweep.schedule does not replace.
+SWEEP_OPT_INS = {
+    'DRIL': (f'+sweep.schedule={"|".join(SWEEP_SCHEDULES)}', 'DRIL trains as one population (il_dril_reward_population, il_bc_step_population)'),
+    'PWIL': (PWIL_POPULATION_KEY, 'PWIL trains as one population (il_pwil_act_reward_population: one coupling launch per lockstep step)'),
+    'AdRIL': (ADRIL_POPULATION_KEY, 'AdRIL trains as one population (il_batch_mix_relabel_population: one relabel launch per update)'),
+    'Mixup': (GAIL_MIXUP_POPULATION_KEY, 'Mixup trains as one population (il_gail_mixup_step_population: every learner\'s coefficients under its own key and counter)'),
+}
 
-def gail_mixup_population(cfg) -> bool:
-  return bool((cfg.get('sweep', {}) or {}).get('gail_mixup_population', False))
+
+def sweep_opt_in(cfg, name: str) -> bool:
+  """`+sweep.<name>=true` was given."""
+  return bool((cfg.get('sweep', {}) or {}).get(name, False))
+
+
+def gail_mixup_population(cfg) -> bool:   # the name tests/test_sweep_gail_mixup_config_cpu.py asks by
+  return sweep_opt_in(cfg, 'gail_mixup_population')
+
+
+def _opt_in_clause(which: str) -> str:
+  key, how = SWEEP_OPT_INS[which]
+  return f'; {how} only when {key} is given'
 
 
 def pwil_atoms_upper_bound(cfg) -> tuple:
@@ -450,16 +499,10 @@ def sweep_fallback_reason(cfg):
   """None when a seed sweep of this configuration can train as one population (what il.BatchedPopulationPlan and il.PopulationActingWorker take); otherwise the reason
   its jobs run one after another through train()."""
   explicit = (cfg.get('sweep', {}) or {}).get('schedule') is not None
-  if cfg.algorithm not in ('SAC', 'GAIL', 'RED', 'GMMIL') and not (cfg.algorithm == 'DRIL' and explicit) and not (cfg.algorithm == 'PWIL' and pwil_population(cfg)) \
-      and not (cfg.algorithm == 'AdRIL' and adril_population(cfg)):
+  opted_in = {'DRIL': explicit, 'PWIL': sweep_opt_in(cfg, 'pwil_population'), 'AdRIL': sweep_opt_in(cfg, 'adril_population')}
+  if cfg.algorithm not in ('SAC', 'GAIL', 'RED', 'GMMIL') and not opted_in.get(cfg.algorithm, False):
     reason = f'algorithm={cfg.algorithm} has no population launches (SAC, GAIL and RED have), and GMMIL under an explicit +sweep.schedule'
-    if cfg.algorithm == 'DRIL':   # opt-in, as for GMMIL: a DRIL sweep without the key runs as it always has
-      reason += f'; DRIL trains as one population (il_dril_reward_population, il_bc_step_population) only when +sweep.schedule={"|".join(SWEEP_SCHEDULES)} is given'
-    if cfg.algorithm == 'PWIL':   # opt-in by a key of its own: a PWIL sweep without it, with or without +sweep.schedule, runs as it always has
-      reason += f'; PWIL trains as one population (il_pwil_act_reward_population: one coupling launch per lockstep step) only when {PWIL_POPULATION_KEY} is given'
-    if cfg.algorithm == 'AdRIL':   # opt-in by a key of its own, as for PWIL: an AdRIL / SQIL sweep without it, with or without +sweep.schedule, runs as it always has
-      reason += f'; AdRIL trains as one population (il_batch_mix_relabel_population: one relabel launch per update) only when {ADRIL_POPULATION_KEY} is given'
-    return reason
+    return reason + (_opt_in_clause(cfg.algorithm) if cfg.algorithm in opted_in else '')
   if cfg.algorithm == 'GMMIL' and (cfg.get('sweep', {}) or {}).get('schedule') is None:
     # opt-in: a GMMIL sweep without the key runs as it always has; with it, its first update is eager (every learner's bandwidths) and the rest are population launches
     return f'algorithm=GMMIL trains as one population (il_gmmil_reward_population) only when +sweep.schedule={"|".join(SWEEP_SCHEDULES)} is given'
@@ -501,9 +544,8 @@ def sweep_fallback_reason(cfg):
       return 'reward shaping / subtract_log_policy run their per-function entry points inside the plan'
     if cfg.imitation.loss_function == 'PUGAIL' and float(cfg.imitation.nonnegative_margin) != float('inf'):
       return 'a finite PUGAIL margin needs a value pass ahead of the gradients'
-    if cfg.imitation.loss_function == 'Mixup' and not gail_mixup_population(cfg):   # opt-in by a key of its own, at any mixup_alpha: a Mixup sweep without it runs as it always has
-      return ('imitation.loss_function=Mixup has no population discriminator step (BCE and PUGAIL with an infinite margin have)'
-              f'; Mixup trains as one population (il_gail_mixup_step_population: every learner\'s coefficients under its own key and counter) only when {GAIL_MIXUP_POPULATION_KEY} is given')
+    if cfg.imitation.loss_function == 'Mixup' and not sweep_opt_in(cfg, 'gail_mixup_population'):   # at any mixup_alpha
+      return 'imitation.loss_function=Mixup has no population discriminator step (BCE and PUGAIL with an infinite margin have)' + _opt_in_clause('Mixup')
   return None
 
 
@@ -541,10 +583,6 @@ def sweep_dir(cfg, stamp: str) -> str:
   return os.path.join('outputs', f'{cfg.algorithm}_{cfg.env}_sweeper', stamp)
 
 
-class _Learner:
-  """Everything one job of a seed sweep owns."""
-
-
 def train_sweep(cfgs, prefixes):
   """The loop of train() in lockstep over L learners that differ only in their seed: per lockstep step ONE population act launch, L host environment steps and ONE
   append launch (`+acting.schedule=fused`: one launch for both); on update steps ONE population update (il.BatchedPopulationPlan); on evaluation steps
@@ -577,70 +615,30 @@ def train_sweep(cfgs, prefixes):
     ln.normalise = lambda returns, lo=lo, hi=hi: (np.asarray(returns) - lo) / (hi - lo)
     ln.expert_memory = ln.env.get_dataset(trajectories=cfg.imitation.trajectories, subsample=cfg.imitation.subsample, device=dev)
     S, A = ln.env.observation_space.shape[0], ln.env.action_space.shape[0]
-    ln.actor, ln.critic, ln.log_alpha = il.SoftActor(S, A, cfg.reinforcement.actor), il.TwinCritic(S, A, cfg.reinforcement.critic), torch.zeros(1, device=dev)
-    ln.target_critic, entropy_target = il.create_target_network(ln.critic), cfg.reinforcement.target_temperature * A
-    ln.actor_optimiser = il.AdamW(ln.actor, lr=cfg.training.learning_rate, weight_decay=cfg.training.weight_decay)
-    ln.critic_optimiser = il.AdamW(ln.critic, lr=cfg.training.learning_rate, weight_decay=cfg.training.weight_decay)
-    ln.temperature_optimiser = il.Adam(ln.log_alpha, lr=cfg.training.learning_rate)
-    ln.memory = il.ReplayMemory(cfg.memory.size, S, A, cfg.imitation.absorbing)
+    build_agent(ln, cfg, S, A, dev)
     ln.memory.index_rng = ln.expert_memory.index_rng = ln.stream
-    ln.discriminator = ln.discriminator_optimiser = None
-    if cfg.algorithm == 'GAIL':
-      ln.discriminator = il.GAILDiscriminator(S, A, cfg.imitation, cfg.reinforcement.discount)
-      ln.discriminator_optimiser = il.AdamW(ln.discriminator, lr=cfg.imitation.learning_rate, weight_decay=cfg.imitation.weight_decay)
-    elif cfg.algorithm == 'RED':
-      ln.discriminator = il.REDDiscriminator(S, A, cfg.imitation)
-      ln.discriminator_optimiser = il.AdamW(ln.discriminator, lr=cfg.imitation.learning_rate, weight_decay=cfg.imitation.weight_decay)
-    elif cfg.algorithm == 'GMMIL':   # no parameters and no optimiser: its state is the two bandwidths the learner's first batch fixes
-      ln.discriminator = il.GMMILDiscriminator(S, A, cfg.imitation)
-    elif cfg.algorithm == 'DRIL':   # the dropout policy ensemble (train.py:73)
-      ln.discriminator = il.DropoutSoftActor(S, A, cfg.imitation.discriminator)
-      ln.discriminator_optimiser = il.AdamW(ln.discriminator, lr=cfg.imitation.learning_rate, weight_decay=cfg.imitation.weight_decay)
-    elif cfg.algorithm == 'PWIL':   # this learner's own atoms: its expert data was subsampled under its seed
-      ln.discriminator = il.PWILDiscriminator(S, A, cfg.imitation, ln.expert_memory, ln.env.max_episode_steps)
-    elif cfg.algorithm == 'AdRIL':   # no parameters: its state is the balanced alternation (update_freq=0: SQIL)
-      ln.discriminator = il.RewardRelabeller(cfg.imitation.update_freq, cfg.imitation.balanced)
-    ln.metrics = dict(train_steps=[], train_returns=[], test_steps=[], test_returns=[], test_returns_normalized=[], update_steps=[], predicted_rewards=[], alphas=[], entropies=[], Q_values=[])
-    ln.score = []
+    ln.discriminator, ln.discriminator_optimiser = build_reward_model(cfg, S, A, ln.expert_memory, ln.env.max_episode_steps)
+    ln.metrics, ln.score = new_metrics(), []
     start_time += time.time() - built
     began = time.time()
     if cfg.bc_pretraining.iterations > 0:
       pretrain_bc(cfg, ln.actor, ln.expert_memory, S, A)   # one PretrainPlan per learner
-    if cfg.algorithm == 'RED':   # train.py:114-134 in train()'s order, under this learner's seeds: predictor pretraining, its own bandwidth, the prefill
-      if pretraining_schedule(cfg) == 'plan' and cfg.imitation.pretraining.iterations > 0:
-        il.PretrainPlan('RED', ln.discriminator, ln.discriminator_optimiser, ln.expert_memory, B, torch.Generator().manual_seed(cfg.seed)).run(cfg.imitation.pretraining.iterations)
-      else:
-        for batch in expert_batches(cfg, ln.expert_memory, S, A, cfg.imitation.pretraining.iterations):
-          il.target_estimation_update(ln.discriminator, batch, ln.discriminator_optimiser)
-      ln.discriminator.set_sigma(ln.expert_memory['states'][:B], ln.expert_memory['actions'][:B])
+    if cfg.algorithm in ('DRIL', 'RED'):   # train.py:114-134 in train()'s order, under this learner's seeds: pretraining, its own threshold / bandwidth, the prefill
+      pretrain_reward_model(cfg, ln.discriminator, ln.discriminator_optimiser, ln.expert_memory, S, A)
       if cfg.check_time_usage:   # what train() reports: this learner's pretraining on its own, and a training_time that starts behind it
         ln.metrics['pre_training_time'] = time.time() - began
         start_time += ln.metrics['pre_training_time']
       if cfg.imitation.mix_expert_data == 'prefill_memory': ln.memory.transfer_transitions(ln.expert_memory)
-      ln.discriminator.eval()   # train.py:147, in front of the plan: from here on the predictor's dropout is off
-    if cfg.algorithm == 'DRIL':   # train.py:114-134 in train()'s order, while this learner's seed is the process seed (the ensemble's descriptors read their Philox key from it): ensemble pretraining, its own threshold, the prefill
-      if pretraining_schedule(cfg) == 'plan' and cfg.imitation.pretraining.iterations > 0:
-        il.PretrainPlan('DRIL', ln.discriminator, ln.discriminator_optimiser, ln.expert_memory, B, torch.Generator().manual_seed(cfg.seed)).run(cfg.imitation.pretraining.iterations)
-      else:
-        for batch in expert_batches(cfg, ln.expert_memory, S, A, cfg.imitation.pretraining.iterations):
-          il.behavioural_cloning_update(ln.discriminator, batch, ln.discriminator_optimiser)
-      ln.discriminator.set_uncertainty_threshold(ln.expert_memory['states'][:ln.expert_memory.size], ln.expert_memory['actions'][:ln.expert_memory.size], cfg.imitation.quantile_cutoff)
-      if cfg.check_time_usage:
-        ln.metrics['pre_training_time'] = time.time() - began
-        start_time += ln.metrics['pre_training_time']
-      if cfg.imitation.mix_expert_data == 'prefill_memory': ln.memory.transfer_transitions(ln.expert_memory)
+      if cfg.algorithm == 'RED': ln.discriminator.eval()   # train.py:147, in front of the plan: from here on the predictor's dropout is off
     if cfg.algorithm == 'GMMIL' and cfg.imitation.mix_expert_data == 'prefill_memory': ln.memory.transfer_transitions(ln.expert_memory)   # train.py:192, once, in front of the loop
     if cfg.algorithm == 'PWIL' and cfg.imitation.mix_expert_data == 'prefill_memory':   # train.py:135-141, 192 as train() runs them: the relabel on the device (or row by row), then the prefill
       if pretraining_schedule(cfg) == 'plan':
         ln.discriminator.relabel_memory(ln.expert_memory)   # (sweep_fallback_reason has bounded the atoms: inside the one-launch coupling)
       else:
-        for r in range(ln.expert_memory.size):
-          tr = ln.expert_memory[r]
-          ln.expert_memory.rewards[r] = ln.discriminator.compute_reward(tr['states'].unsqueeze(0), tr['actions'].unsqueeze(0))
-          if tr['terminals'] or tr['timeouts']: ln.discriminator.reset()
+        relabel_row_by_row(ln.discriminator, ln.expert_memory)
       ln.memory.transfer_transitions(ln.expert_memory)
     ln.plan = il.UpdatePlan(cfg.algorithm, ln.actor, ln.critic, ln.log_alpha, ln.target_critic, ln.memory, ln.actor_optimiser, ln.critic_optimiser, ln.temperature_optimiser, B,
-                            cfg.reinforcement.discount, entropy_target, cfg.reinforcement.polyak_factor, expert_memory=ln.expert_memory, discriminator=ln.discriminator,
+                            cfg.reinforcement.discount, ln.entropy_target, cfg.reinforcement.polyak_factor, expert_memory=ln.expert_memory, discriminator=ln.discriminator,
                             discriminator_optimiser=ln.discriminator_optimiser, imitation_cfg=cfg.imitation if cfg.algorithm == 'GAIL' else None, overlap=False, learner_id=i,
                             bc_aux=bool(cfg.imitation.bc_aux_loss),   # (sweep_fallback_reason: set for DRIL learners only)
                             noise_seed_offset=0 if cfg.algorithm == 'PWIL' or mixup_sweep else None)   # PWIL and Mixup jobs train as train() trains them, bit for bit: its Philox key for this learner's seed
@@ -721,17 +719,9 @@ def train_sweep(cfgs, prefixes):
       else:
         returns = [evaluate_agent(ln.actor, ln.eval_env, cfg0.evaluation.episodes) for ln in learners]
       for ln, episode_returns in zip(learners, returns):
-        m, cfg, normalised = ln.metrics, ln.cfg, ln.normalise(episode_returns)
+        normalised = ln.normalise(episode_returns)
         ln.score.append(float(normalised.mean()))
-        for key, value in (('test_steps', step), ('test_returns', episode_returns), ('test_returns_normalized', list(normalised))): m[key].append(value)
-        lineplot(m['test_steps'], m['test_returns'], filename=f'{ln.prefix}test_returns', title=f'{cfg.algorithm}: {cfg.env} Test Returns')
-        if len(m['train_returns']) > 0:
-          lineplot(m['train_steps'], m['train_returns'], filename=f'{ln.prefix}train_returns', title=f'Training {cfg.algorithm}: {cfg.env} Train Returns')
-        if cfg.logging.interval > 0 and len(m['update_steps']) > 0:   # train.py:224-228
-          if cfg.algorithm != 'SAC': lineplot(m['update_steps'], m['predicted_rewards'], filename=f'{ln.prefix}predicted_rewards', yaxis='Predicted Reward', title=f'{cfg.algorithm}: {cfg.env} Predicted Rewards')
-          lineplot(m['update_steps'], m['alphas'], filename=f'{ln.prefix}sac_alpha', yaxis='Alpha', title=f'{cfg.algorithm}: {cfg.env} Alpha')
-          lineplot(m['update_steps'], m['entropies'], filename=f'{ln.prefix}sac_entropy', yaxis='Entropy', title=f'{cfg.algorithm}: {cfg.env} Entropy')
-          lineplot(m['update_steps'], m['Q_values'], filename=f'{ln.prefix}Q_values', yaxis='Q-value', title=f'{cfg.algorithm}: {cfg.env} Q-values')
+        record_evaluation(ln.cfg, ln.metrics, ln.prefix, step, episode_returns, normalised)
 
   for p in plans:   # never save a learner whose last updates ran on expired device-side waits
     p.join()
@@ -742,12 +732,7 @@ def train_sweep(cfgs, prefixes):
   for ln in learners:
     cfg, m = ln.cfg, ln.metrics
     if cfg.check_time_usage: m['training_time'] = time.time() - start_time
-    if cfg.save_trajectories:   # train.py:231-234
-      _, trajectories = evaluate_agent(ln.actor, ln.eval_env, cfg.evaluation.episodes, return_trajectories=True, render=cfg.render)
-      torch.save(trajectories, f'{ln.prefix}trajectories.pth')
-    torch.save(dict(actor=ln.actor.state_dict(), critic=ln.critic.state_dict(), log_alpha=ln.log_alpha), f'{ln.prefix}agent.pth')
-    if cfg.algorithm in ('DRIL', 'GAIL', 'RED'): torch.save(ln.discriminator.state_dict(), f'{ln.prefix}discriminator.pth')   # train.py:238
-    torch.save(m, f'{ln.prefix}metrics.pth')
+    save_run(cfg, ln.prefix, m, ln.actor, ln.critic, ln.log_alpha, ln.discriminator, ln.eval_env)
     scores.append(float(np.mean(ln.score)) if ln.score else float('nan'))
   return scores
 
