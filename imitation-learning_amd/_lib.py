@@ -102,6 +102,10 @@ class ActLearner(C.Structure):   # il_act_learner: one learner of il_act_step_po
   _fields_ = [('actor', C.c_void_p), ('mailbox', C.c_void_p), ('carry', C.c_void_p), ('ring', C.c_void_p), ('ring_state', C.c_void_p), ('noise_seed', C.c_uint64)]
 
 
+class ActDims(C.Structure):   # il_act_dims: learner l's widths for il_act_step_population_mixed (an array beside the il_act_learner array; 16 bytes)
+  _fields_ = [('state_dim', C.c_int32), ('action_dim', C.c_int32), ('ring_row_floats', C.c_int32), ('reserved', C.c_int32)]
+
+
 class GmmilLearner(C.Structure):   # il_gmmil_learner: one learner of il_gmmil_reward_population (a device array of these)
   _fields_ = [('policy', Batch), ('expert', Batch), ('gamma_1', C.c_float), ('gamma_2', C.c_float), ('workspace', C.c_void_p), ('out_rewards', C.c_void_p)]
 
@@ -174,6 +178,9 @@ _SIGNATURES = {
     'il_replay_draw_resident': (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     'il_replay_sample_population': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P]),
     'il_sac_update_population': (C.c_int, [_P, _P, C.c_int32, C.POINTER(Sac), C.c_uint32, _P]),
+    'il_sac_update_population_mixed': (C.c_int, [_P, _P, C.c_int32, _P, C.c_uint32, _P]),   # (descs_dev, batches_dev, n_learners, descs_host, flags, stream)
+    'il_gail_step_population_mixed': (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P]),   # (..., n_learners, descs_host, stream)
+    'il_act_step_population_mixed': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P]),   # (learners_dev, dims_dev, dims_host, n_learners, hidden, stream)
     'il_gail_step_population': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(Disc), _P]),
     'il_gail_mixup_step_population': (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(Disc), _P, _P, C.c_float, _P]),   # (..., extras_dev, extras_host, mixup_alpha, stream)
     'il_adam_step': (C.c_int, [_P, _P, C.POINTER(Adam), C.c_int64, C.c_uint32, _P]),

@@ -312,15 +312,40 @@ class _MailboxBlock:
     return self.words
 
   def wait(self, what: str, timeout_s: float = 10.0):
-    echo, words, spins, t0 = self.echo, self.words, 0, 0.0
-    while not np.array_equal(echo, words):
+    words, spins, t0 = self.words, 0, 0.0
+    while not np.array_equal(self.echo, words):   # (self.echo: a view of the echo column here, a fresh gather of the per-learner slots in _MixedMailboxBlock)
       spins += 1
       if spins == 1:
         t0 = time.perf_counter()
       elif spins & 0xFFF == 0 and time.perf_counter() - t0 > timeout_s:
         torch.cuda.synchronize()  # surfaces an asynchronous launch failure, if that is what happened
+        echo = self.echo
         missing = [l for l in range(self.L) if echo[l] != words[l]]
         raise RuntimeError(f'{what}: no echo from the device after {timeout_s:.0f} s for learner(s) {missing} (commit words {words[missing].tolist()}, mailboxes hold {echo[missing].tolist()})')
+
+
+class _MixedMailboxBlock(_MailboxBlock):
+  """L mailboxes of learners with different (S, A) as one pinned [L, widest mailbox] block: row l starts learner l's mailbox, laid out inside as
+  il_act_mailbox_floats(S_l, A_l) lays it out, so the observation, action and echo slots sit at per-learner offsets (`o_obs`, `o_act`, `o_echo`: arrays)."""
+
+  def __init__(self, L: int, Ss, As):
+    assert len(Ss) == L and len(As) == L
+    n = max(int(_lib.lib().il_act_mailbox_floats(S, A)) for S, A in zip(Ss, As))
+    self.tensor = torch.zeros(L, n, dtype=torch.float32, pin_memory=True)
+    self.host = self.tensor.numpy()
+    self.bits = self.host.view(np.uint32)
+    Sp, Ap = (np.asarray(Ss) + 3) & ~3, (np.asarray(As) + 3) & ~3
+    self.L, self.S, self.A, self.floats = L, list(Ss), list(As), n
+    self.o_next, self.o_obs, self.o_act = _HEADER, _HEADER + Sp, _HEADER + 2 * Sp
+    self.o_echo = self.o_act + Ap
+    assert int(self.o_echo.max()) < n
+    self._ar = np.arange(L)
+    self.host[self._ar, self.o_echo] = -1.0
+    self.words = None
+
+  @property
+  def echo(self) -> np.ndarray:
+    return self.host[self._ar, self.o_echo]   # a fresh read of every learner's echo slot
 
 
 def _rows(xs, rows, width: int) -> np.ndarray:
@@ -328,8 +353,9 @@ def _rows(xs, rows, width: int) -> np.ndarray:
 
 
 class PopulationActingWorker:
-  """L environment workers of one shape - L `SoftActor`s feeding L `ReplayMemory`s - whose device work per lockstep environment step is ONE launch
-  (`il_act_step_population`: workgroup l = learner l's `il_act_step`). `act` / `append` / `step` are `ActingWorker`'s exact and fused schedules over lists (entry l belongs to
+  """L environment workers - L `SoftActor`s of one hidden size feeding L `ReplayMemory`s - whose device work per lockstep environment step is ONE launch
+  (`il_act_step_population`: workgroup l = learner l's `il_act_step`; learners of different state / action widths: `il_act_step_population_mixed`, mailboxes and carries
+  laid out per learner, `act` / `step` / `act_eval` then return [L, widest A] with learner l's `widths[l][1]` components in row l and zeros behind them). `act` / `append` / `step` are `ActingWorker`'s exact and fused schedules over lists (entry l belongs to
   learner l); a `None` entry makes that learner idle in the launch. Every learner's `actor._act_calls`, `memory.idx / full / num_trajectories`, ring and cursor end up
   where its own `ActingWorker(actor, memory, noise_seed=noise_seeds[l])` would have left them. Fused actor shapes only (depth 2, ReLU, hidden 64..256 in multiples of 64);
   no mirror / overlap schedule. `reward_models`: None, or one PWILDiscriminator per learner (each on its own atoms: the learners of a sweep subsample their expert data
@@ -353,15 +379,35 @@ class PopulationActingWorker:
       raise NotImplementedError('PopulationActingWorker: actor shapes outside depth 2 / ReLU / hidden 64..256 in multiples of 64 / action_size <= 8 have no population launch (one ActingWorker per learner)')
     for a, m in zip(actors, memories):
       assert _lib.on_device(a.flat) and _lib.on_device(m.ring), 'PopulationActingWorker needs the actors and the rings on the GPU (there is no CPU path)'
-      assert (a.state_size, a.action_size, a.hidden) == (a0.state_size, a0.action_size, a0.hidden) and (m.state_size, m.action_size) == (a0.state_size, a0.action_size), 'PopulationActingWorker: one shape for all learners'
+      assert (a.state_size, a.action_size) == (m.state_size, m.action_size), f'PopulationActingWorker: an actor of widths {(a.state_size, a.action_size)} feeds a memory of widths {(m.state_size, m.action_size)}'
+      assert a.hidden == a0.hidden, f'PopulationActingWorker: one hidden size for all learners (got {a0.hidden} and {a.hidden})'
       assert m.ring.device == m0.ring.device and a.flat.device == a0.flat.device
     self.actors, self.memories, self.L = actors, memories, L
     self.S, self.A, self.H = m0.state_size, m0.action_size, a0.hidden
     self.device = m0.ring.device
     self._seeds = noise_seeds
-    self.carry = torch.zeros(L, self.S + self.A + 4, dtype=torch.float32, device=self.device)
-    self.eval_carry = torch.zeros(L, self.S + self.A + 4, dtype=torch.float32, device=self.device)   # evaluation acts between two fused steps: never the carry of a transition in flight
-    self._act_box, self._append_box, self._eval_box = _MailboxBlock(L, self.S, self.A), _MailboxBlock(L, self.S, self.A), _MailboxBlock(L, self.S, self.A)
+    # learners of different (S, A) - the four environments of train_all.py - step through il_act_step_population_mixed: mailboxes and carries laid out per learner
+    self.widths = [(int(m.state_size), int(m.action_size)) for m in memories]
+    self.mixed = len(set(self.widths)) > 1
+    self._dims = self._dims_host = None
+    if self.mixed:
+      if reward_models is not None:
+        raise NotImplementedError('PopulationActingWorker(reward_models=...): learners of different state / action widths have no population coupling launch (one shape for all learners)')
+      T = max(256, 4 * self.H)   # il_act_step's workgroup: the limits below are ITS limits, for each learner's own widths
+      for l, (S, A) in enumerate(self.widths):
+        row = int(_lib.lib().il_ring_row_floats(S, A))
+        assert 2 * A <= 16 and row <= T and 64 + S <= T, f'PopulationActingWorker: learner {l} (state {S}, action {A}) is outside il_act_step\'s limits at hidden {self.H} (2A <= 16, ring row {row} and 64 + S within {T} threads)'
+        assert memories[l].row == row, f'PopulationActingWorker: learner {l}: the memory\'s ring row ({memories[l].row} floats) is not il_ring_row_floats({S}, {A}) = {row}'
+      from .training import _device_array
+      dims = [_lib.ActDims(S, A, int(_lib.lib().il_ring_row_floats(S, A)), 0) for S, A in self.widths]
+      self._dims_host = (_lib.ActDims * L)(*dims)   # the entry point sizes the launch, and decides its refusals, on this copy
+      self._dims = _device_array(dims, self.device)
+      self.S, self.A = [w[0] for w in self.widths], max(w[1] for w in self.widths)   # per-learner state widths; the action tensor is [L, widest A]
+    cw = max(S + A for S, A in self.widths) + 4
+    self.carry = torch.zeros(L, cw, dtype=torch.float32, device=self.device)
+    self.eval_carry = torch.zeros(L, cw, dtype=torch.float32, device=self.device)   # evaluation acts between two fused steps: never the carry of a transition in flight
+    new_box = (lambda: _MixedMailboxBlock(L, [w[0] for w in self.widths], [w[1] for w in self.widths])) if self.mixed else (lambda: _MailboxBlock(L, self.S, self.A))
+    self._act_box, self._append_box, self._eval_box = new_box(), new_box(), new_box()
     self._seq = 0   # one sequence for the act and the append mailboxes: the device de-duplicates appends by commit word
     self._eval_seq = 0   # the evaluation mailboxes never post PENDING: a sequence of their own, so no number of evaluation launches between two appends can bring a learner's consumed word round again
     self._descs = {id(box): self._descriptors(box, carry) for box, carry in ((self._act_box, self.carry), (self._append_box, self.carry), (self._eval_box, self.eval_carry))}
@@ -398,7 +444,10 @@ class PopulationActingWorker:
     if appends and self.reward_models is not None:
       rc = _lib.lib().il_pwil_act_reward_population(_lib.ptr(self._pwil_descs[id(box)]), self.L, C.byref(self._pwil_shape), torch.cuda.current_stream().cuda_stream)
       if rc: _lib.check(rc)
-    rc = _lib.lib().il_act_step_population(_lib.ptr(self._descs[id(box)]), self.L, self.S, self.A, self.H, torch.cuda.current_stream().cuda_stream)
+    if self.mixed:
+      rc = _lib.lib().il_act_step_population_mixed(_lib.ptr(self._descs[id(box)]), _lib.ptr(self._dims), C.cast(self._dims_host, C.c_void_p), self.L, self.H, torch.cuda.current_stream().cuda_stream)
+    else:
+      rc = _lib.lib().il_act_step_population(_lib.ptr(self._descs[id(box)]), self.L, self.S, self.A, self.H, torch.cuda.current_stream().cuda_stream)
     if rc: _lib.check(rc)
 
   def _next_seq(self) -> int:
@@ -413,7 +462,10 @@ class PopulationActingWorker:
     """Observation and Philox offset of every learner that acts (flags without NO_ACTION); counts the act in its actor, as SoftActor._act does."""
     rows = [l for l in self._all if not flags[l] & NO_ACTION]
     if rows:
-      box.host[rows, box.o_obs:box.o_obs + self.S] = _rows(obs, rows, self.S)
+      if self.mixed:
+        for l in rows: box.host[l, box.o_obs[l]:box.o_obs[l] + self.S[l]] = _row(obs[l])[:self.S[l]]
+      else:
+        box.host[rows, box.o_obs:box.o_obs + self.S] = _rows(obs, rows, self.S)
       calls = []
       for l in rows:
         a = self.actors[l]
@@ -424,7 +476,10 @@ class PopulationActingWorker:
   def _post_transition(self, box: _MailboxBlock, rows, step, next_obs, reward, terminal, timeout):
     if rows:
       box.host[rows, 2:6] = np.array([(float(reward[l]), float(bool(terminal[l])), float(bool(timeout[l])), float(step[l] if np.ndim(step) else step)) for l in rows], dtype=np.float32)
-      box.host[rows, box.o_next:box.o_next + self.S] = _rows(next_obs, rows, self.S)
+      if self.mixed:
+        for l in rows: box.host[l, box.o_next:box.o_next + self.S[l]] = _row(next_obs[l])[:self.S[l]]
+      else:
+        box.host[rows, box.o_next:box.o_next + self.S] = _rows(next_obs, rows, self.S)
 
   def _mirror_appends(self, rows, terminal, timeout, wrap):
     for l in rows:
@@ -434,6 +489,10 @@ class PopulationActingWorker:
 
   def _collect(self, box: _MailboxBlock) -> torch.Tensor:
     box.wait('il_act_step_population')
+    if self.mixed:   # [L, widest A]: row l holds learner l's A_l components, zeros behind them
+      out = np.zeros((self.L, self.A), dtype=np.float32)
+      for l, (_, A) in enumerate(self.widths): out[l, :A] = box.host[l, box.o_act[l]:box.o_act[l] + A]
+      return torch.from_numpy(out)
     return torch.from_numpy(box.host[:, box.o_act:box.o_act + self.A].copy())
 
   def _transition_flags(self, next_obs, terminal, timeout):

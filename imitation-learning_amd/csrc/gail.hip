@@ -760,9 +760,11 @@ extern "C" int il_gail_disc_step_draw_peer(const il_disc* d, const il_batch* pol
 
 // population axis: discriminator step + reward relabel of n_learners independent discriminators (same shapes) in three launches. xL: il_gail_mixup_step_population's
 // per-learner optional inputs (null otherwise).
+// D_widest (il_gail_step_population_mixed; 0 = the learners share d's widths): the widest learner's input width, which sizes the LDS of the tile launches and the grid of the
+// reduce launch; the layouts inside the workgroups are each learner's own.
 static int gail_population_launches(const il_disc* descs_dev, const il_batch* policy_dev, const il_batch* expert_dev, float* const* rewards_out_dev, int L, const il_disc* d,
-                                    const il_gail_extra* xL, hipStream_t st, const char* who) {
-  const int D = d->state_dim + (d->state_only ? 0 : d->action_dim), nt = ceil_div(d->batch, IL_TILE_R);
+                                    const il_gail_extra* xL, hipStream_t st, const char* who, int D_widest = 0) {
+  const int D = D_widest > 0 ? D_widest : d->state_dim + (d->state_only ? 0 : d->action_dim), nt = ceil_div(d->batch, IL_TILE_R);
   static const int compact = [] { const char* e = getenv("IL_POP_DISC_LDS"); return e && e[0] == '0' ? 0 : 1; }();   // IL_POP_DISC_LDS=0: one workgroup per CU, as in round 3 (A/B)
   const size_t need = disc_lds_floats(D, d->hidden) * sizeof(float);
   const size_t lds = compact || need > (size_t)96 * 1024 ? need : (size_t)96 * 1024, lds_r = compact ? disc_reward_lds_floats(D, d->hidden) * sizeof(float) : lds;
@@ -785,6 +787,26 @@ extern "C" int il_gail_step_population(const il_disc* descs_dev, const il_batch*
   IL_CHECK_ARG(descs_dev && policy_dev && expert_dev && rewards_out_dev && n_learners >= 1 && n_learners <= 65535, "il_gail_step_population: bad arguments");
   IL_CHECK_ARG(shape_host->loss_function != IL_LOSS_MIXUP, "il_gail_step_population: loss_function Mixup is not available on the population path");
   return gail_population_launches(descs_dev, policy_dev, expert_dev, rewards_out_dev, n_learners, shape_host, nullptr, (hipStream_t)stream_, "il_gail_step_population");
+}
+extern "C" int il_gail_step_population_mixed(const il_disc* descs_dev, const il_batch* policy_dev, const il_batch* expert_dev, float* const* rewards_out_dev, int32_t n_learners,
+                                             const il_disc* descs_host, il_stream_t stream_) {
+  IL_CHECK_ARG(descs_dev && policy_dev && expert_dev && rewards_out_dev && descs_host, "il_gail_step_population_mixed: null descriptor / batch / reward array");
+  IL_CHECK_ARG(n_learners >= 1 && n_learners <= 65535, "il_gail_step_population_mixed: n_learners=%d must be in 1..65535 (the learner is a grid dimension)", n_learners);
+  const il_disc& f = descs_host[0];
+  IL_CHECK_ARG(f.loss_function != IL_LOSS_MIXUP, "il_gail_step_population_mixed: loss_function Mixup has no mixed-width population form");
+  IL_CHECK_ARG(!f.pu_clamped, "il_gail_step_population_mixed: pu_clamped (a finite PUGAIL margin's value pass) has no population form");
+  int D_widest = 0;
+  for (int l = 0; l < n_learners; ++l) {
+    const il_disc& e = descs_host[l];
+    IL_CHECK_ARG(e.hidden == f.hidden && e.batch == f.batch, "il_gail_step_population_mixed: learner %d has hidden=%d batch=%d, learner 0 has hidden=%d batch=%d", l, e.hidden, e.batch, f.hidden,
+                 f.batch);
+    IL_CHECK_ARG(e.spectral_norm == f.spectral_norm && e.state_only == f.state_only && e.reward_function == f.reward_function && e.loss_function == f.loss_function &&
+                     e.pu_clamped == f.pu_clamped && (e.grad_penalty > 0.f) == (f.grad_penalty > 0.f),
+                 "il_gail_step_population_mixed: learner %d differs from learner 0 in its discriminator or loss settings (only state_dim / action_dim may differ)", l);
+    if (int rc = check_disc(&e)) return rc;   // (behind the shared settings: the workspace is sized by them)
+    D_widest = std::max(D_widest, e.state_dim + (e.state_only ? 0 : e.action_dim));
+  }
+  return gail_population_launches(descs_dev, policy_dev, expert_dev, rewards_out_dev, n_learners, descs_host, nullptr, (hipStream_t)stream_, "il_gail_step_population_mixed", D_widest);
 }
 // The same step for discriminators whose loss is Mixup (include/il_hip.h): for mixup_alpha != 1 one launch draws every learner's coefficients in front of the three.
 extern "C" int il_gail_mixup_step_population(const il_disc* descs_dev, const il_batch* policy_dev, const il_batch* expert_dev, float* const* rewards_out_dev, int32_t n_learners,

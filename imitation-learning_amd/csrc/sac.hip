@@ -2692,8 +2692,9 @@ extern "C" int il_sac_update_gather_peer(const il_sac* d, const il_batch* rows, 
 // gridDim.y (z for k_repack) selects the learner. Kernels are latency-bound at B = 256 (16-64 workgroups): a population fills the chip.
 // ---------------------------------------------------------------------------------------------
 __host__ __device__ static inline bool pop_small_blocks(int H, int B) { return H % DWS == 0 && B % DWS_ROWS == 0; }
+#define IL_POP_TAIL_BLOCKS 33   // tail workgroups per learner of the population's actor optimiser launch (log alpha and the counter bump in the first, the target step over all)
 // workgroups per learner of a population dW launch behind its nb64 dw_block64 workgroups (without the tail)
-static inline int pop_dw_small_grid(int IN, int H, int OUT, int nets, int B, bool b64) {
+__host__ __device__ static inline int pop_dw_small_grid(int IN, int H, int OUT, int nets, int B, bool b64) {
   if (b64 && pop_small_blocks(H, B)) return (dw_block_jobs(IN, H, OUT) - (H / DWS) * (H / DWS)) * nets + (H / 16 * nets + 3) / 4;
   return dw_blocks(IN, H, OUT, nets, b64);
 }
@@ -2765,15 +2766,76 @@ __global__ __launch_bounds__(256) IL_POP_DW_ATTR void k_dw_adam_pop(const il_sac
   a.n_dw_blocks = dw_blocks(a.in_dim, a.hidden, a.out_dim, a.n_nets, 0); a.n_big_blocks = 0; a.jobs_per_block = 4;
   dw_adam_body<4>(a, bx, (int)gridDim.x);
 }
+// k_dw_adam_pop for learners that differ in state_dim / action_dim (il_sac_update_population_mixed): the grid is the widest learner's, so `own` - this learner's workgroup
+// count, worked out from ITS descriptor - stands wherever k_dw_adam_pop reads gridDim.x, and workgroups beyond it return before they touch anything (in the critic launch,
+// which has no tail, they would otherwise run the end-of-update tail: log alpha, the counter bump, the target step). A kernel of its own, with its own copy of the
+// decode: k_dw_adam_pop above is textually what it was, and so is its code object (profiles/mixed_population_resources.txt).
+__global__ __launch_bounds__(256) IL_POP_DW_ATTR void k_dw_adam_pop_mixed(const il_sac* __restrict__ dL, const il_batch* __restrict__ bL, int kind, uint32_t flags, int nb64) {
+  __shared__ __attribute__((aligned(16))) float smem[2 * DWB * DWB_LD];
+  int bx = blockIdx.x, by = blockIdx.y;
+  pop_ids(bx, by);   // a learner's blocks on one XCD: the four blocks that share a [64 features][B] operand panel find it in that L2
+  il_sac d = dL[by]; il_batch b = bL[by];
+  globalize(d); globalize(b);
+  DwArgs a = kind ? actor_dw_args(&d, &b, flags) : critic_dw_args(&d, flags);
+  const int own = nb64 + pop_dw_small_grid(a.in_dim, a.hidden, a.out_dim, a.n_nets, a.batch, nb64 > 0) + (kind ? IL_POP_TAIL_BLOCKS : 0);   // this learner's workgroups
+  if (bx >= own) return;   // a narrower learner's surplus under the widest learner's grid: nothing is touched
+  IL_TL(kind ? 11 : 10, 0);
+  IL_TLV(kind ? 11 : 10, 2, (unsigned long long)(unsigned)bx | ((unsigned long long)(unsigned)by << 32));   // which job of which learner (profiles/tools/pop_dw_timeline.py)
+  IL_TLV(kind ? 11 : 10, 3, ((unsigned long long)il_st_xcc() << 16) | ((il_st_hwid() >> 8) & 0xffu));   // and where it runs
+  IL_TLC(kind ? 11 : 10, 4);   // shader-clock counter at the start (slot 5: at the end) - the clock this workgroup ran at = delta / the 100 MHz counter's delta
+  if (nb64 > 0) {
+    const int H = a.hidden, nbh = H / DWB, per_net = nbh * nbh;
+    if (bx < nb64) {
+      const int net = bx / per_net, blk = bx - net * per_net;
+      adam_consts ac = {};
+      if (!a.grads_only) ac = load_adam_consts(a.opt);
+      const int64_t oW2 = (int64_t)net * a.net_stride + (int64_t)H * a.in_dim + H;
+      dw_block64(a, ac, a.dz2 + net * a.h_net_stride, a.h1 + net * a.h_net_stride, H, (blk / nbh) * DWB, (blk % nbh) * DWB, oW2,
+                 a.pk_f ? a.pk_f + (size_t)net * H * H : nullptr, a.pk_b ? a.pk_b + (size_t)net * H * H : nullptr, smem, dL + by);
+      IL_TLC(kind ? 11 : 10, 5); IL_TL_END(kind ? 11 : 10);
+      return;
+    }
+    if (pop_small_blocks(a.hidden, a.batch)) {
+      // (round 3) layers 1 and 3 with their biases as 32 x 32 LDS block jobs (dw_block32: whole-line staging instead of the wave-per-tile jobs' half-line gathers, which were
+      // 72 % of this launch's line requests), bias 2 as wave jobs (dw_block64 does not fold it), then the tail. Grid: pop_dw_grid().
+      const int nb32 = H / DWS, small = dw_block_jobs(a.in_dim, H, a.out_dim) - nb32 * nb32, sb = bx - nb64;
+      if (sb < small * a.n_nets) { dw_block_job<false, DwNoGate, true>(a, sb / small, nb32 * nb32 + sb % small, smem); IL_TLC(kind ? 11 : 10, 5); IL_TL_END(kind ? 11 : 10); return; }
+      const int bias_blocks = (H / 16 * a.n_nets + 3) / 4, bb = sb - small * a.n_nets;
+      if (bb < bias_blocks) {
+        const int job = bb * 4 + (int)(threadIdx.x >> 6);
+        if (job < H / 16 * a.n_nets) {
+          const int net = job / (H / 16), jn = job % (H / 16);
+          adam_consts ac = {};
+          if (!a.grads_only) ac = load_adam_consts(a.opt);
+          dw_bias(a, ac, a.dz2 + net * a.h_net_stride, H, jn * 16, (int64_t)net * a.net_stride + (int64_t)H * a.in_dim + H + (int64_t)H * H);
+        }
+        IL_TLC(kind ? 11 : 10, 5); IL_TL_END(kind ? 11 : 10);
+        return;
+      }
+      a.n_dw_blocks = 0; a.n_big_blocks = 0; a.jobs_per_block = 4;   // the tail blocks (actor launch)
+      dw_adam_body<4, true>(a, bb - bias_blocks, own - nb64 - small * a.n_nets - bias_blocks);
+      IL_TLC(kind ? 11 : 10, 5); IL_TL_END(kind ? 11 : 10);
+      return;
+    }
+    a.n_dw_blocks = dw_blocks(a.in_dim, a.hidden, a.out_dim, a.n_nets, 1); a.n_big_blocks = 0; a.jobs_per_block = 4;
+    dw_adam_body<4, true>(a, bx - nb64, own - nb64);
+    IL_TLC(kind ? 11 : 10, 5); IL_TL_END(kind ? 11 : 10);
+    return;
+  }
+  a.n_dw_blocks = dw_blocks(a.in_dim, a.hidden, a.out_dim, a.n_nets, 0); a.n_big_blocks = 0; a.jobs_per_block = 4;
+  dw_adam_body<4>(a, bx, own);
+}
 
-extern "C" int il_sac_update_population(const il_sac* descs_dev, const il_batch* batches_dev, int32_t n_learners, const il_sac* shape_host, uint32_t flags, il_stream_t stream_) {
-  IL_CHECK_ARG(descs_dev && batches_dev && shape_host && n_learners >= 1 && n_learners <= 65535, "il_sac_update_population: bad arguments");
-  IL_CHECK_ARG(!(flags & IL_FLAG_GRADS_ONLY), "il_sac_update_population: IL_FLAG_GRADS_ONLY is not supported on the population path");
+// The launches of il_sac_update_population (mixed_host == nullptr: every learner has shape_host's widths) and of il_sac_update_population_mixed (mixed_host = the n_learners
+// host descriptors, already checked; shape_host = the first of them). Only three things depend on a learner's widths: the tile kernels' LDS allocation (the LAYOUT inside
+// is the learner's own), and the grids of the two optimiser launches - those are the maxima over the learners, and k_dw_adam_pop_mixed ends a learner's surplus workgroups.
+static int sac_population_launches(const il_sac* descs_dev, const il_batch* batches_dev, int32_t n_learners, const il_sac* shape_host, const il_sac* mixed_host, uint32_t flags,
+                                   il_stream_t stream_, const char* who) {
   const il_sac* d = shape_host;
-  IL_CHECK_ARG(d->hidden % 64 == 0 && d->hidden >= 64 && d->hidden <= 256 && d->batch % IL_TILE_R == 0 && d->batch > 0 && 2 * d->action_dim <= 16, "il_sac_update_population: unsupported shape");
   hipStream_t st = (hipStream_t)stream_;
   const int S = d->state_dim, A = d->action_dim, H = d->hidden, B = d->batch, nt = B / IL_TILE_R, L = n_learners;
-  const size_t lds = tile_lds_bytes(round_up16(S + A), H);
+  size_t lds = tile_lds_bytes(round_up16(S + A), H);
+  for (int l = 0; mixed_host && l < L; ++l) lds = std::max(lds, tile_lds_bytes(round_up16(mixed_host[l].state_dim + mixed_host[l].action_dim), H));
   il_sac z = *d; il_batch zb = {};
   // Tile kernels of the population launch run with HALF the waves of the single-learner launch (each wave then owns two 16-column tiles): two workgroups share a CU
   // and their load / barrier / epilogue phases overlap each other's MFMA phases (measured at 32 learners: 60.2k -> 64.5k aggregate updates/s; a quarter: 60.0k).
@@ -2810,7 +2872,16 @@ extern "C" int il_sac_update_population(const il_sac* descs_dev, const il_batch*
     // must see the same setting (the actor launch's tail skips exactly what the critic launch's blocks stepped). IL_POP_FUSE_POLYAK=0: the whole step in the tail - same bits.
     static const uint32_t fuse = [] { const char* e = getenv("IL_POP_FUSE_POLYAK"); return e && e[0] == '0' ? 0u : IL_FLAG_POP_FUSE_POLYAK; }();
     if (b64) flags |= fuse;
-    { IL_TRACE("k_dw_adam_critic", st); k_dw_adam_pop<<<dim3(nbc + pop_dw_small_grid(S + A, H, 1, 2, B, b64), L), 256, 0, st>>>(descs_dev, batches_dev, 0, flags, nbc); }
+    int gc = nbc + pop_dw_small_grid(S + A, H, 1, 2, B, b64), ga = nba + pop_dw_small_grid(S, H, 2 * A, 1, B, b64) + IL_POP_TAIL_BLOCKS;
+    for (int l = 0; mixed_host && l < L; ++l) {
+      const int Sl = mixed_host[l].state_dim, Al = mixed_host[l].action_dim;
+      gc = std::max(gc, nbc + pop_dw_small_grid(Sl + Al, H, 1, 2, B, b64)); ga = std::max(ga, nba + pop_dw_small_grid(Sl, H, 2 * Al, 1, B, b64) + IL_POP_TAIL_BLOCKS);
+    }
+    {
+      IL_TRACE("k_dw_adam_critic", st);
+      if (mixed_host) k_dw_adam_pop_mixed<<<dim3(gc, L), 256, 0, st>>>(descs_dev, batches_dev, 0, flags, nbc);
+      else k_dw_adam_pop<<<dim3(gc, L), 256, 0, st>>>(descs_dev, batches_dev, 0, flags, nbc);
+    }
     {
       IL_TRACE("k_policy_critic", st);
       // Round 4: the policy backward is a launch of its own behind the critics (uniform workgroups in both) instead of the tail of each tile's second arriver, which made
@@ -2823,10 +2894,45 @@ extern "C" int il_sac_update_population(const il_sac* descs_dev, const il_batch*
         else k_actor_bwd<<<dim3(nt, L), tt, lds, st>>>(z, zb, descs_dev, batches_dev);
       }
     }
-    { IL_TRACE("k_dw_adam_actor", st); k_dw_adam_pop<<<dim3(nba + pop_dw_small_grid(S, H, 2 * A, 1, B, b64) + 33, L), 256, 0, st>>>(descs_dev, batches_dev, 1, flags, nba); }
+    {
+      IL_TRACE("k_dw_adam_actor", st);
+      if (mixed_host) k_dw_adam_pop_mixed<<<dim3(ga, L), 256, 0, st>>>(descs_dev, batches_dev, 1, flags, nba);
+      else k_dw_adam_pop<<<dim3(ga, L), 256, 0, st>>>(descs_dev, batches_dev, 1, flags, nba);
+    }
   }
-  IL_CHECK_LAUNCH("il_sac_update_population");
+  IL_CHECK_LAUNCH(who);
   return IL_OK;
+}
+extern "C" int il_sac_update_population(const il_sac* descs_dev, const il_batch* batches_dev, int32_t n_learners, const il_sac* shape_host, uint32_t flags, il_stream_t stream_) {
+  IL_CHECK_ARG(descs_dev && batches_dev && shape_host && n_learners >= 1 && n_learners <= 65535, "il_sac_update_population: bad arguments");
+  IL_CHECK_ARG(!(flags & IL_FLAG_GRADS_ONLY), "il_sac_update_population: IL_FLAG_GRADS_ONLY is not supported on the population path");
+  const il_sac* d = shape_host;
+  IL_CHECK_ARG(d->hidden % 64 == 0 && d->hidden >= 64 && d->hidden <= 256 && d->batch % IL_TILE_R == 0 && d->batch > 0 && 2 * d->action_dim <= 16, "il_sac_update_population: unsupported shape");
+  return sac_population_launches(descs_dev, batches_dev, n_learners, shape_host, nullptr, flags, stream_, "il_sac_update_population");
+}
+// Learners of different state / action widths under il_sac_update_population's schedule (include/il_hip.h). Everything is decided on the host, ahead of every launch.
+extern "C" int il_sac_update_population_mixed(const il_sac* descs_dev, const il_batch* batches_dev, int32_t n_learners, const il_sac* descs_host, uint32_t flags, il_stream_t stream_) {
+  IL_CHECK_ARG(descs_dev && batches_dev && descs_host, "il_sac_update_population_mixed: null array (device descriptors %p, device batches %p, host descriptors %p)", (const void*)descs_dev,
+               (const void*)batches_dev, (const void*)descs_host);
+  IL_CHECK_ARG(n_learners >= 1 && n_learners <= 65535, "il_sac_update_population_mixed: n_learners=%d must be in 1..65535 (the learner is a grid dimension)", n_learners);
+  IL_CHECK_ARG(!(flags & IL_FLAG_GRADS_ONLY), "il_sac_update_population_mixed: IL_FLAG_GRADS_ONLY is not supported on the population path");
+  const int H = descs_host[0].hidden, B = descs_host[0].batch;
+  IL_CHECK_ARG(H % 64 == 0 && H >= 64 && H <= 256, "il_sac_update_population_mixed: hidden=%d must be a multiple of 64 in [64,256]", H);
+  IL_CHECK_ARG(B > 0 && B % IL_TILE_R == 0, "il_sac_update_population_mixed: batch=%d must be a positive multiple of %d", B, IL_TILE_R);
+  for (int l = 0; l < n_learners; ++l) {
+    const il_sac& e = descs_host[l];
+    IL_CHECK_ARG(e.hidden == H, "il_sac_update_population_mixed: learner %d has hidden=%d, learner 0 has %d (one hidden size per population)", l, e.hidden, H);
+    IL_CHECK_ARG(e.batch == B, "il_sac_update_population_mixed: learner %d has batch=%d, learner 0 has %d (one batch size per population)", l, e.batch, B);
+    IL_CHECK_ARG(e.action_dim >= 1 && 2 * e.action_dim <= 16, "il_sac_update_population_mixed: learner %d: action_dim=%d unsupported (2A <= 16)", l, e.action_dim);
+    IL_CHECK_ARG(e.state_dim >= 1 && e.state_dim + e.action_dim <= 508, "il_sac_update_population_mixed: learner %d: state_dim=%d too large", l, e.state_dim);
+  }
+  for (int l = 0; l < n_learners; ++l) {   // (behind the shapes: a workspace is sized by them)
+    const il_sac& e = descs_host[l];
+    const SacWs ws = sac_ws(e.state_dim, e.action_dim, H, B);
+    if (!e.workspace || e.workspace_floats < ws.total)
+      return il_set_error(IL_ERR_WORKSPACE, "il_sac_update_population_mixed: learner %d: workspace too small (%lld < %lld floats)", l, (long long)e.workspace_floats, (long long)ws.total);
+  }
+  return sac_population_launches(descs_dev, batches_dev, n_learners, descs_host, descs_host, flags, stream_, "il_sac_update_population_mixed");
 }
 
 // The lane-ordered weight copies only depend on the parameters: a caller may build them early (e.g. next to the replay sampling on
@@ -3413,6 +3519,15 @@ __global__ __launch_bounds__(1024) void k_act_step_population(const il_act_learn
   act_step_body<true>(smem, d.actor, S, A, H, d.mailbox, d.carry, d.ring, (long long*)d.ring_state, row, d.noise_seed, 0u);
 }
 
+// The same launch for learners of different widths (il_act_step_population_mixed): S, A and the ring row are learner l's own, read from dims[l] beside learners[l]; the
+// LDS layout is actor_tile's for those widths, only the allocation is the widest learner's.
+__global__ __launch_bounds__(1024) void k_act_step_population_mixed(const il_act_learner* __restrict__ learners, const il_act_dims* __restrict__ dims, int H) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const il_act_learner d = learners[blockIdx.x];
+  const il_act_dims w = dims[blockIdx.x];
+  act_step_body<true>(smem, d.actor, w.state_dim, w.action_dim, H, d.mailbox, d.carry, d.ring, (long long*)d.ring_state, w.ring_row_floats, d.noise_seed, 0u);
+}
+
 extern "C" int il_actor_act(const float* actor, int32_t S, int32_t A, int32_t H, const float* states, int32_t ld_states, int32_t n, const float* eps,
                             uint64_t noise_seed, uint32_t noise_offset, int32_t greedy, float* out_action, float* out_logp, il_stream_t stream_) {
   IL_CHECK_ARG(actor && states && out_action && n > 0, "il_actor_act: null argument");
@@ -3477,6 +3592,28 @@ extern "C" int il_act_step_population(const il_act_learner* learners, int32_t n_
     k_act_step_population<<<n_learners, tile_threads(H), tile_lds_bytes(round_up16(S + A), H), (hipStream_t)stream_>>>(learners, S, A, H, row);
   }
   IL_CHECK_LAUNCH("il_act_step_population");
+  return IL_OK;
+}
+
+extern "C" int il_act_step_population_mixed(const il_act_learner* learners, const il_act_dims* dims_dev, const il_act_dims* dims_host, int32_t n_learners, int32_t H, il_stream_t stream_) {
+  IL_CHECK_ARG(learners && dims_dev && dims_host, "il_act_step_population_mixed: null array (descriptors %p, device widths %p, host widths %p)", (const void*)learners, (const void*)dims_dev,
+               (const void*)dims_host);
+  IL_CHECK_ARG(n_learners >= 1, "il_act_step_population_mixed: no learner (n_learners=%d)", n_learners);
+  IL_CHECK_ARG(H % 64 == 0 && H >= 64 && H <= 256, "il_act_step_population_mixed: hidden=%d must be a multiple of 64 in [64,256]", H);
+  size_t lds = 0;
+  for (int l = 0; l < n_learners; ++l) {
+    const int S = dims_host[l].state_dim, A = dims_host[l].action_dim, row = dims_host[l].ring_row_floats;
+    IL_CHECK_ARG(A >= 1 && 2 * A <= 16 && S >= 1, "il_act_step_population_mixed: learner %d: unsupported dims (state_dim=%d, action_dim=%d)", l, S, A);
+    IL_CHECK_ARG(row == il_ring_row_floats(S, A), "il_act_step_population_mixed: learner %d: ring_row_floats=%d is not il_ring_row_floats(%d, %d) = %d", l, row, S, A, il_ring_row_floats(S, A));
+    IL_CHECK_ARG(row <= tile_threads(H) && 64 + S <= tile_threads(H), "il_act_step_population_mixed: learner %d: ring row of %d floats / state_dim %d exceed the %d-thread workgroup", l, row, S,
+                 tile_threads(H));
+    lds = std::max(lds, tile_lds_bytes(round_up16(S + A), H));
+  }
+  {
+    IL_TRACE("k_act_step_population_mixed", stream_);
+    k_act_step_population_mixed<<<n_learners, tile_threads(H), lds, (hipStream_t)stream_>>>(learners, dims_dev, H);
+  }
+  IL_CHECK_LAUNCH("il_act_step_population_mixed");
   return IL_OK;
 }
 

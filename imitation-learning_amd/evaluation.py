@@ -63,13 +63,14 @@ def evaluate_population(worker, eval_envs, num_episodes: int):
   assert len(eval_envs) == L
   returns = [[] for _ in range(L)]
   if num_episodes <= 0: return returns
+  widths = worker.widths if getattr(worker, 'mixed', False) else None   # learners of different widths: row l of the [L, widest A] actions holds learner l's own A_l components
   with torch.inference_mode():
     obs, totals = [env.reset() for env in eval_envs], [0.0] * L
     while any(o is not None for o in obs):
       acts = worker.act_eval(obs)
       for l in range(L):
         if obs[l] is None: continue
-        nxt, r, finished = eval_envs[l].step(acts[l:l + 1])
+        nxt, r, finished = eval_envs[l].step(acts[l:l + 1, :widths[l][1]] if widths else acts[l:l + 1])
         totals[l] += float(r)
         if finished:
           returns[l].append(totals[l]); totals[l] = 0.0

@@ -1514,6 +1514,7 @@ class _GailStep(_SacStep):
     pop.reward_ptrs = _reward_ptrs(plans, dev)
     assert len({int(p.disc.loss_function) for p in plans}) == 1, 'BatchedPopulationPlan(GAIL): the discriminators of one population share loss_function'
     pop.mixup_alpha, pop.extras, pop._extras_host = None, None, None
+    pop._disc_host = (_lib.Disc * pop.L)(*[p.disc for p in plans]) if getattr(pop, 'mixed', False) else None
     if int(p0.disc.loss_function) == LOSS_FUNCTIONS['Mixup']:
       alphas = {1.0 if p._beta_alpha is None else float(p._beta_alpha) for p in plans}
       assert len(alphas) == 1, f'BatchedPopulationPlan(GAIL): the Mixup learners of one population share mixup_alpha (got {sorted(alphas)})'
@@ -1527,7 +1528,10 @@ class _GailStep(_SacStep):
     """Mixup with alpha != 1: the coefficient launch inside reads each learner's update counter on the device, like the gradient launch behind it does for its
     gradient-penalty draws - both sit behind the previous update's actor step, which bumps it."""
     L, p0 = _lib.lib(), pop.plans[0]
-    if pop.mixup_alpha is None:
+    if pop._disc_host is not None:   # learners of different widths (Mixup was refused when the plan was built)
+      _lib.check(L.il_gail_step_population_mixed(_lib.ptr(pop.disc_descs), _lib.ptr(pop.batches), _lib.ptr(pop.expert_batches), _lib.ptr(pop.reward_ptrs), pop.L,
+                                                 C.cast(pop._disc_host, C.c_void_p), st))
+    elif pop.mixup_alpha is None:
       _lib.check(L.il_gail_step_population(_lib.ptr(pop.disc_descs), _lib.ptr(pop.batches), _lib.ptr(pop.expert_batches), _lib.ptr(pop.reward_ptrs), pop.L, C.byref(p0.disc), st))
     else:
       _lib.check(L.il_gail_mixup_step_population(_lib.ptr(pop.disc_descs), _lib.ptr(pop.batches), _lib.ptr(pop.expert_batches), _lib.ptr(pop.reward_ptrs), pop.L, C.byref(p0.disc),
@@ -1682,8 +1686,9 @@ POPULATION_STEPS = {'SAC': _SacStep(), 'GAIL': _GailStep(), 'RED': _RedStep(), '
 
 
 class BatchedPopulationPlan(_Branches):
-  """N independent learners with identical shapes advanced by the SAME kernel launches (`il_*_population`): the learner id is a grid
-  dimension, so one update of the whole population costs 11 launches instead of 11 N.  This is the route from the latency-bound
+  """N independent learners advanced by the SAME kernel launches (`il_*_population`): the learner id is a grid
+  dimension, so one update of the whole population costs 11 launches instead of 11 N. The learners have identical shapes (a seed sweep), or - SAC and GAIL without Mixup -
+  share hidden size and batch and differ in state / action width (the reference's train_all.py: four environments side by side), which the `_mixed` entry points serve.  This is the route from the latency-bound
   single-learner regime towards the HBM roofline.  Every learner keeps its own replay ring, MT19937 index stream,
   networks, optimiser state, scratch and Philox counter (build the `UpdatePlan`s with distinct `learner_id`s).
 
@@ -1713,6 +1718,17 @@ class BatchedPopulationPlan(_Branches):
     if any(getattr(p, 'general', False) for p in self.plans):
       raise NotImplementedError('BatchedPopulationPlan: actor / critic shapes outside depth 2 / ReLU / hidden <= 256 / action_size <= 8 have no population launches (PopulationPlan runs them as independent graph branches)')
     self.algorithm, self.B, self.L, dev = p0.algorithm, p0.B, len(self.plans), p0.rows.device
+    # learners of different state / action widths (the four environments of train_all.py): the `_mixed` entry points, which size every launch from ALL descriptors. What one
+    # launch cannot serve is refused here, before any launch
+    self.mixed = len({(int(p.sac.state_dim), int(p.sac.action_dim)) for p in self.plans}) > 1
+    self._sac_host = None
+    if self.mixed:
+      assert p0.algorithm in ('SAC', 'GAIL'), f'BatchedPopulationPlan({p0.algorithm}): learners of different state / action widths have population launches for SAC and GAIL only'
+      _refuse_mixing(self.plans, p0.algorithm + ', mixed widths')
+      assert len({int(p.sac.hidden) for p in self.plans}) == 1, f'BatchedPopulationPlan: the learners of a mixed-width population share one hidden size (got {sorted({int(p.sac.hidden) for p in self.plans})})'
+      if p0.algorithm == 'GAIL':
+        assert not any(int(p.disc.loss_function) == LOSS_FUNCTIONS['Mixup'] for p in self.plans), 'BatchedPopulationPlan(GAIL): Mixup has no population launch for learners of different widths'
+      self._sac_host = (_lib.Sac * self.L)(*[p.sac for p in self.plans])   # host copies: the entry point takes its maxima, and decides its refusals, on these
     self.sac_descs = _device_array([p.sac for p in self.plans], dev)
     self.batches = _device_array([p.pb for p in self.plans], dev)
     args = []
@@ -1742,6 +1758,8 @@ class BatchedPopulationPlan(_Branches):
     self.step.relabel_args(self, step, num_trajectories)
 
   def _sac_update(self, flags: int, st):
+    if self.mixed:
+      return _lib.check(_lib.lib().il_sac_update_population_mixed(_lib.ptr(self.sac_descs), _lib.ptr(self.batches), self.L, C.cast(self._sac_host, C.c_void_p), flags, st))
     _lib.check(_lib.lib().il_sac_update_population(_lib.ptr(self.sac_descs), _lib.ptr(self.batches), self.L, C.byref(self.plans[0].sac), flags, st))
 
   def run(self):

@@ -312,11 +312,20 @@ int il_sac_dp_phase(const il_sac* d, const il_batch* batch, int32_t phase, float
 /* DP tail after the all-reduce of actor_grad/alpha_grad: AdamW(actor) + Adam(log_alpha) + polyak (same kernels, no recompute). */
 int il_sac_apply_actor_grads(const il_sac* d, il_stream_t stream);
 int il_sac_apply_critic_grads(const il_sac* d, il_stream_t stream);
-/* Population axis (the reference's own usage: 10-seed sweeps, Ax trials -- README.md:96-99, train_all.py:26): n_learners independent
- * learners with identical shapes advanced by the same launches. descs_dev / batches_dev are DEVICE arrays of descriptors (each learner
- * owns its arenas, optimiser state, workspace, noise counter, batch); shape_host supplies the common dimensions. Philox noise only. */
+/* Population axis (the reference's own usage: 10-seed sweeps, Ax trials -- README.md:96-99; the four environments of train_all.py:26): n_learners independent
+ * learners advanced by the same launches. descs_dev / batches_dev are DEVICE arrays of descriptors (each learner owns its arenas, optimiser state, workspace, noise
+ * counter, batch). Philox noise only. Two forms: learners of identical shapes (a seed sweep), whose common dimensions shape_host supplies, and - the `_mixed` entry
+ * points - learners one launch can serve: one algorithm, one hidden size, one batch size, but each its own state_dim / action_dim (ant, halfcheetah, hopper and walker2d
+ * side by side), whose launches are sized on the host from all n_learners descriptors. */
 int il_sac_update_population(const il_sac* descs_dev, const il_batch* batches_dev, int32_t n_learners, const il_sac* shape_host, uint32_t flags,
                              il_stream_t stream);
+/* il_sac_update_population's schedule over learners that differ in state_dim / action_dim. descs_host: the n_learners descriptors of descs_dev in host memory (the
+ * launches are sized from them: tile LDS for the widest round_up16(S + A), every grid the maximum over the learners of that learner's own count; a workgroup beyond a
+ * narrower learner's own count returns before it touches anything, and each learner's tail gets its own index and count). Inside a workgroup the widths, the workspace
+ * layout and the LDS layout are the learner's own, so every learner's results are bit-identical to il_sac_update_population on a uniform population of its widths, and
+ * so to il_sac_update. Shared by all learners and checked here: hidden (64..256 in multiples of 64) and batch (a positive multiple of 16); per learner: 2A <= 16,
+ * S + A <= 508, its workspace. IL_ERR_ARG / IL_ERR_WORKSPACE name the learner; nothing is launched then. */
+int il_sac_update_population_mixed(const il_sac* descs_dev, const il_batch* batches_dev, int32_t n_learners, const il_sac* descs_host, uint32_t flags, il_stream_t stream);
 /* Builds the lane-ordered copies of the hidden-layer weights in the workspace (k_repack). il_sac_update does this itself unless told
  * IL_FLAG_SAC_PREPARED; exposing it lets a caller overlap it with the replay sampling. */
 int il_sac_prepare(const il_sac* d, il_stream_t stream);
@@ -459,6 +468,15 @@ typedef struct il_act_learner {
   const float* actor; float* mailbox; float* carry; float* ring; int64_t* ring_state; uint64_t noise_seed;
 } il_act_learner;
 int il_act_step_population(const il_act_learner* learners /* device */, int32_t n_learners, int32_t state_dim, int32_t action_dim, int32_t hidden, il_stream_t stream);
+/* il_act_step_population for learners of different widths: learner l's state_dim, action_dim and ring row come from dims[l], a second array beside the unchanged
+ * il_act_learner array (dims_dev on the device for the kernel, dims_host - the same records - for the host, which sizes the launch's LDS for the widest learner and
+ * checks every learner against il_act_step's limits for ITS widths: 2A <= 16, ring row and 64 + S within the workgroup, ring_row_floats == il_ring_row_floats(S, A)).
+ * Learner l's mailbox is laid out as il_act_mailbox_floats(S_l, A_l)'s, its carry has S_l + A_l + 4 floats. One hidden size. Per learner bit-identical to il_act_step. */
+typedef struct il_act_dims {
+  int32_t state_dim, action_dim, ring_row_floats, reserved;
+} il_act_dims;
+int il_act_step_population_mixed(const il_act_learner* learners /* device */, const il_act_dims* dims_dev, const il_act_dims* dims_host, int32_t n_learners, int32_t hidden,
+                                 il_stream_t stream);
 /* Publish the actor arena (n floats) into snapshot slot (version+1)%3 of `mirror` and advance the version. version_and_counter: device
  * int32[2] = {version, internal completion counter}, zero-initialised. Enqueue after every update (capturable into the update's graph). */
 int il_act_publish(const float* actor, int64_t n, float* mirror, int64_t mirror_stride, int32_t* version_and_counter, il_stream_t stream);
@@ -534,6 +552,13 @@ int il_gail_disc_step_draw_staged2(const il_disc* d, const il_batch* policy, con
 /* Population axis: discriminator step + AIRL/GAIL/FAIRL reward relabel for n_learners discriminators; rewards_out_dev[l] -> float[batch]. */
 int il_gail_step_population(const il_disc* descs_dev, const il_batch* policy_dev, const il_batch* expert_dev, float* const* rewards_out_dev,
                             int32_t n_learners, const il_disc* shape_host, il_stream_t stream);
+/* il_gail_step_population over discriminators that differ in state_dim / action_dim (BCE, and PUGAIL with an infinite margin). descs_host: the n_learners descriptors in
+ * host memory; the gradient and reward launches get the LDS of the widest D = S + A, the reduce launch the widest (P + 255) / 256 workgroups (surplus threads of a
+ * narrower learner have no element and do nothing); inside a workgroup every layout is the learner's own. Shared by all learners and checked here: hidden, batch,
+ * spectral_norm, state_only, reward_function, loss_function, and whether there is a gradient penalty. Refused (IL_ERR_ARG, nothing launched): Mixup, pu_clamped, a
+ * learner that differs in one of those. Per learner bit-identical to il_gail_disc_step + il_gail_reward. */
+int il_gail_step_population_mixed(const il_disc* descs_dev, const il_batch* policy_dev, const il_batch* expert_dev, float* const* rewards_out_dev, int32_t n_learners,
+                                  const il_disc* descs_host, il_stream_t stream);
 /* The same step for discriminators whose loss is Mixup (training.py:104-113), which il_gail_step_population refuses. extras_dev: a device array of n_learners
  * il_gail_extra, or NULL; extras_host: the same array in host memory (the refusals below are decided on the host, ahead of every launch), NULL exactly when extras_dev is.
  * Learner l mixes with extras[l].eps_mix [batch] where that pointer is set, and otherwise with the on-chip U(0,1) stream of ITS noise_seed / *noise_counter (alpha = 1).

@@ -549,10 +549,11 @@ def sweep_fallback_reason(cfg):
   return None
 
 
-def _without_seed(cfg) -> dict:
+def _without_seed(cfg, also=()) -> dict:
   import copy
   d = copy.deepcopy(dict(cfg))
   d.pop('seed', None)
+  for k in also: d.pop(k, None)
   return d
 
 
@@ -583,8 +584,24 @@ def sweep_dir(cfg, stamp: str) -> str:
   return os.path.join('outputs', f'{cfg.algorithm}_{cfg.env}_sweeper', stamp)
 
 
-def train_sweep(cfgs, prefixes):
-  """The loop of train() in lockstep over L learners that differ only in their seed: per lockstep step ONE population act launch, L host environment steps and ONE
+def mixed_env_fallback_reason(cfg):
+  """None when learners of this configuration on DIFFERENT environments (train_all.py: different state / action widths) can train as one population; otherwise why not.
+  The population launches serve learners of different widths for SAC and for GAIL without Mixup (the `_mixed` entry points of include/il_hip.h)."""
+  reason = sweep_fallback_reason(cfg)
+  if reason is not None: return reason
+  if cfg.algorithm not in ('SAC', 'GAIL'):
+    return f'algorithm={cfg.algorithm} has no population launches for learners of different state / action widths (SAC and GAIL have)'
+  if cfg.algorithm == 'GAIL' and cfg.imitation.loss_function == 'Mixup':
+    return 'imitation.loss_function=Mixup has no population discriminator step for learners of different state / action widths'
+  return None
+
+
+def train_sweep(cfgs, prefixes, vary_env: bool = False, noise_ids=None):
+  """`vary_env` (train_all.py): the learners may also differ in `env`, i.e. in their state / action widths - SAC and GAIL without Mixup (mixed_env_fallback_reason).
+  `noise_ids` (train_all.py -m): per learner, the id its Philox key is derived from instead of its position in the population - a job's four learners then draw the noise
+  they draw when that job runs alone, wherever they stand in a population of several jobs. The key is seed + 7919 * (id + 1), as for positions: two learners of one population
+  share a key only if their seeds differ by a multiple of 7919 on different ids (seed=3 on id 1 and seed=7922 on id 0) - different environments then, so different streams of use.
+  The loop of train() in lockstep over L learners that differ only in their seed: per lockstep step ONE population act launch, L host environment steps and ONE
   append launch (`+acting.schedule=fused`: one launch for both); on update steps ONE population update (il.BatchedPopulationPlan); on evaluation steps
   evaluate_population. Every learner has its own seeds, index stream, environments, rings, networks, optimisers and `learner_id`; job l writes what a single run writes
   under prefixes[l] (GAIL, RED and DRIL: with a discriminator.pth; PWIL, AdRIL and GMMIL, as in train(): without one - its bandwidths are fixed by each learner's first batch, in the first, eager,
@@ -593,9 +610,13 @@ def train_sweep(cfgs, prefixes):
   assert L >= 1 and len(prefixes) == L
   for cfg in cfgs: il_config.validate(cfg)
   cfg0 = cfgs[0]
-  assert all(_without_seed(c) == _without_seed(cfg0) for c in cfgs), 'train_sweep: the jobs of one population differ only in their seed'
-  reason = sweep_fallback_reason(cfg0)
-  if reason is not None: raise NotImplementedError(f'train_sweep: {reason}')
+  if vary_env:
+    assert all(_without_seed(c, ('env',)) == _without_seed(cfg0, ('env',)) for c in cfgs), 'train_sweep: the jobs of one population differ only in seed and env'
+  else:
+    assert all(_without_seed(c) == _without_seed(cfg0) for c in cfgs), 'train_sweep: the jobs of one population differ only in their seed'
+  for c in (cfgs if vary_env else cfgs[:1]):
+    reason = mixed_env_fallback_reason(c) if vary_env and len({x.env for x in cfgs}) > 1 else sweep_fallback_reason(c)
+    if reason is not None: raise NotImplementedError(f'train_sweep: {reason}')
   how, schedule = sweep_schedule(cfg0), (cfg0.get('acting', {}) or {}).get('schedule', 'exact')
   dev = default_device()
   assert _lib.on_device(torch.empty(0, device=dev)), 'train.py needs a GPU: the update path has no CPU fallback'
@@ -641,7 +662,7 @@ def train_sweep(cfgs, prefixes):
                             cfg.reinforcement.discount, ln.entropy_target, cfg.reinforcement.polyak_factor, expert_memory=ln.expert_memory, discriminator=ln.discriminator,
                             discriminator_optimiser=ln.discriminator_optimiser, imitation_cfg=cfg.imitation if cfg.algorithm == 'GAIL' else None, overlap=False, learner_id=i,
                             bc_aux=bool(cfg.imitation.bc_aux_loss),   # (sweep_fallback_reason: set for DRIL learners only)
-                            noise_seed_offset=0 if cfg.algorithm == 'PWIL' or mixup_sweep else None)   # PWIL and Mixup jobs train as train() trains them, bit for bit: its Philox key for this learner's seed
+                            noise_seed_offset=0 if cfg.algorithm == 'PWIL' or mixup_sweep else (None if noise_ids is None else 7919 * (int(noise_ids[i]) + 1)))   # PWIL and Mixup jobs train as train() trains them, bit for bit: its Philox key for this learner's seed
     ln.plan.main_feeds_ring = True
     ln.plan.watch_timeouts()
     if ln.discriminator is not None and cfg.algorithm not in ('DRIL', 'PWIL', 'AdRIL'): ln.discriminator.eval()   # train.py:147 (the DRIL ensemble keeps its dropout, i.e. train mode, on purpose)
@@ -661,18 +682,20 @@ def train_sweep(cfgs, prefixes):
       for p in plans: p.run()
 
   every = range(L)
+  widths = [ln.env.action_space.shape[0] for ln in learners]   # learner l's own action components: row l of the population's [L, widest A] tensor, or its own worker's [1, A_l]
+  own = lambda action, l: action[l] if isinstance(action, list) else action[l:l + 1, :widths[l]]
   t, train_return = [0] * L, [0.0] * L
   state = [ln.env.reset() for ln in learners]
   action = None
   if schedule == 'fused':
-    action = worker.act(state) if worker is not None else torch.cat([workers[l].act(state[l]) for l in every])
+    action = worker.act(state) if worker is not None else [workers[l].act(state[l]) for l in every]
   captured, last_good = False, 0
   for step in range(1, cfg0.steps + 1):
     if schedule == 'exact':
-      action = worker.act(state) if worker is not None else torch.cat([workers[l].act(state[l]) for l in every])
+      action = worker.act(state) if worker is not None else [workers[l].act(state[l]) for l in every]
     next_state, reward, terminal, timed_out, following = [None] * L, [0.0] * L, [False] * L, [False] * L, [None] * L
     for l, ln in enumerate(learners):
-      next_state[l], reward[l], terminal[l] = ln.env.step(action[l:l + 1])
+      next_state[l], reward[l], terminal[l] = ln.env.step(own(action, l))
       t[l] += 1
       timed_out[l] = t[l] == ln.env.max_episode_steps
       following[l] = ln.env.reset() if terminal[l] else next_state[l]   # the observation the next action is for
@@ -683,7 +706,7 @@ def train_sweep(cfgs, prefixes):
         for l in every: workers[l].append(step, next_state[l], reward[l], true_terminal[l], timed_out[l])
     else:
       if worker is not None: action = worker.step(step, next_state, reward, true_terminal, timed_out, obs=following)
-      else: action = torch.cat([workers[l].step(step, next_state[l], reward[l], true_terminal[l], timed_out[l], obs=following[l]) for l in every])
+      else: action = [workers[l].step(step, next_state[l], reward[l], true_terminal[l], timed_out[l], obs=following[l]) for l in every]
     for l, ln in enumerate(learners):
       train_return[l] += reward[l]
       if terminal[l]:
