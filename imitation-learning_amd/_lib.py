@@ -106,6 +106,10 @@ class ActDims(C.Structure):   # il_act_dims: learner l's widths for il_act_step_
   _fields_ = [('state_dim', C.c_int32), ('action_dim', C.c_int32), ('ring_row_floats', C.c_int32), ('reserved', C.c_int32)]
 
 
+class EvalLearner(C.Structure):   # il_eval_learner: one learner of il_act_eval_rows (a device array of these and the same records on the host; 24 bytes)
+  _fields_ = [('actor', C.c_void_p), ('mailbox', C.c_void_p), ('state_dim', C.c_int32), ('action_dim', C.c_int32)]
+
+
 class GmmilLearner(C.Structure):   # il_gmmil_learner: one learner of il_gmmil_reward_population (a device array of these)
   _fields_ = [('policy', Batch), ('expert', Batch), ('gamma_1', C.c_float), ('gamma_2', C.c_float), ('workspace', C.c_void_p), ('out_rewards', C.c_void_p)]
 
@@ -214,6 +218,8 @@ _SIGNATURES = {
     'il_act_step': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, C.c_int64, _P]),
     'il_act_step_population': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     'il_act_publish': (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P]),
+    'il_eval_mailbox_floats': (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
+    'il_act_eval_rows': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),   # (learners_dev, learners_host, n_learners, max_rows, hidden, stream)
     'il_disc_workspace_floats': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     'il_gail_disc_step': (C.c_int, [C.POINTER(Disc), C.POINTER(Batch), C.POINTER(Batch), _P, C.POINTER(GailExtra), C.c_uint32, _P]),
     'il_disc_deep_numel': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),

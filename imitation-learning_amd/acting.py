@@ -352,6 +352,137 @@ def _rows(xs, rows, width: int) -> np.ndarray:
   return np.stack([_row(xs[l])[:width] for l in rows])
 
 
+def lockstep_refusal(actor, max_rows: int = 1):
+  """None when `il_act_eval_rows` serves this actor; otherwise the predicate it misses, in words (LockstepEvaluator raises it, train.py prints it and evaluates
+  sequentially). A fused-shape actor (`not actor.general`: depth 2, ReLU, hidden a multiple of 64 in 64..256, 2 * action_size <= 16) is inside the entry point's limits on
+  hidden and action width by construction; what is left to ask here, because the evaluator sizes its pinned block from them before the first launch, is the state width
+  against the workgroup and max_rows. The entry point itself checks all of them again on every launch (csrc/sac.hip il_act_eval_rows)."""
+  if getattr(actor, 'general', False):
+    return (f'an actor outside depth 2 / ReLU / hidden 64..256 in multiples of 64 / action_size <= 8 (depth {getattr(actor, "depth", "?")}, {getattr(actor, "activation", "?")}, hidden '
+            f'{actor.hidden}, action_size {actor.action_size}) has no lockstep evaluation launch (general shapes are out of its scope)')
+  H, S = actor.hidden, actor.state_size
+  if S < 1 or 64 + S > max(256, 4 * H): return f'state_size {S} is outside 1 <= state_size and 64 + state_size <= {max(256, 4 * H)} (the workgroup at hidden {H})'
+  if not 1 <= max_rows <= 1024: return f'max_rows {max_rows} is outside 1..1024'
+  return None
+
+
+class LockstepEvaluator:
+  """The greedy actions of up to `max_rows` observations per learner - one row per evaluation episode still running - in ONE `il_act_eval_rows` launch per lockstep step,
+  for one `SoftActor` or several (one hidden size; their state / action widths may differ). Owns the mailboxes (one pinned block, learner l's laid out as
+  il_eval_mailbox_floats(S_l, A_l, max_rows) lays it out) and the descriptor array on the device. Fused actor shapes only: a general shape raises NotImplementedError naming
+  the predicate (`lockstep_refusal`). The launch reads live parameters and changes nothing on the device; nothing of the acting workers is touched.
+
+  Pinned-memory lifetime (the rule of `_drain`): `act` returns with the echoes of the tiles that hold live rows; the tiles without one only echo, and may do so a little
+  later. The next `act` waits for those before it posts (so a launch only ever sees its own post), and the evaluator waits for them before it lets go of the block."""
+
+  def __init__(self, actors, max_rows: int):
+    actors = list(actors) if isinstance(actors, (list, tuple)) else [actors]
+    max_rows = int(max_rows)
+    assert len(actors) >= 1, 'LockstepEvaluator: at least one actor'
+    a0 = actors[0]
+    for l, a in enumerate(actors):
+      reason = lockstep_refusal(a, max_rows)
+      if reason is not None: raise NotImplementedError(f'LockstepEvaluator: learner {l}: {reason}')
+      assert _lib.on_device(a.flat), 'LockstepEvaluator needs the actors on the GPU (there is no CPU path)'
+      assert a.hidden == a0.hidden, f'LockstepEvaluator: one hidden size for all learners (got {a0.hidden} and {a.hidden})'
+      assert a.flat.device == a0.flat.device
+    from .training import _device_array
+    lib = _lib.lib()
+    L = len(actors)
+    self.actors, self.L, self.H, self.max_rows, self.device = actors, L, a0.hidden, max_rows, a0.flat.device
+    self.widths = [(int(a.state_size), int(a.action_size)) for a in actors]
+    self.tiles = (max_rows + 15) // 16
+    self.floats = max(int(lib.il_eval_mailbox_floats(S, A, max_rows)) for S, A in self.widths)
+    self.tensor = torch.zeros(L, self.floats, dtype=torch.float32, pin_memory=True)
+    self.host = self.tensor.numpy()
+    self._flat = self.host.reshape(-1)
+    self._obs, self._act, echo = [], [], []
+    for l, (S, A) in enumerate(self.widths):
+      Sp, Ap = (S + 3) & ~3, (A + 3) & ~3
+      o_obs, o_act = _HEADER, _HEADER + max_rows * Sp
+      o_echo = o_act + max_rows * Ap
+      assert o_echo + self.tiles <= int(lib.il_eval_mailbox_floats(S, A, max_rows)) <= self.floats
+      self._obs.append(self.host[l, o_obs:o_act].reshape(max_rows, Sp)[:, :S])   # views into the block
+      self._act.append(self.host[l, o_act:o_echo].reshape(max_rows, Ap)[:, :A])
+      echo.append(l * self.floats + o_echo + np.arange(self.tiles))
+    self._echo = np.stack(echo)                      # [L, tiles] positions of the echo words in the block
+    self._flat[self._echo.reshape(-1)] = -1.0
+    base, stride = self.tensor.data_ptr(), self.floats * 4
+    descs = [_lib.EvalLearner(a.flat.data_ptr(), base + l * stride, S, A) for l, (a, (S, A)) in enumerate(zip(actors, self.widths))]
+    self._descs_host = (_lib.EvalLearner * L)(*descs)   # the entry point sizes the launch, and decides its refusals, on this copy
+    self._descs = _device_array(descs, self.device)
+    self._arenas = [a.flat.data_ptr() for a in actors]
+    self._seq, self.word = 0, None   # word: the commit word of the last post
+    self._in_flight = False          # a launch has been issued whose echoes (all tiles) have not all been seen yet
+
+  def _next_seq(self) -> int:
+    self._seq = self._seq % (_SEQ_MOD - 1) + 1   # ActingWorker._next_seq's rule: 1 .. 2^17-1, never 0
+    return self._seq
+
+  def _wait(self, where: np.ndarray, what: str, timeout_s: float = 10.0):
+    flat, word, spins, t0 = self._flat, self.word, 0, 0.0
+    while not (flat[where] == word).all():
+      spins += 1
+      if spins == 1:
+        t0 = time.perf_counter()
+      elif spins & 0xFFF == 0 and time.perf_counter() - t0 > timeout_s:
+        torch.cuda.synchronize()  # surfaces an asynchronous launch failure, if that is what happened
+        raise RuntimeError(f'{what}: no echo from the device after {timeout_s:.0f} s (commit word {word}, echoes hold {flat[where].tolist()})')
+
+  def wait(self, what: str = 'il_act_eval_rows'):
+    """Every tile's echo of the last launched post, those without a live row included: behind it no workgroup of that launch reads or writes the block any more. Nothing
+    to wait for when no launch is outstanding (a post that was never launched, or whose launch the entry point refused)."""
+    if not self._in_flight: return
+    self._wait(self._echo.reshape(-1), what)
+    self._in_flight = False
+
+  def post(self, obs_per_learner) -> list:
+    """Pack learner l's observations into rows [0, n_l) of its mailbox, then the row counts, then - last - the L commit words. Returns the row counts."""
+    assert len(obs_per_learner) == self.L, f'LockstepEvaluator: one entry per learner ({self.L}), got {len(obs_per_learner)}'
+    self.wait()
+    counts = []
+    for l, rows in enumerate(obs_per_learner):
+      n = 0 if rows is None else len(rows)
+      assert n <= self.max_rows, f'LockstepEvaluator: learner {l} has {n} rows, the mailbox holds {self.max_rows}'
+      if n:
+        S = self.widths[l][0]
+        if torch.is_tensor(rows): rows = rows.detach().to('cpu', torch.float32).numpy()
+        self._obs[l][:n] = rows.reshape(n, -1)[:, :S] if isinstance(rows, np.ndarray) else np.stack([_row(x)[:S] for x in rows])
+      counts.append(n)
+    self.host[:, 1] = counts
+    self.word = np.float32(self._next_seq() * 64 + GREEDY)
+    self.host[:, 0] = self.word
+    return counts
+
+  def launch(self):
+    """ONE il_act_eval_rows on the current stream (what to act on is read from the mailboxes)."""
+    if any(a.flat.data_ptr() != p for a, p in zip(self.actors, self._arenas)):   # an arena was re-homed: re-derive the descriptors
+      from .training import _device_array
+      for l, a in enumerate(self.actors): self._descs_host[l].actor = a.flat.data_ptr()
+      self._descs, self._arenas = _device_array(list(self._descs_host), self.device), [a.flat.data_ptr() for a in self.actors]
+    rc = _lib.lib().il_act_eval_rows(_lib.ptr(self._descs), C.cast(self._descs_host, C.c_void_p), self.L, self.max_rows, self.H, torch.cuda.current_stream().cuda_stream)
+    if rc: _lib.check(rc)
+    self._in_flight = True
+
+  def act(self, obs_per_learner) -> list:
+    """`obs_per_learner[l]`: the observations of learner l's still-running episodes (a list of rows or an [n_l, S_l] array; empty or None: the learner idles). Returns, per
+    learner, the greedy actions as a CPU tensor [n_l, A_l]. Each actor's `_act_calls` advances by its n_l, as n_l `get_greedy_action` calls would have advanced it."""
+    counts = self.post(obs_per_learner)
+    self.launch()
+    live = [self._echo[l, :(n + 15) // 16] for l, n in enumerate(counts) if n]
+    if live: self._wait(np.concatenate(live), 'il_act_eval_rows')
+    out = []
+    for l, n in enumerate(counts):
+      self.actors[l]._act_calls += n
+      out.append(torch.from_numpy(self._act[l][:n].copy()))
+    return out
+
+  def __del__(self):
+    if getattr(self, '_in_flight', False):
+      try: self.wait()
+      except RuntimeError: pass   # no echo within the bound (a failed launch): nothing left to protect, and __del__ must not raise
+
+
 class PopulationActingWorker:
   """L environment workers - L `SoftActor`s of one hidden size feeding L `ReplayMemory`s - whose device work per lockstep environment step is ONE launch
   (`il_act_step_population`: workgroup l = learner l's `il_act_step`; learners of different state / action widths: `il_act_step_population_mixed`, mailboxes and carries

@@ -188,6 +188,28 @@ def validate(cfg: Config):
   return cfg
 
 
+EVALUATION_SCHEDULES = ('sequential', 'lockstep')
+EVALUATION_DEFAULT_SCHEDULE = 'sequential'
+EVAL_SEED_STRIDE = 7919
+
+
+def evaluation_schedule(cfg) -> str:
+  """`+evaluation.schedule=sequential` (default): evaluate_agent / evaluate_population - the episodes of an evaluation one after another on ONE evaluation environment, a
+  launch and a turn-around per episode step. `lockstep`: `evaluation.episodes` seeded copies of the evaluation environment per learner (lockstep_eval_envs), all episodes
+  stepped together, ONE il_act_eval_rows launch per lockstep step (evaluate_agent_lockstep / evaluate_population_lockstep). The returns under `lockstep` are those of the
+  E seeded copies, not of one environment stepped E times: an opt-in, and training itself is the same bits under both."""
+  schedule = (cfg.get('evaluation', {}) or {}).get('schedule', EVALUATION_DEFAULT_SCHEDULE)
+  assert schedule in EVALUATION_SCHEDULES, f'+evaluation.schedule={schedule}: expected one of {EVALUATION_SCHEDULES}'
+  return schedule
+
+
+def eval_env_seed(seed: int, k: int) -> int:
+  """The seed of evaluation-environment copy k of a learner seeded `seed`: copy 0 is the sequential schedule's eval_env (`seed` itself), copy k > 0 gets
+  seed + 7919 * k - the stride train_sweep uses between its learners' Philox keys, a prime far above any sweep's seed range, so the copies of one learner never share a
+  stream and copy k of seed s coincides with copy 0 of another job only for seeds 7919 apart."""
+  return int(seed) + EVAL_SEED_STRIDE * int(k)
+
+
 def write_conf_tree(path: str):
   """A reference-style `conf/` tree (train_config.yaml, algorithm/<ALG>.yaml with the `# @package _global_` header, optimised_hyperparameters/<name>.yaml) written from this
   module's tables: what `config_dir=` reads back, and a starting point for one's own overlays. `distributed` is this repository's key and is left out."""

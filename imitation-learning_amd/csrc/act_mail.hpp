@@ -1,5 +1,6 @@
 // The acting worker's device protocol (include/il_hip.h il_act_step: the contract; this header: the one place on the device side that knows the layout). Shared by
-// k_act_step / k_act_step_population (sac.hip), k_act_step_general / k_act_commit_general (general.hip) and k_pwil_couple (pwil.hip).
+// k_act_step / k_act_step_population (sac.hip), k_act_step_general / k_act_commit_general (general.hip) and k_pwil_couple (pwil.hip); at the end, the mailbox of the lockstep
+// evaluation launch (k_act_eval_rows, sac.hip).
 #pragma once
 #include "il_common.hpp"
 
@@ -92,4 +93,22 @@ __device__ __forceinline__ void act_commit(const ActPost& p, float* carry, long 
     }
     __hip_atomic_store(p.m.echo(), p.commit, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
+}
+
+// ---- lockstep evaluation mailbox (il_act_eval_rows; pinned host memory): IL_MAIL_HEADER words, then observations [max_rows][Sp] | actions [max_rows][Ap] | one echo word per
+// 16-row tile, Sp / Ap = S / A rounded up to 4 floats, the total to 16. Host -> device: the observation rows, the row count, then the commit word (sequence * 64 + flags, the
+// LAST thing the host writes); device -> host: the action rows [0, n) and every tile's echo of the commit word. No next_state, no carry: the launch changes nothing on the device.
+enum { EVAL_MAIL_COMMIT = 0, EVAL_MAIL_ROWS = 1 };   // [1]: n, the rows in use this step (as a float: 0 <= n <= max_rows <= 1024)
+template <class F>
+struct EvalMail {
+  F* mail; int o_obs, o_act, o_echo, ld_obs, ld_act, tiles;
+  __host__ __device__ F* obs() const { return mail + o_obs; }     // row r: obs() + r * ld_obs
+  __host__ __device__ F* act() const { return mail + o_act; }     // row r: act() + r * ld_act
+  __host__ __device__ F* echo() const { return mail + o_echo; }   // tile t: echo()[t]
+  __host__ __device__ int floats() const { return (o_echo + tiles + 15) & ~15; }   // il_eval_mailbox_floats
+};
+template <class F>
+__host__ __device__ inline EvalMail<F> eval_mail(F* mail, int S, int A, int max_rows) {
+  const int Sp = (S + 3) & ~3, Ap = (A + 3) & ~3;
+  return EvalMail<F>{mail, IL_MAIL_HEADER, IL_MAIL_HEADER + max_rows * Sp, IL_MAIL_HEADER + max_rows * (Sp + Ap), Sp, Ap, (max_rows + 15) / 16};
 }

@@ -3617,6 +3617,59 @@ extern "C" int il_act_step_population_mixed(const il_act_learner* learners, cons
   return IL_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Lockstep evaluation (evaluation.py evaluate_agent_lockstep / evaluate_population_lockstep): the greedy actions of up to max_rows observations per learner - one row per
+// evaluation episode still running - in ONE launch. grid = (16-row tiles, learners); workgroup (t, l) reads learner l's post (act_mail.hpp EvalMail), runs actor_tile on the
+// live rows of tile t in learner l's own LDS layout (the allocation is the widest learner's, as in k_act_step_population_mixed) and stores tanh(mean) for them; rows >= n are
+// left alone. Every tile, live or not, ends with its echo of the commit word. No ring, no carry, no Philox draw: nothing on the device changes, so a launch that runs again
+// without a new post rewrites the same actions and echoes. Per row the action is k_act's at greedy = 1 (the rows of a tile do not depend on each other).
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void k_act_eval_rows(const il_eval_learner* __restrict__ learners, int max_rows, int H) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const il_eval_learner d = learners[blockIdx.y];
+  const int S = d.state_dim, A = d.action_dim, tid = threadIdx.x;
+  const EvalMail<float> m = eval_mail(d.mailbox, S, A, max_rows);
+  const float commit = d.mailbox[EVAL_MAIL_COMMIT];
+  const int n = min(max((int)d.mailbox[EVAL_MAIL_ROWS], 0), max_rows);   // (clamped: whatever the word holds, no row outside the blocks is touched)
+  const int row0 = blockIdx.x * IL_TILE_R, nrows = min(IL_TILE_R, n - row0);
+  if (nrows > 0) {  // block-uniform
+    const ActTile t = actor_tile(smem, d.actor, S, A, H, m.obs(), m.ld_obs, row0, nrows);
+    if (tid < IL_TILE_R * A) {
+      const int r = tid / A, c = tid - r * A;
+      if (r < nrows) m.act()[(size_t)(row0 + r) * m.ld_act + c] = tanhf(t.Os[r * 16 + c]);
+    }
+  }
+  __threadfence_system();
+  __syncthreads();
+  if (tid == 0) __hip_atomic_store(m.echo() + blockIdx.x, commit, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+extern "C" int32_t il_eval_mailbox_floats(int32_t S, int32_t A, int32_t max_rows) { return eval_mail((const float*)nullptr, S, A, max_rows).floats(); }
+
+extern "C" int il_act_eval_rows(const il_eval_learner* learners, const il_eval_learner* learners_host, int32_t n_learners, int32_t max_rows, int32_t H, il_stream_t stream_) {
+  IL_CHECK_ARG(learners && learners_host, "il_act_eval_rows: null array (device descriptors %p, host descriptors %p)", (const void*)learners, (const void*)learners_host);
+  IL_CHECK_ARG(((uintptr_t)learners & 7u) == 0, "il_act_eval_rows: the device descriptor array %p is not 8-byte aligned", (const void*)learners);
+  IL_CHECK_ARG(n_learners >= 1 && n_learners <= 65535, "il_act_eval_rows: n_learners=%d must be in [1,65535]", n_learners);
+  IL_CHECK_ARG(max_rows >= 1 && max_rows <= 1024, "il_act_eval_rows: max_rows=%d must be in [1,1024]", max_rows);
+  IL_CHECK_ARG(H % 64 == 0 && H >= 64 && H <= 256, "il_act_eval_rows: hidden=%d must be a multiple of 64 in [64,256]", H);
+  size_t lds = 0;
+  for (int l = 0; l < n_learners; ++l) {
+    const int S = learners_host[l].state_dim, A = learners_host[l].action_dim;
+    IL_CHECK_ARG(learners_host[l].actor && learners_host[l].mailbox, "il_act_eval_rows: learner %d: null pointer (actor %p, mailbox %p)", l, (const void*)learners_host[l].actor,
+                 (const void*)learners_host[l].mailbox);
+    IL_CHECK_ARG(A >= 1 && 2 * A <= 16 && S >= 1, "il_act_eval_rows: learner %d: unsupported dims (state_dim=%d, action_dim=%d)", l, S, A);
+    IL_CHECK_ARG(64 + S <= tile_threads(H), "il_act_eval_rows: learner %d: state_dim %d exceeds the %d-thread workgroup", l, S, tile_threads(H));
+    lds = std::max(lds, tile_lds_bytes(round_up16(S + A), H));
+  }
+  if (int rc = il_ensure_lds(k_act_eval_rows, lds)) return rc;
+  {
+    IL_TRACE("k_act_eval_rows", stream_);
+    k_act_eval_rows<<<dim3(ceil_div(max_rows, IL_TILE_R), n_learners), tile_threads(H), lds, (hipStream_t)stream_>>>(learners, max_rows, H);
+  }
+  IL_CHECK_LAUNCH("il_act_eval_rows");
+  return IL_OK;
+}
+
 IL_STAMP_READER(il_debug_stamps_sac)
 IL_TL_READER(il_debug_timeline_sac)
 IL_ST_READER(il_stamps_sac)

@@ -477,6 +477,26 @@ typedef struct il_act_dims {
 } il_act_dims;
 int il_act_step_population_mixed(const il_act_learner* learners /* device */, const il_act_dims* dims_dev, const il_act_dims* dims_host, int32_t n_learners, int32_t hidden,
                                  il_stream_t stream);
+/* Lockstep evaluation: the greedy actions (tanh of the policy mean) of up to max_rows observations per learner - one row per evaluation episode still running - in ONE
+ * launch, grid (ceil(max_rows / 16), n_learners). Learner l reads and answers through its own mailbox, il_eval_mailbox_floats(S_l, A_l, max_rows) floats of pinned host
+ * memory (csrc/act_mail.hpp EvalMail), Sp = roundup4(S), Ap = roundup4(A), T = ceil(max_rows / 16):
+ *   host -> device  [0] commit word = sequence * 64 + flags (as a float, < 2^23), written LAST: it publishes the post
+ *                   [1] n, the rows in use this step (as a float), 0 <= n <= max_rows
+ *                   [8, 8 + max_rows * Sp)                          observation r at [8 + r * Sp, + S)
+ *   device -> host  [8 + max_rows * Sp, + max_rows * Ap)            action r at [.. + r * Ap, + A), written for r < n only
+ *                   [8 + max_rows * (Sp + Ap), + T)                 tile t's echo of the commit word, stored last with system-scope release - by every tile, also one
+ *                                                                   that holds no live row (it writes nothing else)
+ * The launch has no ring, carry or noise and changes nothing on the device: run again without a new post it rewrites the same actions and echoes. Per row the action is
+ * il_actor_act(..., greedy = 1)'s on that observation, bit for bit (so also il_act_step's under IL_ACT_GREEDY). learners: a DEVICE array (8-byte aligned) for the kernel;
+ * learners_host: the same records on the host, from which every refusal is decided before anything is launched and the LDS is sized for the widest learner.
+ * Limits, per learner, are il_actor_act's: hidden a multiple of 64 in 64..256 (one for all learners), 2 * action_dim <= 16, state_dim >= 1 and 64 + state_dim within the
+ * workgroup of max(256, 4 * hidden) threads; 1 <= max_rows <= 1024, 1 <= n_learners <= 65535. IL_ERR_ARG for a null array, pointer or mailbox and a misaligned device
+ * array; IL_ERR_UNSUPPORTED when the widest learner's LDS exceeds the CU's. */
+typedef struct il_eval_learner {
+  const float* actor; float* mailbox; int32_t state_dim, action_dim;
+} il_eval_learner; /* 24 bytes */
+int32_t il_eval_mailbox_floats(int32_t state_dim, int32_t action_dim, int32_t max_rows);
+int il_act_eval_rows(const il_eval_learner* learners /* device */, const il_eval_learner* learners_host, int32_t n_learners, int32_t max_rows, int32_t hidden, il_stream_t stream);
 /* Publish the actor arena (n floats) into snapshot slot (version+1)%3 of `mirror` and advance the version. version_and_counter: device
  * int32[2] = {version, internal completion counter}, zero-initialised. Enqueue after every update (capturable into the update's graph). */
 int il_act_publish(const float* actor, int64_t n, float* mirror, int64_t mirror_stride, int32_t* version_and_counter, il_stream_t stream);

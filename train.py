@@ -16,6 +16,10 @@ one `il_pwil_act_reward_population` coupling launch per lockstep step in front o
 one `il_batch_mix_relabel_population` launch per update between the gathers and the SAC launches, GAIL sweeps whose loss is Mixup (the `GAIL_5_trajectories` and
 `GAIL_10_trajectories` overlays) only under `+sweep.gail_mixup_population=true`: `il_gail_mixup_step_population`, at any `mixup_alpha`, every learner's coefficients under
 its own Philox key and update counter); every other sweep runs its jobs one after another, and says so.
+
+Evaluation: `+evaluation.schedule=sequential` (default: evaluate_agent / evaluate_population, unchanged) or `lockstep` - `evaluation.episodes` seeded copies of the evaluation
+environment per learner (copy k seeded seed + 7919 k, copy 0 the sequential schedule's), all episodes stepped together with ONE il_act_eval_rows launch per lockstep step
+(il.LockstepEvaluator). Lockstep returns are those of the E copies, not of one environment stepped E times; where it cannot be served a `[train] evaluation:` line says why.
 """
 import os
 import sys
@@ -28,8 +32,9 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import imitation_learning_amd as il  # noqa: E402
 from imitation_learning_amd import _lib  # noqa: E402
 from imitation_learning_amd import config as il_config  # noqa: E402
+from imitation_learning_amd.config import EVALUATION_SCHEDULES, eval_env_seed, evaluation_schedule  # noqa: E402,F401
 from imitation_learning_amd.environments import env_dims, make_env  # noqa: E402
-from imitation_learning_amd.evaluation import evaluate_agent, evaluate_population  # noqa: E402
+from imitation_learning_amd.evaluation import evaluate_agent, evaluate_agent_lockstep, evaluate_population, evaluate_population_lockstep  # noqa: E402
 from imitation_learning_amd.models import default_device  # noqa: E402
 from imitation_learning_amd.utils import cycle, lineplot  # noqa: E402
 
@@ -137,9 +142,37 @@ def record_evaluation(cfg, metrics, prefix, step, episode_returns, normalised):
     lineplot(metrics['update_steps'], metrics['Q_values'], filename=f'{prefix}Q_values', yaxis='Q-value', title=f'{cfg.algorithm}: {cfg.env} Q-values')
 
 
-def save_run(cfg, prefix, metrics, actor, critic, log_alpha, discriminator, eval_env):
-  """What a finished run leaves behind (train.py:231-240)."""
-  if cfg.save_trajectories:   # train.py:231-234
+def lockstep_eval_envs(cfg, seed: int, eval_env, env_kw) -> list:
+  """The `evaluation.episodes` evaluation environments of one learner under +evaluation.schedule=lockstep: `eval_env` (already seeded with `seed`) is copy 0, the others
+  are built here and seeded by eval_env_seed. They persist across the evaluations of a run, like eval_env."""
+  envs = [eval_env]
+  for k in range(1, max(int(cfg.evaluation.episodes), 1)):
+    env = make_env(cfg.env, cfg.imitation.absorbing, **env_kw)
+    env.seed(eval_env_seed(seed, k))
+    envs.append(env)
+  return envs
+
+
+def lockstep_evaluator(cfg, actors, each: bool = False):
+  """An il.LockstepEvaluator for `actors` (`each`: a list of them, one per actor - the per_learner sweep schedule) when +evaluation.schedule=lockstep asks for one and
+  il_act_eval_rows serves them all; otherwise None - under `lockstep` with ONE `[train] evaluation:` line for the run that gives the reason (a general actor shape,
+  algorithm=BC's actor outside the limits, more than 1,024 episodes): the run then evaluates sequentially, every learner of it."""
+  if evaluation_schedule(cfg) != 'lockstep': return None
+  rows = max(int(cfg.evaluation.episodes), 1)
+  try:
+    return [il.LockstepEvaluator([a], rows) for a in actors] if each else il.LockstepEvaluator(actors, rows)
+  except NotImplementedError as e:
+    print(f'[train] evaluation: +evaluation.schedule=lockstep cannot be served: {e}; evaluating under the sequential schedule', file=sys.stderr)
+    return None
+
+
+def save_run(cfg, prefix, metrics, actor, critic, log_alpha, discriminator, eval_env, lockstep=None):
+  """What a finished run leaves behind (train.py:231-240). `lockstep`: (evaluator, environments) - the trajectories then come from evaluate_agent_lockstep (which, like
+  evaluate_agent here, renders nothing: `cfg.render` has no effect on either path)."""
+  if cfg.save_trajectories and lockstep is not None:
+    _, trajectories = evaluate_agent_lockstep(actor, lockstep[1], cfg.evaluation.episodes, return_trajectories=True, evaluator=lockstep[0])
+    torch.save(trajectories, f'{prefix}trajectories.pth')
+  elif cfg.save_trajectories:   # train.py:231-234
     _, trajectories = evaluate_agent(actor, eval_env, cfg.evaluation.episodes, return_trajectories=True, render=cfg.render)
     torch.save(trajectories, f'{prefix}trajectories.pth')
   torch.save(dict(actor=actor.state_dict(), critic=critic.state_dict(), log_alpha=log_alpha), f'{prefix}agent.pth')
@@ -175,6 +208,7 @@ def check_handoff(plan, step, runner=None):
 
 def train(cfg, file_prefix: str = '') -> float:
   il_config.validate(cfg)
+  evaluation_schedule(cfg)   # an unknown +evaluation.schedule stops the run here, on every rank
   # ---- data parallelism (BASELINE.json configs[4]): one process per GPU, own environment + replay shard, replicated networks, three gradient
   # all-reduces per update. Launched by torch.distributed.run; rank r seeds everything with seed + r (its data must differ), parameters come from rank 0.
   world = int(cfg.distributed.world_size)
@@ -209,6 +243,11 @@ def train(cfg, file_prefix: str = '') -> float:
 
   if world > 1:   # replicas start from rank 0's initialisation (the per-rank torch seeds differ)
     parallel.broadcast_parameters(parallel.replica_tensors(actor, critic, target_critic, log_alpha, discriminator))
+  # +evaluation.schedule=lockstep: one seeded copy of the evaluation environment per evaluation episode and one launch per lockstep step (rank 0 evaluates)
+  evaluator = lockstep_evaluator(cfg, [actor]) if lead else None
+  lockstep = (evaluator, lockstep_eval_envs(cfg, seed, eval_env, env_kw)) if evaluator is not None else None
+  evaluate = (lambda: evaluate_agent_lockstep(actor, lockstep[1], cfg.evaluation.episodes, evaluator=evaluator)) if lockstep is not None else \
+             (lambda: evaluate_agent(actor, eval_env, cfg.evaluation.episodes))
   metrics = new_metrics()
   score = []
   if cfg.check_time_usage: start_time = time.time()
@@ -219,7 +258,7 @@ def train(cfg, file_prefix: str = '') -> float:
     pretrain_bc(cfg, actor, expert_memory, state_size, action_size)
     if cfg.algorithm == 'BC':
       if cfg.check_time_usage: metrics['pre_training_time'] = time.time() - start_time
-      episode_returns = evaluate_agent(actor, eval_env, cfg.evaluation.episodes)
+      episode_returns = evaluate()
       normalised = normalise(episode_returns)
       metrics.update(test_steps=[0], test_returns=[episode_returns], test_returns_normalized=[list(normalised)])
       if world > 1:   # algorithm=BC has no update block to parallelise: every rank clones on its own, rank 0 reports
@@ -401,7 +440,7 @@ def train(cfg, file_prefix: str = '') -> float:
       dog.grace(0.005 * cfg.evaluation.episodes * env.max_episode_steps, 'evaluation')
     if step % cfg.evaluation.interval == 0 and not cfg.check_time_usage and lead:
       if plan is not None: plan.launcher_wait()
-      episode_returns = evaluate_agent(actor, eval_env, cfg.evaluation.episodes)
+      episode_returns = evaluate()
       normalised = normalise(episode_returns)
       score.append(float(normalised.mean()))
       record_evaluation(cfg, metrics, file_prefix, step, episode_returns, normalised)
@@ -431,7 +470,7 @@ def train(cfg, file_prefix: str = '') -> float:
       dist.destroy_process_group()
       return float('nan')
   if cfg.check_time_usage: metrics['training_time'] = time.time() - start_time
-  save_run(cfg, file_prefix, metrics, actor, critic, log_alpha, discriminator, eval_env)
+  save_run(cfg, file_prefix, metrics, actor, critic, log_alpha, discriminator, eval_env, lockstep)
   if world > 1:
     dist.destroy_process_group()
   return float(np.mean(score)) if score else float('nan')
@@ -618,6 +657,7 @@ def train_sweep(cfgs, prefixes, vary_env: bool = False, noise_ids=None):
     reason = mixed_env_fallback_reason(c) if vary_env and len({x.env for x in cfgs}) > 1 else sweep_fallback_reason(c)
     if reason is not None: raise NotImplementedError(f'train_sweep: {reason}')
   how, schedule = sweep_schedule(cfg0), (cfg0.get('acting', {}) or {}).get('schedule', 'exact')
+  evaluation_schedule(cfg0)
   dev = default_device()
   assert _lib.on_device(torch.empty(0, device=dev)), 'train.py needs a GPU: the update path has no CPU fallback'
   B, env_kw = cfg0.training.batch_size, dict(cfg0.get('synthetic_env', {}) or {})
@@ -668,6 +708,14 @@ def train_sweep(cfgs, prefixes, vary_env: bool = False, noise_ids=None):
     if ln.discriminator is not None and cfg.algorithm not in ('DRIL', 'PWIL', 'AdRIL'): ln.discriminator.eval()   # train.py:147 (the DRIL ensemble keeps its dropout, i.e. train mode, on purpose)
     learners.append(ln)
   plans = [ln.plan for ln in learners]
+
+  # +evaluation.schedule=lockstep: E seeded evaluation environments per learner; under the population schedule ONE evaluator (one launch per lockstep step for all L x E
+  # rows), under per_learner one evaluator per learner - per row the same action either way, so the same bytes
+  lock_all, lock_own = None, None
+  if how == 'population': lock_all = lockstep_evaluator(cfg0, [ln.actor for ln in learners])
+  else: lock_own = lockstep_evaluator(cfg0, [ln.actor for ln in learners], each=True)
+  for ln in learners:
+    ln.eval_envs = lockstep_eval_envs(ln.cfg, ln.cfg.seed, ln.eval_env, env_kw) if lock_all is not None or lock_own is not None else None
 
   if how == 'population':
     pop = il.BatchedPopulationPlan(plans)
@@ -737,7 +785,11 @@ def train_sweep(cfgs, prefixes, vary_env: bool = False, noise_ids=None):
           m['alphas'].append(ln.log_alpha.exp().cpu().numpy()); m['entropies'].append((-p.logp).cpu().numpy()); m['Q_values'].append(p.q.cpu().numpy())
 
     if step % cfg0.evaluation.interval == 0 and not cfg0.check_time_usage:
-      if worker is not None:
+      if lock_all is not None:
+        returns = evaluate_population_lockstep(lock_all, [ln.eval_envs for ln in learners], cfg0.evaluation.episodes)
+      elif lock_own is not None:
+        returns = [evaluate_agent_lockstep(ln.actor, ln.eval_envs, cfg0.evaluation.episodes, evaluator=e) for ln, e in zip(learners, lock_own)]
+      elif worker is not None:
         returns = evaluate_population(worker, [ln.eval_env for ln in learners], cfg0.evaluation.episodes)
       else:
         returns = [evaluate_agent(ln.actor, ln.eval_env, cfg0.evaluation.episodes) for ln in learners]
@@ -755,7 +807,10 @@ def train_sweep(cfgs, prefixes, vary_env: bool = False, noise_ids=None):
   for ln in learners:
     cfg, m = ln.cfg, ln.metrics
     if cfg.check_time_usage: m['training_time'] = time.time() - start_time
-    save_run(cfg, ln.prefix, m, ln.actor, ln.critic, ln.log_alpha, ln.discriminator, ln.eval_env)
+    lockstep = None
+    if lock_all is not None and cfg.save_trajectories: lockstep = (il.LockstepEvaluator([ln.actor], max(int(cfg.evaluation.episodes), 1)), ln.eval_envs)   # one learner's final pass: an evaluator of its own
+    elif lock_own is not None: lockstep = (lock_own[learners.index(ln)], ln.eval_envs)
+    save_run(cfg, ln.prefix, m, ln.actor, ln.critic, ln.log_alpha, ln.discriminator, ln.eval_env, lockstep)
     scores.append(float(np.mean(ln.score)) if ln.score else float('nan'))
   return scores
 

@@ -12,6 +12,8 @@ The reference trains the four in four processes. Here they train in ONE process,
   +sweep.schedule=per_learner  the same driver, learners and seeds through one ActingWorker and one plan.run() per learner: the A/B partner, and the same bits.
 Configurations the population launches do not serve at different widths (PWIL, AdRIL, RED, GMMIL, DRIL, BC, GAIL with Mixup, general shapes, ...:
 `train.mixed_env_fallback_reason`) train environment after environment through `train()` under the same prefixes; a `[train_all]` line on stderr gives the reason.
+`+evaluation.schedule=lockstep` (default `sequential`) is train.py's key and is passed through: every learner then evaluates on `evaluation.episodes` seeded copies of its
+evaluation environment, one il_act_eval_rows launch per lockstep step for all learners and episodes (per learner under `per_learner` and in the fallback).
 
 `python train_all.py -m key=a,b,... algorithm=<ALG>`: the jobs are expanded like Hydra's BASIC sweeper (il.config.compose_multirun: the Cartesian product of the comma
 lists). The reference's train_all_config.yaml selects the Ax sweeper and reads conf/hyperparameter_search_space/<ALG>.yaml; neither exists here: no Ax, and
