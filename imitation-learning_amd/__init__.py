@@ -5,7 +5,7 @@ HIP kernels behind the C ABI in include/il_hip.h).  Import as `imitation_learnin
 the importable alias at the repo root points its package path here).
 """
 from . import _lib  # noqa: F401
-from .acting import ActingWorker, LockstepEvaluator, PopulationActingWorker  # noqa: F401
+from .acting import ActingWorker, GeneralLockstepEvaluator, LockstepEvaluator, PopulationActingWorker  # noqa: F401
 from .evaluation import evaluate_agent_lockstep, evaluate_population_lockstep  # noqa: F401
 from .memory import IndexStream, ReplayMemory, seed  # noqa: F401
 from .models import (DropoutSoftActor, GAILDiscriminator, GMMILDiscriminator, PWILDiscriminator, REDDiscriminator, RewardRelabeller, SoftActor, TwinCritic, create_target_network,  # noqa: F401

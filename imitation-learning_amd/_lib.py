@@ -220,6 +220,7 @@ _SIGNATURES = {
     'il_act_publish': (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P]),
     'il_eval_mailbox_floats': (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
     'il_act_eval_rows': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),   # (learners_dev, learners_host, n_learners, max_rows, hidden, stream)
+    'il_act_eval_rows_general': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),   # (learners_dev, learners_host, n_learners, max_rows, hidden, depth, activation, stream)
     'il_disc_workspace_floats': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     'il_gail_disc_step': (C.c_int, [C.POINTER(Disc), C.POINTER(Batch), C.POINTER(Batch), _P, C.POINTER(GailExtra), C.c_uint32, _P]),
     'il_disc_deep_numel': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),

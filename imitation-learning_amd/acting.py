@@ -366,6 +366,28 @@ def lockstep_refusal(actor, max_rows: int = 1):
   return None
 
 
+def general_lockstep_refusal(actor, max_rows: int = 1):
+  """None when `il_act_eval_rows_general` serves this actor; otherwise the predicate it misses, in words (GeneralLockstepEvaluator raises it, train.py prints it and
+  evaluates sequentially). An object that is not a general-shape actor (`general` not true: a fused actor, or anything without the attribute) gets a reason and nothing
+  else of it is read. For a general actor this restates the tile-engine predicate of il_actor_act_general (csrc/general.hip gt_env() && gt_shape_ok) from the actor's
+  fields - the entry point has no layer-at-a-time form - with IL_GENERAL_TILES read as gt_env reads it: set, and its first character is `0`. The entry point itself checks
+  all of it again on every launch."""
+  import os
+  if not getattr(actor, 'general', False):
+    return 'not a general-shape actor (the fused shape - depth 2 / ReLU / hidden 64..256 in multiples of 64 - is served by il_act_eval_rows: LockstepEvaluator)'
+  from .models import ACTIVATION_IDS
+  H, S, A, depth = actor.hidden, actor.state_size, actor.action_size, actor.depth
+  if not 1 <= depth <= 8: return f'depth {depth} is outside 1..8'
+  if actor.activation not in ACTIVATION_IDS: return f'activation {actor.activation} is none of {sorted(ACTIVATION_IDS)}'
+  if H % 16 != 0 or not 16 <= H <= 512:
+    return f'hidden {H} is not a multiple of 16 in 16..512 (the one-launch tile engine; il_act_eval_rows_general has no layer-at-a-time form)'
+  if not 1 <= S <= 512: return f'state_size {S} is outside 1..512 (the one-launch tile engine; il_act_eval_rows_general has no layer-at-a-time form)'
+  if not 1 <= A <= 8: return f'action_size {A} is outside 1..8 (the one-launch tile engine; il_act_eval_rows_general has no layer-at-a-time form)'
+  if os.environ.get('IL_GENERAL_TILES', '')[:1] == '0': return 'IL_GENERAL_TILES=0 switches the tile engine off (il_act_eval_rows_general has no layer-at-a-time form)'
+  if not 1 <= max_rows <= 1024: return f'max_rows {max_rows} is outside 1..1024'
+  return None
+
+
 class LockstepEvaluator:
   """The greedy actions of up to `max_rows` observations per learner - one row per evaluation episode still running - in ONE `il_act_eval_rows` launch per lockstep step,
   for one `SoftActor` or several (one hidden size; their state / action widths may differ). Owns the mailboxes (one pinned block, learner l's laid out as
@@ -373,18 +395,32 @@ class LockstepEvaluator:
   the predicate (`lockstep_refusal`). The launch reads live parameters and changes nothing on the device; nothing of the acting workers is touched.
 
   Pinned-memory lifetime (the rule of `_drain`): `act` returns with the echoes of the tiles that hold live rows; the tiles without one only echo, and may do so a little
-  later. The next `act` waits for those before it posts (so a launch only ever sees its own post), and the evaluator waits for them before it lets go of the block."""
+  later. The next `act` waits for those before it posts (so a launch only ever sees its own post), and the evaluator waits for them before it lets go of the block.
+
+  `GeneralLockstepEvaluator` is this class with three hooks replaced: the refusal predicate, what the learners have to share, and the library call."""
+
+  _entry = 'il_act_eval_rows'
+
+  def _refusal(self, actor, max_rows: int):
+    return lockstep_refusal(actor, max_rows)
+
+  def _shares_shape(self, a, a0):
+    assert a.hidden == a0.hidden, f'LockstepEvaluator: one hidden size for all learners (got {a0.hidden} and {a.hidden})'
+
+  def _call(self, lib, stream):
+    return lib.il_act_eval_rows(_lib.ptr(self._descs), C.cast(self._descs_host, C.c_void_p), self.L, self.max_rows, self.H, stream)
 
   def __init__(self, actors, max_rows: int):
     actors = list(actors) if isinstance(actors, (list, tuple)) else [actors]
     max_rows = int(max_rows)
-    assert len(actors) >= 1, 'LockstepEvaluator: at least one actor'
+    who = type(self).__name__
+    assert len(actors) >= 1, f'{who}: at least one actor'
     a0 = actors[0]
     for l, a in enumerate(actors):
-      reason = lockstep_refusal(a, max_rows)
-      if reason is not None: raise NotImplementedError(f'LockstepEvaluator: learner {l}: {reason}')
-      assert _lib.on_device(a.flat), 'LockstepEvaluator needs the actors on the GPU (there is no CPU path)'
-      assert a.hidden == a0.hidden, f'LockstepEvaluator: one hidden size for all learners (got {a0.hidden} and {a.hidden})'
+      reason = self._refusal(a, max_rows)
+      if reason is not None: raise NotImplementedError(f'{who}: learner {l}: {reason}')
+      assert _lib.on_device(a.flat), f'{who} needs the actors on the GPU (there is no CPU path)'
+      self._shares_shape(a, a0)
       assert a.flat.device == a0.flat.device
     from .training import _device_array
     lib = _lib.lib()
@@ -429,21 +465,21 @@ class LockstepEvaluator:
         torch.cuda.synchronize()  # surfaces an asynchronous launch failure, if that is what happened
         raise RuntimeError(f'{what}: no echo from the device after {timeout_s:.0f} s (commit word {word}, echoes hold {flat[where].tolist()})')
 
-  def wait(self, what: str = 'il_act_eval_rows'):
+  def wait(self, what: str = None):
     """Every tile's echo of the last launched post, those without a live row included: behind it no workgroup of that launch reads or writes the block any more. Nothing
     to wait for when no launch is outstanding (a post that was never launched, or whose launch the entry point refused)."""
     if not self._in_flight: return
-    self._wait(self._echo.reshape(-1), what)
+    self._wait(self._echo.reshape(-1), what or self._entry)
     self._in_flight = False
 
   def post(self, obs_per_learner) -> list:
     """Pack learner l's observations into rows [0, n_l) of its mailbox, then the row counts, then - last - the L commit words. Returns the row counts."""
-    assert len(obs_per_learner) == self.L, f'LockstepEvaluator: one entry per learner ({self.L}), got {len(obs_per_learner)}'
+    assert len(obs_per_learner) == self.L, f'{type(self).__name__}: one entry per learner ({self.L}), got {len(obs_per_learner)}'
     self.wait()
     counts = []
     for l, rows in enumerate(obs_per_learner):
       n = 0 if rows is None else len(rows)
-      assert n <= self.max_rows, f'LockstepEvaluator: learner {l} has {n} rows, the mailbox holds {self.max_rows}'
+      assert n <= self.max_rows, f'{type(self).__name__}: learner {l} has {n} rows, the mailbox holds {self.max_rows}'
       if n:
         S = self.widths[l][0]
         if torch.is_tensor(rows): rows = rows.detach().to('cpu', torch.float32).numpy()
@@ -455,12 +491,12 @@ class LockstepEvaluator:
     return counts
 
   def launch(self):
-    """ONE il_act_eval_rows on the current stream (what to act on is read from the mailboxes)."""
+    """ONE il_act_eval_rows (il_act_eval_rows_general) on the current stream (what to act on is read from the mailboxes)."""
     if any(a.flat.data_ptr() != p for a, p in zip(self.actors, self._arenas)):   # an arena was re-homed: re-derive the descriptors
       from .training import _device_array
       for l, a in enumerate(self.actors): self._descs_host[l].actor = a.flat.data_ptr()
       self._descs, self._arenas = _device_array(list(self._descs_host), self.device), [a.flat.data_ptr() for a in self.actors]
-    rc = _lib.lib().il_act_eval_rows(_lib.ptr(self._descs), C.cast(self._descs_host, C.c_void_p), self.L, self.max_rows, self.H, torch.cuda.current_stream().cuda_stream)
+    rc = self._call(_lib.lib(), torch.cuda.current_stream().cuda_stream)
     if rc: _lib.check(rc)
     self._in_flight = True
 
@@ -470,7 +506,7 @@ class LockstepEvaluator:
     counts = self.post(obs_per_learner)
     self.launch()
     live = [self._echo[l, :(n + 15) // 16] for l, n in enumerate(counts) if n]
-    if live: self._wait(np.concatenate(live), 'il_act_eval_rows')
+    if live: self._wait(np.concatenate(live), self._entry)
     out = []
     for l, n in enumerate(counts):
       self.actors[l]._act_calls += n
@@ -481,6 +517,28 @@ class LockstepEvaluator:
     if getattr(self, '_in_flight', False):
       try: self.wait()
       except RuntimeError: pass   # no echo within the bound (a failed launch): nothing left to protect, and __del__ must not raise
+
+
+class GeneralLockstepEvaluator(LockstepEvaluator):
+  """`LockstepEvaluator` for general actor shapes: ONE `il_act_eval_rows_general` launch per lockstep step (csrc/general.hip k_act_eval_rows_general: the tile engine's
+  forward on every 16-row tile). The same mailboxes, posts, waits and pinned-memory rules; per row the action is `get_greedy_action`'s (il_actor_act_general, greedy), bit
+  for bit. Serves the shapes that entry point runs as one launch (`general_lockstep_refusal`); the learners share one (hidden, depth, activation), their state / action
+  widths may differ. A fused-shape actor, a shape outside the tile engine and learners of different shapes raise NotImplementedError with the reason."""
+
+  _entry = 'il_act_eval_rows_general'
+
+  def _refusal(self, actor, max_rows: int):
+    return general_lockstep_refusal(actor, max_rows)
+
+  def _shares_shape(self, a, a0):
+    mine, first = (a.hidden, a.depth, a.activation), (a0.hidden, a0.depth, a0.activation)
+    if mine != first:
+      raise NotImplementedError(f'GeneralLockstepEvaluator: one (hidden, depth, activation) for all learners of a launch (got {first} and {mine})')
+
+  def _call(self, lib, stream):
+    from .models import ACTIVATION_IDS
+    a0 = self.actors[0]
+    return lib.il_act_eval_rows_general(_lib.ptr(self._descs), C.cast(self._descs_host, C.c_void_p), self.L, self.max_rows, self.H, a0.depth, ACTIVATION_IDS[a0.activation], stream)
 
 
 class PopulationActingWorker:

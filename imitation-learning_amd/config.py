@@ -196,7 +196,7 @@ EVAL_SEED_STRIDE = 7919
 def evaluation_schedule(cfg) -> str:
   """`+evaluation.schedule=sequential` (default): evaluate_agent / evaluate_population - the episodes of an evaluation one after another on ONE evaluation environment, a
   launch and a turn-around per episode step. `lockstep`: `evaluation.episodes` seeded copies of the evaluation environment per learner (lockstep_eval_envs), all episodes
-  stepped together, ONE il_act_eval_rows launch per lockstep step (evaluate_agent_lockstep / evaluate_population_lockstep). The returns under `lockstep` are those of the
+  stepped together, ONE il_act_eval_rows (general actor shapes: il_act_eval_rows_general) launch per lockstep step (evaluate_agent_lockstep / evaluate_population_lockstep). The returns under `lockstep` are those of the
   E seeded copies, not of one environment stepped E times: an opt-in, and training itself is the same bits under both."""
   schedule = (cfg.get('evaluation', {}) or {}).get('schedule', EVALUATION_DEFAULT_SCHEDULE)
   assert schedule in EVALUATION_SCHEDULES, f'+evaluation.schedule={schedule}: expected one of {EVALUATION_SCHEDULES}'

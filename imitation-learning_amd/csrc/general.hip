@@ -1308,4 +1308,66 @@ extern "C" int il_act_step_general(const float* actor, int32_t S, int32_t A, int
   IL_CHECK_LAUNCH("il_act_step_general");
   return IL_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------------------------
+// Lockstep evaluation for the tile-engine shapes (evaluation.py evaluate_agent_lockstep; sac.hip k_act_eval_rows is the fused shape's): the greedy actions of up to max_rows
+// observations per learner in ONE launch. grid = (16-row tiles, learners); workgroup (t, l) reads learner l's post (act_mail.hpp EvalMail), runs gt_fwd_tile on the live rows
+// of tile t in learner l's own LDS layout (the allocation is the widest learner's) with the weights read directly (PF null, as k_gt_fwd runs for il_actor_act_general and
+// k_act_step_general runs: per row the action is il_actor_act_general(greedy = 1)'s, bit for bit - a row's value depends neither on its tile nor on its slot in it), and
+// stores tanh(mean) for them; rows >= n are left alone. The head keeps its values in registers: nothing of it lives in LDS, so there is no scratch that could alias Os
+// (k_act_step_general's rule; k_gt_fwd's log-probability scratch once did at H == 16). Every tile, live or not, ends with its echo of the commit word. No ring, no carry,
+// no Philox draw: nothing on the device changes, so a launch that runs again without a new post rewrites the same actions and echoes.
+// ---------------------------------------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(512) void k_act_eval_rows_general(const il_eval_learner* __restrict__ learners, int max_rows, int H, int depth, int act) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const il_eval_learner d = learners[blockIdx.y];
+  const int S = d.state_dim, A = d.action_dim, tid = threadIdx.x;
+  const EvalMail<float> m = eval_mail(d.mailbox, S, A, max_rows);
+  const float commit = d.mailbox[EVAL_MAIL_COMMIT];
+  const int n = min(max((int)d.mailbox[EVAL_MAIL_ROWS], 0), max_rows);   // (clamped: whatever the word holds, no row outside the blocks is touched)
+  const int row0 = blockIdx.x * 16, nrows = min(16, n - row0);
+  if (nrows > 0) {  // block-uniform
+    const GtNet nn = {d.actor, S, H, depth, 2 * A, act, nullptr, nullptr};
+    const GtTile t = gt_fwd_tile(smem, nn, m.obs(), m.ld_obs, S, nullptr, 0, 0, nullptr, nullptr, 16, row0, nrows, false);   // (barriers inside: Os is complete for every thread)
+    if (tid < 16 * A) {
+      const int r = tid / A, c = tid - r * A;
+      if (r < nrows) m.act()[(size_t)(row0 + r) * m.ld_act + c] = tanhf(t.Os[r * 16 + c]);
+    }
+  }
+  __threadfence_system();
+  __syncthreads();
+  if (tid == 0) __hip_atomic_store(m.echo() + blockIdx.x, commit, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+extern "C" int il_act_eval_rows_general(const il_eval_learner* learners, const il_eval_learner* learners_host, int32_t n_learners, int32_t max_rows, int32_t H, int32_t depth, int32_t activation,
+                                        il_stream_t stream_) {
+  IL_CHECK_ARG(learners && learners_host, "il_act_eval_rows_general: null array (device descriptors %p, host descriptors %p)", (const void*)learners, (const void*)learners_host);
+  IL_CHECK_ARG(((uintptr_t)learners & 7u) == 0, "il_act_eval_rows_general: the device descriptor array %p is not 8-byte aligned", (const void*)learners);
+  IL_CHECK_ARG(n_learners >= 1 && n_learners <= 65535, "il_act_eval_rows_general: n_learners=%d must be in [1,65535]", n_learners);
+  IL_CHECK_ARG(max_rows >= 1 && max_rows <= 1024, "il_act_eval_rows_general: max_rows=%d must be in [1,1024]", max_rows);
+  size_t lds = 0;
+  for (int l = 0; l < n_learners; ++l) {   // every refusal, for every learner, ahead of the launch
+    const int S = learners_host[l].state_dim, A = learners_host[l].action_dim;
+    IL_CHECK_ARG(learners_host[l].actor && learners_host[l].mailbox, "il_act_eval_rows_general: learner %d: null pointer (actor %p, mailbox %p)", l, (const void*)learners_host[l].actor,
+                 (const void*)learners_host[l].mailbox);
+    IL_CHECK_ARG(A >= 1 && A <= 1024 && S >= 1, "il_act_eval_rows_general: learner %d: unsupported dims (state_dim=%d, action_dim=%d)", l, S, A);
+    const GNet an = {S, H, depth, 2 * A, activation};
+    char who[64];
+    snprintf(who, sizeof who, "il_act_eval_rows_general: learner %d", l);
+    if (int rc = g_check_shape(an, who)) return rc;
+    // the predicate of il_actor_act_general's tile-engine branch: a shape it would run a layer at a time has no form here (several launches reading one post across a grid
+    // of tiles is a different protocol) - such a shape keeps evaluating sequentially
+    if (!(gt_env() && gt_shape_ok(an)))
+      return il_set_error(IL_ERR_UNSUPPORTED, "il_act_eval_rows_general: learner %d: outside the one-launch form (hidden a multiple of 16 in 16..512, state_dim <= 512, action_dim <= 8%s; got "
+                          "state_dim=%d hidden=%d action_dim=%d): no layer-at-a-time form", l, gt_env() ? "" : ", IL_GENERAL_TILES != 0", S, H, A);
+    lds = gt_fwd_lds(an) > lds ? gt_fwd_lds(an) : lds;
+  }
+  if (int rc = il_ensure_lds(k_act_eval_rows_general, lds)) return rc;
+  {
+    IL_TRACE("k_act_eval_rows_general", (hipStream_t)stream_);
+    k_act_eval_rows_general<<<dim3((max_rows + 15) / 16, n_learners), gt_threads(H), lds, (hipStream_t)stream_>>>(learners, max_rows, H, depth, activation);
+  }
+  IL_CHECK_LAUNCH("il_act_eval_rows_general");
+  return IL_OK;
+}
 IL_STAMP_READER(il_debug_stamps_general)

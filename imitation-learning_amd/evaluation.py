@@ -7,7 +7,8 @@ known from env.max_episode_steps) instead of python lists of 1-row tensors.
 `evaluate_population` evaluates the L learners of a `PopulationActingWorker` in lockstep: one `il_act_step_population` launch per evaluation step for all of them.
 
 `evaluate_agent_lockstep` / `evaluate_population_lockstep` (`+evaluation.schedule=lockstep`) step ALL episodes of an evaluation in lockstep, one seeded environment per
-episode: one `il_act_eval_rows` launch per lockstep step for every row of every learner (`LockstepEvaluator`). Their returns are those of E seeded copies of the evaluation
+episode: one `il_act_eval_rows` launch per lockstep step for every row of every learner (`LockstepEvaluator`; general actor shapes: `il_act_eval_rows_general`,
+`GeneralLockstepEvaluator`). Their returns are those of E seeded copies of the evaluation
 environment, not of one environment stepped E times; `evaluate_agent` and `evaluate_population` are what they were.
 """
 import torch
@@ -93,9 +94,9 @@ def evaluate_agent_lockstep(actor, envs, num_episodes: int, return_trajectories:
   (`il.LockstepEvaluator`; pass one to reuse its mailbox across evaluations, it must serve `actor` alone) instead of one `get_greedy_action` turn-around per episode and
   step. Per row the action is `get_greedy_action`'s, bit for bit, so episode k's return is what `evaluate_agent(actor, envs[k], 1)` gives - the returns are those of
   `num_episodes` seeded environments, NOT those of one environment stepped `num_episodes` times. `actor._act_calls` advances by the steps taken."""
-  if evaluator is None:
-    from .acting import LockstepEvaluator
-    evaluator = LockstepEvaluator([actor], max(int(num_episodes), 1))
+  if evaluator is None:   # a general actor shape: il_act_eval_rows_general (per row il_actor_act_general's greedy action, which is what its get_greedy_action runs)
+    from .acting import GeneralLockstepEvaluator, LockstepEvaluator
+    evaluator = (GeneralLockstepEvaluator if getattr(actor, 'general', False) else LockstepEvaluator)([actor], max(int(num_episodes), 1))
   assert evaluator.L == 1 and evaluator.actors[0] is actor, 'evaluate_agent_lockstep: the evaluator serves this actor alone (several learners: evaluate_population_lockstep)'
   logs = _lockstep_logs(evaluator, [envs], num_episodes, return_trajectories)[0]
   returns = [log.total for log in logs]

@@ -50,7 +50,8 @@ def _mlp_shape(model_cfg, what):
   """(hidden, depth, activation, general) of an actor / critic network (models.py:48-69 `_create_fcnn` builds any depth with relu / tanh / sigmoid). general = False: the
   shape of every shipped configuration (depth 2, ReLU, hidden 64 .. 256), which the fused kernels of csrc/sac.hip run; True: any other shape, composed a layer at a time
   by csrc/general.hip (sac_update, acting, log_prob, behavioural cloning; a one-stream `UpdatePlan`; `ActingWorker` through il_act_step_general - one launch per environment step
-  where the tile engine applies, layer-at-a-time launches plus a commit kernel otherwise; no population or data-parallel form)."""
+  where the tile engine applies, layer-at-a-time launches plus a commit kernel otherwise; lockstep evaluation through il_act_eval_rows_general - `GeneralLockstepEvaluator`,
+  one launch per lockstep step - where the tile engine applies, the sequential schedule otherwise; no population or data-parallel form)."""
   depth, act, hidden = int(_cfg_get(model_cfg, 'depth')), str(_cfg_get(model_cfg, 'activation')), int(_cfg_get(model_cfg, 'hidden_size'))
   if _cfg_get(model_cfg, 'input_dropout', 0) or _cfg_get(model_cfg, 'dropout', 0):
     raise NotImplementedError(f'{what}: dropout networks (DRIL) are outside the HIP hot path')

@@ -497,6 +497,20 @@ typedef struct il_eval_learner {
 } il_eval_learner; /* 24 bytes */
 int32_t il_eval_mailbox_floats(int32_t state_dim, int32_t action_dim, int32_t max_rows);
 int il_act_eval_rows(const il_eval_learner* learners /* device */, const il_eval_learner* learners_host, int32_t n_learners, int32_t max_rows, int32_t hidden, il_stream_t stream);
+/* il_act_eval_rows for the general actor shapes of il_actor_act_general: the same il_eval_learner records, the same mailbox (il_eval_mailbox_floats; layout, commit
+ * word, row count n clamped to [0, max_rows], actions for r < n only and never their padding, every tile's echo stored last with system-scope release), the same
+ * replay rule (nothing on the device changes), in ONE launch (k_act_eval_rows_general), grid (ceil(max_rows / 16), n_learners), max(256, min(512, 4 * hidden)) threads.
+ * One (hidden, depth, activation) for all learners (activation 0 relu / 1 tanh / 2 sigmoid); state and action widths per learner. Per row the action is
+ * il_actor_act_general(..., greedy = 1)'s on that observation, bit for bit, whatever tile and row slot it sits in (so also il_act_step_general's form (a) under
+ * IL_ACT_GREEDY) - NOT il_act_eval_rows's: a fused shape stays with that entry point, whose arithmetic differs.
+ * Limits, per learner, are those of il_actor_act_general's one-launch branch (form (a) of il_act_step_general): hidden a multiple of 16 in 16..512, state_dim <= 512,
+ * 2 * action_dim <= 16, depth 1-8, IL_GENERAL_TILES != 0; 1 <= max_rows <= 1024, 1 <= n_learners <= 65535. Every refusal is decided from learners_host before anything is
+ * launched: IL_ERR_ARG for a null array, pointer or mailbox, a misaligned device array, n_learners, max_rows, state_dim / action_dim < 1 and a shape outside the general
+ * entry points altogether (depth 0 or 9, activation 3, widths > 2048); IL_ERR_UNSUPPORTED, naming the learner, for a shape those admit but the one-launch branch does not
+ * (hidden 40 or 528, state_dim 513, action_dim 9, IL_GENERAL_TILES=0) - there is no layer-at-a-time form: several launches reading one post across a grid of tiles would
+ * be a different protocol - and when the widest learner's LDS exceeds the CU's. */
+int il_act_eval_rows_general(const il_eval_learner* learners /* device */, const il_eval_learner* learners_host, int32_t n_learners, int32_t max_rows, int32_t hidden, int32_t depth,
+                             int32_t activation, il_stream_t stream);
 /* Publish the actor arena (n floats) into snapshot slot (version+1)%3 of `mirror` and advance the version. version_and_counter: device
  * int32[2] = {version, internal completion counter}, zero-initialised. Enqueue after every update (capturable into the update's graph). */
 int il_act_publish(const float* actor, int64_t n, float* mirror, int64_t mirror_stride, int32_t* version_and_counter, il_stream_t stream);

@@ -10,7 +10,11 @@ faster only where its median beats the sequential median by more than the sequen
 limit of its own, chained so that the first failure ends the job; every part appends to the same file:
   timeout -k 10 300 python profiles/tools/eval_ab.py --part agent --out profiles/eval_ab.txt --fresh && \\
   timeout -k 10 420 python profiles/tools/eval_ab.py --part population --out profiles/eval_ab.txt && \\
-  timeout -k 10 300 python profiles/tools/eval_ab.py --part train --out profiles/eval_ab.txt"""
+  timeout -k 10 300 python profiles/tools/eval_ab.py --part train --out profiles/eval_ab.txt
+`--actor DEPTH ACTIVATION HIDDEN` (part agent) times another actor shape - a general one goes through il.GeneralLockstepEvaluator (ONE il_act_eval_rows_general launch per
+lockstep step) against the same untouched sequential code; without it the shape is the default's and the three commands above reproduce the file as it was:
+  timeout -k 10 300 python profiles/tools/eval_ab.py --part agent --actor 3 tanh 256 --out profiles/eval_ab.txt && \\
+  timeout -k 10 420 python profiles/tools/eval_ab.py --part agent --actor 8 tanh 512 --out profiles/eval_ab.txt"""
 import argparse
 import os
 import sys
@@ -37,10 +41,13 @@ def say(text):
     with open(out_path, 'a') as f: f.write(text + '\n')
 
 
+ACTOR = []   # --actor: overrides of reinforcement.actor (empty: the default shape)
+
+
 def actor_of(seed):
   S, A = env_dims(ENV, True)
   torch.manual_seed(seed)
-  return il.SoftActor(S, A, config.compose(['algorithm=SAC']).reinforcement.actor)
+  return il.SoftActor(S, A, config.compose(['algorithm=SAC'] + ACTOR).reinforcement.actor)
 
 
 def envs_of(seed, copies, horizon):
@@ -73,13 +80,14 @@ def report(title, secs):
 def part_agent(args):
   actor, E, T = actor_of(1), args.episodes, args.horizon
   seq_env, lock_envs = envs_of(1, 1, T)[0], envs_of(1, E, T)
-  evaluator = il.LockstepEvaluator([actor], E)
+  evaluator = (il.GeneralLockstepEvaluator if actor.general else il.LockstepEvaluator)([actor], E)
   forms = dict(sequential=lambda: evaluate_agent(actor, seq_env, E), lockstep=lambda: il.evaluate_agent_lockstep(actor, lock_envs, E, evaluator=evaluator))
   for fn in forms.values(): fn()   # warm-up: code objects, allocator
   secs = {k: [] for k in forms}
   for _ in range(args.repeats):
     for k, fn in forms.items(): secs[k].append(timed(fn))   # interleaved: a drift of the machine hits both alike
-  report(f'one learner: evaluate_agent against evaluate_agent_lockstep, {E} episodes, horizon {T} ({E * T} greedy steps)', secs)
+  shape = f' [actor depth {actor.depth} / {actor.activation} / hidden {actor.hidden}: {type(evaluator).__name__}]' if ACTOR else ''
+  report(f'one learner: evaluate_agent against evaluate_agent_lockstep, {E} episodes, horizon {T} ({E * T} greedy steps){shape}', secs)
 
 
 def part_population(args):
@@ -132,10 +140,14 @@ def main(argv=None):
   ap.add_argument('--learners', type=int, nargs='+', default=[4, 16])
   ap.add_argument('--train-steps', type=int, default=20000)
   ap.add_argument('--train-repeats', type=int, default=2)
+  ap.add_argument('--actor', nargs=3, metavar=('DEPTH', 'ACTIVATION', 'HIDDEN'), default=None, help='part agent: the actor shape (default: that of the configuration, depth 2 / relu / 256)')
   ap.add_argument('--out', default=None)
   ap.add_argument('--fresh', action='store_true', help='start the output file anew (the first part of a job)')
   args = ap.parse_args(argv)
   global out_path
+  if args.actor:
+    assert args.part == 'agent', '--actor: part agent only'
+    ACTOR[:] = [f'reinforcement.actor.depth={int(args.actor[0])}', f'reinforcement.actor.activation={args.actor[1]}', f'reinforcement.actor.hidden_size={int(args.actor[2])}']
   if args.out:
     out_path = os.path.abspath(args.out)
     os.makedirs(os.path.dirname(out_path), exist_ok=True)

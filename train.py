@@ -19,7 +19,8 @@ its own Philox key and update counter); every other sweep runs its jobs one afte
 
 Evaluation: `+evaluation.schedule=sequential` (default: evaluate_agent / evaluate_population, unchanged) or `lockstep` - `evaluation.episodes` seeded copies of the evaluation
 environment per learner (copy k seeded seed + 7919 k, copy 0 the sequential schedule's), all episodes stepped together with ONE il_act_eval_rows launch per lockstep step
-(il.LockstepEvaluator). Lockstep returns are those of the E copies, not of one environment stepped E times; where it cannot be served a `[train] evaluation:` line says why.
+(il.LockstepEvaluator; a general actor shape inside the one-launch tile engine: il_act_eval_rows_general, il.GeneralLockstepEvaluator). Lockstep returns are those of the E
+copies, not of one environment stepped E times; where neither launch serves the run a `[train] evaluation:` line says why.
 """
 import os
 import sys
@@ -154,16 +155,22 @@ def lockstep_eval_envs(cfg, seed: int, eval_env, env_kw) -> list:
 
 
 def lockstep_evaluator(cfg, actors, each: bool = False):
-  """An il.LockstepEvaluator for `actors` (`each`: a list of them, one per actor - the per_learner sweep schedule) when +evaluation.schedule=lockstep asks for one and
-  il_act_eval_rows serves them all; otherwise None - under `lockstep` with ONE `[train] evaluation:` line for the run that gives the reason (a general actor shape,
-  algorithm=BC's actor outside the limits, more than 1,024 episodes): the run then evaluates sequentially, every learner of it."""
+  """An evaluator for `actors` (`each`: a list of them, one per actor - the per_learner sweep schedule) when +evaluation.schedule=lockstep asks for one: an
+  il.LockstepEvaluator when il_act_eval_rows serves them all (the fused actor shape); when it refuses, an il.GeneralLockstepEvaluator, built the same way, when
+  il_act_eval_rows_general does (general shapes inside the one-launch tile engine: hidden a multiple of 16 up to 512, state <= 512, action <= 8, one shape for all).
+  Otherwise None - under `lockstep` with ONE `[train] evaluation:` line for the run that gives both reasons (a shape only the layer-at-a-time kernels run,
+  IL_GENERAL_TILES=0, fused and general actors mixed, more than 1,024 episodes): the run then evaluates sequentially, every learner of it."""
   if evaluation_schedule(cfg) != 'lockstep': return None
   rows = max(int(cfg.evaluation.episodes), 1)
+  build = lambda cls: [cls([a], rows) for a in actors] if each else cls(actors, rows)
   try:
-    return [il.LockstepEvaluator([a], rows) for a in actors] if each else il.LockstepEvaluator(actors, rows)
-  except NotImplementedError as e:
-    print(f'[train] evaluation: +evaluation.schedule=lockstep cannot be served: {e}; evaluating under the sequential schedule', file=sys.stderr)
-    return None
+    return build(il.LockstepEvaluator)
+  except NotImplementedError as fused:
+    try:
+      return build(il.GeneralLockstepEvaluator)
+    except NotImplementedError as general:
+      print(f'[train] evaluation: +evaluation.schedule=lockstep cannot be served: {fused}; {general}; evaluating under the sequential schedule', file=sys.stderr)
+      return None
 
 
 def save_run(cfg, prefix, metrics, actor, critic, log_alpha, discriminator, eval_env, lockstep=None):
